@@ -10,7 +10,9 @@ configs/OCRNet_rf_lvsz.json: ResNet50, output stride 8).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  A plain run sets up, warms up, times the K steps and prints the line;
+--full adds everything else the line can carry (roofline steps, side figures, CPU baseline; each still off with its --no-* option).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -274,10 +276,14 @@ def infer_bench(args):
     model.get_features = False
     img, lbl = synth_batch(B, H, W, 25, 2000 + rank, dev)
     cm = torch.zeros((25, 25), dtype=torch.int32, device=dev)
+    last = {}       # --dump-outputs: the logits of the latest step
 
     def step():
         with torch.no_grad():
-            t_get_confusion_matrix(model(img), lbl, cm)
+            out = model(img)
+            t_get_confusion_matrix(out, lbl, cm)
+        if args.dump_outputs:
+            last["logits"] = out
 
     def barrier():
         torch.cuda.synchronize()
@@ -296,6 +302,9 @@ def infer_bench(args):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's logits, and this rank's confusion matrix accumulated over the warm-up and timed steps
+        _dump(args, {"logits": last["logits"], "confusion_matrix": cm})
     roof = None
     if not args.no_roofline and rank == 0:
         # HIP events around every convolution launch of two more steps (forward only: the fused conv + folded-BN + ReLU kernels)
@@ -352,6 +361,35 @@ def infer_bench(args):
         dist.destroy_process_group()
 
 
+DUMP_SAMPLE = 1 << 21      # --dump-outputs: elements per file at most (8 MB of float32)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every tensor of `arrays` ({name: tensor}) as path/<name>.npy -- float32, or float64 for integer counts and fp64
+    tensors.  A tensor of more than DUMP_SAMPLE elements is written flattened, as its elements at DUMP_SAMPLE fixed positions (sorted,
+    drawn from a generator seeded with 0: the same positions for every tensor of that size, in every run and every build).  Returns
+    {name: bytes written}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy()
+        a = a.astype(np.float64 if (a.dtype == np.float64 or not np.issubdtype(a.dtype, np.floating)) else np.float32)
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = a.nbytes
+    return written
+
+
+def _dump(args, arrays):
+    written = dump_outputs(args.dump_outputs, arrays)
+    print("bench: --dump-outputs wrote %s to %s (%.1f MB)" % (", ".join("%s.npy" % n for n in written), args.dump_outputs,
+                                                             sum(written.values()) / 1e6), file=sys.stderr)
+
+
 _RESULT_OUT = None
 
 
@@ -395,7 +433,16 @@ def main():
     ap.add_argument("--with-h2d", action="store_true",
                     help="side measurement (never the reported `value` of the contract): every step also copies its batch from "
                          "pinned host memory, float32 image + int64 labels as the reference's loader hands them over")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, after the timed steps: the roofline steps, the side figures "
+                         "and the CPU baseline (each can still be left out with its --no-* option).  Without --full none of them runs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_roofline = args.no_side_figures = args.no_cpu_baseline = True
     _claim_stdout()
 
     if args.infer:
@@ -445,6 +492,7 @@ def main():
     from miccai2021_cataract_semantic_segmentation_amd.graph import GraphedTrainStep
     graphed = {"step": None, "key": None, "captures": 0, "capture_s": 0.0}
     use_graph = [not args.eager and not args.with_h2d]
+    last = {}       # --dump-outputs: the outputs of the latest eager step (a replayed step keeps its own: graphed["step"].outputs)
 
     def drop_graph():
         if graphed["step"] is not None:
@@ -490,6 +538,8 @@ def main():
         loss.backward()
         opt.step()
         t_get_confusion_matrix(final.detach(), y, cm)
+        if args.dump_outputs:
+            last["out"] = (interm, final.detach()) if deeplab else (interm.detach(), final.detach())
         return loss
 
     def barrier():
@@ -512,6 +562,19 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
     final_loss = float(loss.detach())
+    if args.dump_outputs and rank == 0:
+        # what a caller of the training step holds after the last timed step: its loss and logits, the parameters after its Adam update,
+        # and the per-step training metric (the confusion matrix, accumulated over the warm-up and timed steps)
+        if graphed["step"] is not None:
+            out = graphed["step"].outputs
+            interm, final = (None, out) if deeplab else out
+        else:
+            interm, final = last["out"]
+        arrays = {"loss": loss.detach().reshape(1)}
+        if interm is not None:
+            arrays["logits_interm"] = interm
+        arrays.update(logits_final=final, weights=model.flat().flat, confusion_matrix=cm)
+        _dump(args, arrays)
 
     roof = None
     if not args.no_roofline:

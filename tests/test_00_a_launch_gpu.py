@@ -7,6 +7,8 @@ GPU before (a GPU-initialised process must not exec on this pool; only torch.cud
     line; both ranks share GPU 0 over gloo (CATSEG_DIST_BACKEND=gloo, the labelled functional artefact): world_seen_by_backend == 2.
 (b) backend 'nccl' (RCCL) with world_size 1: the bucketed gradient exchange forced to launch through a real HRNet-W48 backward
     (tests/_rccl_worker.py) -- gradients bit-identical to the run without a reducer, exposed wait recorded.
+(c) a plain `python bench.py --gpus 1` times its steps and nothing else (the other figures need --full); --dump-outputs writes the last
+    timed step's results as .npy files.
 """
 import json
 import os
@@ -30,7 +32,7 @@ def test_bench_gpus2_launches_its_own_ranks():
     if torch.cuda.device_count() == 0:
         pytest.skip("needs a GPU")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--no-cpu-baseline", "--no-side-figures"], env=_env(CATSEG_DIST_BACKEND="gloo"),
+                        "--full", "--no-cpu-baseline", "--no-side-figures"], env=_env(CATSEG_DIST_BACKEND="gloo"),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     out, err = p.stdout.decode(errors="replace"), p.stderr.decode(errors="replace")
     assert p.returncode == 0, err[-4000:]
@@ -52,7 +54,7 @@ def test_bench_infer_gpus2_shards_frames_and_sums_the_confusion_matrices():
     if torch.cuda.device_count() == 0:
         pytest.skip("needs a GPU")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--infer", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--height", "256", "--width", "384", "--no-cpu-baseline"], env=_env(CATSEG_DIST_BACKEND="gloo"),
+                        "--height", "256", "--width", "384", "--full", "--no-cpu-baseline"], env=_env(CATSEG_DIST_BACKEND="gloo"),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200)
     out, err = p.stdout.decode(errors="replace"), p.stderr.decode(errors="replace")
     assert p.returncode == 0, err[-4000:]
@@ -66,6 +68,38 @@ def test_bench_infer_gpus2_shards_frames_and_sums_the_confusion_matrices():
     assert cmx["summed_over_ranks"] and cmx["pixels_scored_all_ranks"] >= 2 * 3 * cmx["labelled_pixels_per_step_rank0"] * 0.8
     assert cmx["pixels_scored_all_ranks"] > 3 * cmx["labelled_pixels_per_step_rank0"] * 1.5      # ... more than one rank's share
     assert r["value"] > 0 and abs(r["value"] - 4 / (r["ms_per_step"] * 1e-3)) < 1e-6 * r["value"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """a plain `bench.py --gpus 1` times exactly --steps steps and carries nothing measured beside them (no roofline, side figures or CPU
+    baseline: those need --full); --dump-outputs writes the last timed step's loss, logits, updated weights and confusion matrix as .npy"""
+    if torch.cuda.device_count() == 0:
+        pytest.skip("needs a GPU")
+    import numpy as np
+    d = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+                        "--height", "128", "--width", "192", "--dump-outputs", str(d)], env=_env(),
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    out, err = p.stdout.decode(errors="replace"), p.stderr.decode(errors="replace")
+    assert p.returncode == 0, err[-4000:]
+    lines = [ln for ln in out.splitlines() if ln.strip()]
+    assert len(lines) == 1, out[-2000:]
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["n_gpus"] == 1 and r["higher_is_better"] is True
+    assert r["value"] > 0 and abs(r["value"] - 2 / (r["ms_per_step"] * 1e-3)) < 1e-6 * r["value"]
+    assert r["roofline"] is None and r["cpu_baseline"] is None and "side_figures" not in r and r["value_exact_fp32"] is None
+    names = sorted(f.name for f in d.iterdir())
+    assert names == ["confusion_matrix.npy", "logits_final.npy", "logits_interm.npy", "loss.npy", "weights.npy"], names
+    a = {n[:-4]: np.load(d / n) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["loss"].shape == (1,) and float(a["loss"][0]) == np.float32(r["config"]["final_loss"])
+    # logits of 2 x 25 x 128 x 192 at most: written whole; the 73 M weights: their fixed sample of bench.DUMP_SAMPLE elements
+    assert a["logits_final"].ndim == 4 and a["logits_final"].shape[:2] == (2, 25) and a["logits_interm"].shape[:2] == (2, 25)
+    assert a["weights"].shape == (1 << 21,)
+    assert np.isfinite(a["logits_final"]).all() and np.isfinite(a["weights"]).all()
+    cm = a["confusion_matrix"]
+    assert cm.shape == (25, 25) and cm.dtype == np.float64 and (cm == np.round(cm)).all() and cm.sum() > 0
 
 
 def test_bench_refuses_a_group_that_is_not_rccl():

@@ -1,5 +1,5 @@
 """prints the parts of a bench.py JSON line one reads after a change: step time, the families' event times, the HBM-bound kernels, the plan
-   usage: python bench.py ... | python tools/bench_brief.py   (or: bench_brief.py <file>)"""
+   usage: python bench.py --full ... | python tools/bench_brief.py   (or: bench_brief.py <file>)"""
 import json, sys
 src = open(sys.argv[1]).read() if len(sys.argv) > 1 else sys.stdin.read()
 line = [l for l in src.splitlines() if l.startswith("{")][-1]

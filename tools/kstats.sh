@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/$TAG
 mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o p -- python3 "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-roofline "$@" > "$O/bench.json" 2> "$O/bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o p -- python3 "$R/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-roofline "$@" > "$O/bench.json" 2> "$O/bench.err"
 F=$(ls "$O"/prof/*/p_kernel_stats.csv "$O"/prof/p_kernel_stats.csv 2>/dev/null | head -1)
 cp "$F" "$O/kernel_stats.csv"
 python3 - "$O/kernel_stats.csv" <<'PY'

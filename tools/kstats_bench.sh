@@ -1,5 +1,5 @@
 R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out/r03_a; mkdir -p $O; cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o p -- python3 "$R/bench.py" --steps 5 --warmup 2 --no-cpu-baseline > "$O/bench_prof.json" 2> "$O/bench_prof.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o p -- python3 "$R/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline > "$O/bench_prof.json" 2> "$O/bench_prof.err"
 cp $(ls "$O"/prof/*/p_kernel_stats.csv "$O"/prof/p_kernel_stats.csv 2>/dev/null | head -1) "$O/kernel_stats_ocrnet_hrnet48.csv"; rm -rf "$O/prof"
 python3 - "$O/kernel_stats_ocrnet_hrnet48.csv" <<'PY'
 import csv, sys

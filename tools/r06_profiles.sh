@@ -17,7 +17,7 @@ for m in ocrnet_hrnet48 ocrnet_r50; do
   rm -rf "$O"/pmc_fetch_$m "$O"/pmc_write_$m
 done
 for m in ocrnet_hrnet48 ocrnet_r50 deeplabv3plus_r50; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$m" -o p -- python3 "$R/bench.py" --model $m --eager --steps 3 --warmup 1 --no-cpu-baseline --no-side-figures > "$O/bench_prof_$m.json" 2> "$O/bench_prof_$m.err"
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$m" -o p -- python3 "$R/bench.py" --full --model $m --eager --steps 3 --warmup 1 --no-cpu-baseline --no-side-figures > "$O/bench_prof_$m.json" 2> "$O/bench_prof_$m.err"
   cp $(ls "$O"/prof_$m/*/p_kernel_stats.csv "$O"/prof_$m/p_kernel_stats.csv 2>/dev/null | head -1) "$O/kernel_stats_$m.csv"
   if [ "$m" = "ocrnet_hrnet48" ]; then
     python3 "$R/tools/trace_by_grid.py" "$O/prof_$m" > "$O/trace_by_grid_$m.txt" 2>&1
@@ -25,15 +25,15 @@ for m in ocrnet_hrnet48 ocrnet_r50 deeplabv3plus_r50; do
   fi
   rm -rf "$O/prof_$m"
 done
-python3 "$R/bench.py" --steps 20 --warmup 5 > "$O/bench_ocrnet_hrnet48.json" 2> "$O/bench_ocrnet_hrnet48.err"
-CATSEG_PRECISION=fp32 python3 "$R/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-side-figures > "$O/bench_ocrnet_hrnet48_fp32only.json" 2> /dev/null
+python3 "$R/bench.py" --full --steps 20 --warmup 5 > "$O/bench_ocrnet_hrnet48.json" 2> "$O/bench_ocrnet_hrnet48.err"
+CATSEG_PRECISION=fp32 python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline --no-side-figures > "$O/bench_ocrnet_hrnet48_fp32only.json" 2> /dev/null
 python3 "$R/bench.py" --eager --steps 10 --warmup 3 --no-cpu-baseline --no-side-figures --no-roofline > "$O/bench_ocrnet_hrnet48_eager.json" 2> /dev/null
 for m in ocrnet_r50 deeplabv3plus_r50; do
-  python3 "$R/bench.py" --model $m --steps 10 --warmup 3 --no-cpu-baseline > "$O/bench_$m.json" 2> "$O/bench_$m.err"
+  python3 "$R/bench.py" --full --model $m --steps 10 --warmup 3 --no-cpu-baseline > "$O/bench_$m.json" 2> "$O/bench_$m.err"
 done
-python3 "$R/bench.py" --infer > "$O/bench_infer.json" 2> "$O/bench_infer.err"
+python3 "$R/bench.py" --full --infer > "$O/bench_infer.json" 2> "$O/bench_infer.err"
 # two ranks (gloo) sharing the one GPU through bench.py's own launcher: the data-parallel path end to end in its DEFAULT mode (segmented graph replay)
-CATSEG_DIST_BACKEND=gloo python3 "$R/bench.py" --gpus 2 --steps 5 --warmup 2 --batch 4 --no-cpu-baseline --no-side-figures > "$O/bench_2rank_gloo_1gpu.json" 2> "$O/bench_2rank_gloo_1gpu.err"
+CATSEG_DIST_BACKEND=gloo python3 "$R/bench.py" --full --gpus 2 --steps 5 --warmup 2 --batch 4 --no-cpu-baseline --no-side-figures > "$O/bench_2rank_gloo_1gpu.json" 2> "$O/bench_2rank_gloo_1gpu.err"
 CATSEG_DIST_BACKEND=gloo python3 "$R/bench.py" --gpus 2 --steps 5 --warmup 2 --batch 4 --eager --no-cpu-baseline --no-side-figures --no-roofline > "$O/bench_2rank_gloo_1gpu_eager.json" 2> /dev/null
 python3 "$R/tools/stage_times.py" > "$O/stage_times.txt" 2>&1
 python3 "$R/tools/host_time.py" > "$O/host_time.txt" 2>&1
