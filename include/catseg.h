@@ -506,6 +506,27 @@ size_t catseg_ohem_workspace(long long P);
 int catseg_ohem_cross_entropy(const float* logits, const int64_t* labels, long long P, int K, long long ignore_index,
                               float thresh, long long min_kept, float weight, float* loss_out, float* dlogits,
                               void* workspace, size_t workspace_bytes, catseg_stream_t stream);
+/* SoftIoU.forward / GenDiceLoss.forward (losses/SoftIoU.py, losses/GenDiceLoss.py) in two calls around autograd.  Labels 0 <= y < K have
+ * one-hot column y; y == ignore_index (>= 0; -1 = none) is a zero one-hot row whose probabilities still enter the sums; any other label
+ * is invalid: the pixel is dropped and counted in invalid_out[0] (int64, device).  kind 0 = SoftIoU, 1 = GenDice; naive != 0: the mean
+ * over all K classes (nan where 0 / 0), else over the classes whose union / weighted divisor is non-zero.  weight_mode (GenDice):
+ * 0 none, 1 'auto' (1 / n_c^2, 1 where n_c = 0), 2 = weights (HOST array of K floats).  _fwd writes loss_out[0] and coef (device,
+ * 128 floats, owned by the caller until _bwd): d loss / d p_pc = coef[c] [y_p = c] + coef[64 + c].  _bwd writes
+ * dlogits = (d loss / d logits) * upstream[0] (a DEVICE scalar; null = 1). */
+size_t catseg_overlap_workspace(long long P, int K);
+int catseg_overlap_fwd(const float* logits, const int64_t* labels, long long P, int K, long long ignore_index, int kind, int naive,
+                       int weight_mode, const float* weights, float* loss_out, float* coef, long long* invalid_out,
+                       void* workspace, size_t workspace_bytes, catseg_stream_t stream);
+int catseg_overlap_bwd(const float* logits, const int64_t* labels, long long P, int K, long long ignore_index, const float* coef,
+                       const float* upstream, float* dlogits, catseg_stream_t stream);
+/* FocalLoss.forward (losses/FocalLoss.py): mean over all P pixels of -alpha_y (1 - p_y)^gamma log p_y, p_y from the unweighted
+ * log-softmax; alpha = HOST array of K floats or null.  Labels outside [0, K) add zero loss and zero gradient (and stay in the
+ * denominator); their number goes to invalid_out[0] (int64, device).  _bwd: dlogits = (d loss / d logits) * upstream[0] (device; null = 1). */
+size_t catseg_focal_workspace(long long P);
+int catseg_focal_fwd(const float* logits, const int64_t* labels, long long P, int K, float gamma, const float* alpha, float* loss_out,
+                     long long* invalid_out, void* workspace, size_t workspace_bytes, catseg_stream_t stream);
+int catseg_focal_bwd(const float* logits, const int64_t* labels, long long P, int K, float gamma, const float* alpha,
+                     const float* upstream, float* dlogits, catseg_stream_t stream);
 
 /* ---- input side -------------------------------------------------------------- */
 /* Dataset_from_df.__getitem__ + its deterministic transforms (datasets/Dataset_from_df.py:31-69;

@@ -179,6 +179,12 @@ _SIGS = {
     "catseg_cross_entropy": (I, [P, P, L, I, L, F, P, P, P, SZ, P]),
     "catseg_ohem_workspace": (SZ, [L]),
     "catseg_ohem_cross_entropy": (I, [P, P, L, I, L, F, L, F, P, P, P, SZ, P]),
+    "catseg_overlap_workspace": (SZ, [L, I]),
+    "catseg_overlap_fwd": (I, [P, P, L, I, L, I, I, I, P, P, P, P, P, SZ, P]),
+    "catseg_overlap_bwd": (I, [P, P, L, I, L, P, P, P, P]),
+    "catseg_focal_workspace": (SZ, [L]),
+    "catseg_focal_fwd": (I, [P, P, L, I, F, P, P, P, P, SZ, P]),
+    "catseg_focal_bwd": (I, [P, P, L, I, F, P, P, P, P]),
     "catseg_ingest_u8": (I, [P, P, I, I, I, P, P, I, I, P, P, P, P, P, P]),
     "catseg_resize_nearest": (I, [P, I, P, I, I, I, I, I, I, I, I, I, F, P]),
     "catseg_confusion_matrix": (I, [P, P, L, I, P, P]),

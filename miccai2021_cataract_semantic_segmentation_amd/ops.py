@@ -1766,6 +1766,66 @@ def ohem_cross_entropy(logits, labels, ignore_index, thresh, min_kept, weight=1.
     return loss_out
 
 
+def _host_floats(v, K):
+    """a per-class list as a ctypes float array (passed to the kernels by value), or None"""
+    if v is None:
+        return None
+    assert len(v) == K
+    return (ctypes.c_float * K)(*[float(x) for x in v])
+
+
+def overlap_fwd(logits, labels, kind, ignore_index=-1, naive=False, weight_mode=0, weights=None):
+    """forward half of SoftIoU (kind 0) / GenDiceLoss (kind 1) for autograd: (loss [1], coef [128], invalid_labels int64 [1]) -- coef
+    holds d loss / d prob for overlap_bwd in a buffer of its own (not the stream's shared scratch: other launches run between the halves)"""
+    Pn, K = logits.shape
+    assert logits.is_contiguous() and labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == Pn
+    dev = logits.device
+    loss_out = torch.empty(1, dtype=torch.float32, device=dev)
+    coef = torch.empty(128, dtype=torch.float32, device=dev)
+    invalid = torch.empty(1, dtype=torch.int64, device=dev)
+    need = lib.catseg_overlap_workspace(Pn, K)
+    ws = workspace(need, dev)
+    with _Timed("hbm:overlap_fwd", 4.0 * Pn * K + 8.0 * Pn):
+        check(lib.catseg_overlap_fwd(ptr(logits), ptr(labels), Pn, K, ignore_index, kind, 1 if naive else 0, weight_mode,
+                                     _host_floats(weights, K), ptr(loss_out), ptr(coef), ptr(invalid), ptr(ws), ws.numel(), stream()))
+    return loss_out, coef, invalid
+
+
+def overlap_bwd(logits, labels, coef, upstream, ignore_index=-1):
+    """d loss / d logits * upstream (upstream: 1-element float32 device tensor, autograd's grad_output; None = 1)"""
+    Pn, K = logits.shape
+    assert upstream is None or (upstream.numel() == 1 and upstream.dtype == torch.float32 and upstream.is_cuda)
+    dlogits = torch.empty_like(logits)
+    with _Timed("hbm:overlap_bwd", 8.0 * Pn * K + 8.0 * Pn):
+        check(lib.catseg_overlap_bwd(ptr(logits), ptr(labels), Pn, K, ignore_index, ptr(coef), ptr(upstream), ptr(dlogits), stream()))
+    return dlogits
+
+
+def focal_fwd(logits, labels, gamma, alpha=None):
+    """FocalLoss forward: (loss [1], invalid_labels int64 [1]); alpha = per-class host list or None"""
+    Pn, K = logits.shape
+    assert logits.is_contiguous() and labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == Pn
+    dev = logits.device
+    loss_out = torch.empty(1, dtype=torch.float32, device=dev)
+    invalid = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = workspace(lib.catseg_focal_workspace(Pn), dev)
+    with _Timed("hbm:focal_fwd", 4.0 * Pn * K + 8.0 * Pn):
+        check(lib.catseg_focal_fwd(ptr(logits), ptr(labels), Pn, K, float(gamma), _host_floats(alpha, K), ptr(loss_out), ptr(invalid),
+                                   ptr(ws), ws.numel(), stream()))
+    return loss_out, invalid
+
+
+def focal_bwd(logits, labels, gamma, alpha, upstream):
+    """d focal / d logits * upstream (1-element float32 device tensor; None = 1)"""
+    Pn, K = logits.shape
+    assert upstream is None or (upstream.numel() == 1 and upstream.dtype == torch.float32 and upstream.is_cuda)
+    dlogits = torch.empty_like(logits)
+    with _Timed("hbm:focal_bwd", 8.0 * Pn * K + 8.0 * Pn):
+        check(lib.catseg_focal_bwd(ptr(logits), ptr(labels), Pn, K, float(gamma), _host_floats(alpha, K), ptr(upstream), ptr(dlogits),
+                                   stream()))
+    return dlogits
+
+
 def ingest_u8(img, lbl, lut=None, flips=None, pad_top=0, pad_bottom=0, mean=None, std=None, nhwc4=False):
     """img uint8 [B,H,W,3] and / or lbl uint8 [B,H,W] -> (x float32 [B,3,H',W] (or NHWC-4 [B,H',W,4]), labels int64 [B,H',W])"""
     ref = img if img is not None else lbl
