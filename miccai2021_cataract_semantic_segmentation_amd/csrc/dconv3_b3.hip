@@ -31,11 +31,6 @@
 #define dconv3_b3_spec_kernel dconv3_h2_spec_kernel
 #define dconv3_prep_kernel dconv3_h2_prep_kernel
 #define dconv3_prep_batch_kernel dconv3_h2_prep_batch_kernel
-#elif defined(DC_AB2)
-// (timing-only build -DDC_AB2: two planes and three products of the bf16 arithmetic -- WRONG results; what the f16x2 build was worth
-//  before it existed: the l plane is neither stored, streamed nor read, the products mm / hl / lh are dropped)
-#define DC_NPL 2
-#define DC_MFMA __builtin_amdgcn_mfma_f32_16x16x32_bf16
 #else
 #define DC_NPL 3
 #define DC_MFMA __builtin_amdgcn_mfma_f32_16x16x32_bf16
@@ -250,10 +245,6 @@ __global__ __launch_bounds__(G::NTHR, 2) void dconv3_b3_kernel(const DcArgs a) {
     t_end = (int)((long long)(v + 1) * ntile / nb);
   }
   if (t_begin >= t_end) return;
-#ifdef DC_PRIO
-  // static priority: the two blocks that share a CU (dispatch order: block b and b + grid / 2) do not arbitrate step by step
-  if (blockIdx.x < (gridDim.x >> 1)) __builtin_amdgcn_s_setprio(DC_PRIO);
-#endif
 
   // ---- staging: unit u = wave + i NW covers 16 halo pixels x 4 channel groups, lane = pixel + 16 group ------------------------
   // Prefetch of the next (tile, chunk): raw buffer loads over ONE image (rows above / below it are out of range: the hardware
@@ -283,17 +274,10 @@ __global__ __launch_bounds__(G::NTHR, 2) void dconv3_b3_kernel(const DcArgs a) {
   auto fetch_item = [&](int i) {
     const bool okx = (unsigned)(f_x0 + it_hx[i]) < (unsigned)a.W;
     const int off = okx ? f_org + it_off[i] : (int)0xFFFFFFE0;
-#ifndef DC_NO_FETCH
     pre[i][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(f_rs, off, 0, 0));
     pre[i][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(f_rs, off + 16, 0, 0));
-#else
-    pre[i][0] = pre[i][1] = f32x4{(float)off, 0.f, 0.f, 0.f};
-#endif
   };
   auto convert_item = [&](int i) {
-#ifdef DC_NO_STASH
-    return;
-#endif
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float v = pre[i][j >> 2][j & 3];
@@ -328,9 +312,6 @@ __global__ __launch_bounds__(G::NTHR, 2) void dconv3_b3_kernel(const DcArgs a) {
     }
   };
   auto stash = [&]() {
-#ifdef DC_NO_STASH
-    return;
-#endif
 #pragma unroll
     for (int i = 0; i < G::IPT; ++i) {
       const int px = item_px(i);
@@ -346,9 +327,6 @@ __global__ __launch_bounds__(G::NTHR, 2) void dconv3_b3_kernel(const DcArgs a) {
   // ---- weight stream: step q (0 .. NCHUNK NSTEP - 1, the same for every tile) of this co block -> LDS slot --------------------
   const unsigned char* wsrc = (const unsigned char*)a.wimg + (long long)cob * (G::NCHUNK * G::NSTEP) * G::WSTEP + lane * 16;
   auto wfill = [&](int q, int slot) {
-#ifdef DC_NO_DMA
-    return;
-#endif
     unsigned char* dst = smem + G::XBYTES + slot * G::WSTEP;
     const unsigned char* src = wsrc + (long long)q * G::WSTEP;
 #pragma unroll
@@ -434,22 +412,12 @@ __global__ __launch_bounds__(G::NTHR, 2) void dconv3_b3_kernel(const DcArgs a) {
           qn = qn + 1 == TSTEPS ? 0 : qn + 1;
         }
         if (s < G::IPT) fetch_item(s);
-#ifdef DC_SGB
-        __builtin_amdgcn_sched_barrier(0);      // (region of the group barriers below: split arithmetic + fragment reads + MFMAs)
-#endif
         if (s >= 2 && s - 2 < G::IPT) convert_item(s - 2);
         const int set = G::XPF ? (s & 1) : 0;
-#ifndef DC_NO_XREAD
         if (G::XPF && s + 1 < G::NSTEP) xread(s + 1, (s + 1) & 1);
-#endif
 #pragma unroll
         for (int ct = 0; ct < G::CB; ++ct) {
-#if !defined(DC_NOFENCE) && !defined(DC_SGB)
           __builtin_amdgcn_sched_barrier(0);
-#endif
-#ifdef DC_SETPRIO
-          __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
           for (int pt = 0; pt < G::PB; ++pt) {
             f32x4 c = acc[ct][pt];
@@ -462,50 +430,21 @@ __global__ __launch_bounds__(G::NTHR, 2) void dconv3_b3_kernel(const DcArgs a) {
             c = DC_MFMA(wf[ct][1], xf[set][pt][0], c, 0, 0, 0);   // m h
             c = DC_MFMA(wf[ct][0], xf[set][pt][0], c, 0, 0, 0);   // h h
             acc[ct][pt] = c;
-#ifndef DC_NO_XREAD
             if (!G::XPF && ct == G::CB - 1 && s + 1 < G::NSTEP) {   // single fragment set: refilled behind its last use
-#ifndef DC_SGB
               __builtin_amdgcn_sched_barrier(0);
-#endif
               xread1(s + 1, 0, pt);
             }
-#endif
           }
-#ifdef DC_SETPRIO
-          __builtin_amdgcn_s_setprio(0);
-#endif
-#if !defined(DC_NOFENCE) && !defined(DC_SGB)
           __builtin_amdgcn_sched_barrier(0);
-#endif
-#ifndef DC_NO_WREAD
           wread1((gs + 1) & 1, ct);     // the next step's weight fragments roll in behind the last use of these registers
-#endif
         }
-#ifdef DC_SGB
-        // issue order of the step's region: the pixel-fragment prefetch first, then every MFMA followed by two of the VALU operations
-        // of the split arithmetic (they run in the shadow of the MFMA's own pipe time instead of as a block in front of the MFMAs),
-        // the weight fragments of the next step behind each output-channel tile's last MFMA
-        if (G::XPF && s + 1 < G::NSTEP) __builtin_amdgcn_sched_group_barrier(0x100, 3 * G::PB, 0);
-#pragma unroll
-        for (int ct = 0; ct < G::CB; ++ct) {
-#pragma unroll
-          for (int k = 0; k < 6 * G::PB; ++k) {
-            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x2, 2, 0);
-          }
-          __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#endif
         ++gs;
         // the weights of step gs + 1 have landed (the two prefetch loads issued behind their DMA may stay in flight), every LDS
         // read of this step has returned
-#ifndef DC_NO_SYNC
         if (s < G::IPT) DC_WAIT_VM(2);
         else DC_WAIT_VM(0);
         DC_WAIT_LGKM0();
         __builtin_amdgcn_s_barrier();
-#endif
       }
     }
 
@@ -542,11 +481,7 @@ __global__ __launch_bounds__(G::NTHR, 2) void dconv3_b3_kernel(const DcArgs a) {
 #pragma unroll
       for (int pt = 0; pt < G::PB; ++pt) {
         acc[ct][pt] += bv;
-#ifdef DC_NO_STORE
-        if (p_ok[pt] && acc[ct][pt][0] == 123.456f) {
-#else
         if (p_ok[pt]) {
-#endif
           float* dst = a.y + (img0 + (long long)(y0 + prow(pt)) * a.W + x0 + pcol(pt)) * a.ldy + co0 + ct * 16;
           f32x4 v = acc[ct][pt];
           if (a.accumulate) v += *(const f32x4*)dst;
@@ -1056,11 +991,8 @@ __global__ __launch_bounds__(256) void dconv3_prep_batch_kernel(const float* __r
 #endif
 
 //                     C  KC  NT WC WP PB TPH TPW PH PW  XPF
-#ifndef DC_SPEC48      // (A/B hook: wave specialisation for 48 / 64 channels.  bf16x3 build: 65 -> 70 us; f16x2 build: 53 / 52 -> 54 / 50 us at 48
-#define DC_SPEC48 false  //  channels, 72 -> 84 us at 64: not adopted in either)
-#endif
-using Cfg48 = DcCfg<48, 48, 48, 1, 4, 2, 8, 1, 1, 16, true, DC_SPEC48>;    // tile  8 x 16, wave = 48 co x 32 px
-using Cfg64 = DcCfg<64, 32, 64, 1, 4, 2, 8, 1, 1, 16, true, DC_SPEC48>;    // tile  8 x 16, wave = 64 co x 32 px (the stage-1 bottlenecks' 3x3)
+using Cfg48 = DcCfg<48, 48, 48, 1, 4, 2, 8, 1, 1, 16, true, false>;    // tile  8 x 16, wave = 48 co x 32 px
+using Cfg64 = DcCfg<64, 32, 64, 1, 4, 2, 8, 1, 1, 16, true, false>;    // tile  8 x 16, wave = 64 co x 32 px (the stage-1 bottlenecks' 3x3)
 using Cfg96 = DcCfg<96, 32, 96, 2, 2, 4, 4, 2, 1, 16, false>;    // tile  4 x 32, wave = 48 co x 64 px (A/B alternative)
 
 using Cfg96s = DcCfg<96, 32, 96, 2, 2, 2, 4, 1, 1, 16, true, true>;   // tile 4 x 16, wave = 48 co x 32 px, specialised waves (the default for 96)

@@ -69,11 +69,7 @@ struct PlCfg {
   static constexpr int BUDGET = (NT2 == 1 ? 80 : 128) * 1024;
   // weight slots: as many (3 .. 5) as fit two blocks per CU (80 KB each).  With NWB slots the weights of K-step s + NWB are issued in step s
   // and must have landed NWB - 2 steps later: the helpers' counted waits then cover an L2 round trip under load (~1 - 2 K-steps)
-#ifdef PL_NWB
-  static constexpr int NWB = PL_NWB;
-#else
   static constexpr int NWB = (NXB * RING + 5 * WSTEP <= BUDGET) ? 5 : ((NXB * RING + 4 * WSTEP <= BUDGET) ? 4 : 3);
-#endif
   static constexpr int LDS = NXB * RING + NWB * WSTEP;
   static_assert(WSTEP % 1024 == 0 && KGS % 256 == 0, "LDS image strides");
   static constexpr int sub_steps(int u) { return u == 0 ? 9 : 5; }
@@ -168,7 +164,6 @@ __global__ __launch_bounds__(G::NTHR, G::MINW) void dconv3_pl_kernel(const PlArg
     constexpr int Q = G::WSTEP / 4, NW = (Q + 1023) / 1024;
     const unsigned char* wsrc = (const unsigned char*)a.wimg + (long long)cob * G::TSTEPS * G::WSTEP + hw * Q + lane * 16;
     auto wfill = [&](int q, int slot) {
-#ifndef PL_NO_WDMA
       unsigned char* dst = smem + G::NXB * G::RING + slot * G::WSTEP + hw * Q;
       const unsigned char* src = wsrc + (long long)q * G::WSTEP;
 #pragma unroll
@@ -176,7 +171,6 @@ __global__ __launch_bounds__(G::NTHR, G::MINW) void dconv3_pl_kernel(const PlArg
         if (i * 1024 + lane * 16 < Q)
           __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i * 1024),
                                            (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
-#endif
     };
     // ---- the NEXT sub-chunk to fetch: (tile, weight chunk, sub-chunk) -> image offset, tile origin, first channel group, ring buffer
     int f_tile = t_begin, f_chunk = 0, f_buf = 0;
@@ -253,9 +247,6 @@ __global__ __launch_bounds__(G::NTHR, G::MINW) void dconv3_pl_kernel(const PlArg
     __builtin_amdgcn_s_barrier();          // P: image 0 and the first weights have landed
     __builtin_amdgcn_s_barrier();          // P2: the compute waves hold their fragments of K-step 0 (slot 0 may be refilled)
     int q3 = G::NWB % G::TSTEPS, s3 = 0;   // step-in-tile index of the weights of step gs + NWB, and their slot (= gs % NWB)
-#ifdef PL_WSTAGGER      // (timing-only: every block streams the weight image from a different K-step -- WRONG results)
-    q3 = (q3 + blockIdx.x * 5) % G::TSTEPS;
-#endif
 
     // one sub-chunk of type U: NS K-steps; the NEXT sub-chunk (type UN) is fetched during steps 0 .. NS - 3
     auto run_sub = [&](auto U_) {
@@ -267,25 +258,15 @@ __global__ __launch_bounds__(G::NTHR, G::MINW) void dconv3_pl_kernel(const PlArg
         static_assert(PER <= 2, "at most two halo pieces per helper and K-step");
         wfill(q3, s3);                                      // weights of step gs + NWB (past the end: clamped, see f_advance)
         q3 = q3 + 1 == G::TSTEPS ? 0 : q3 + 1;
-#ifndef PL_NO_XDMA
         if constexpr (X0) xissue(std::integral_constant<int, UN>{}, std::integral_constant<int, LS * PER>{});
         if constexpr (X1) xissue(std::integral_constant<int, UN>{}, std::integral_constant<int, LS * PER + 1>{});
-#endif
         s3 = s3 == G::NWB - 1 ? 0 : s3 + 1;
         // The weights of step gs + 2 (issued NWB - 2 steps ago) have landed: at most the NW (NWB - 2) youngest operations stay in flight
         // (this and the previous NWB - 3 steps issued at least that many -- halo pieces on top make the wait only stricter).  Behind
         // step NS - 2 the whole next image must be there: everything older than this step's own issues.
-#ifndef PL_NO_HWAIT
-#if defined(PL_NO_WDMA) || defined(PL_NO_XDMA)
-        PL_WAIT_VM(0);
-#else
         if constexpr (LS == NS - 2) PL_WAIT_VM(NW + (X0 ? 1 : 0) + (X1 ? 1 : 0));
         else PL_WAIT_VM(NW * (G::NWB - 2));
-#endif
-#endif
-#ifndef PL_NO_LOOPBAR
         __builtin_amdgcn_s_barrier();
-#endif
       };
       one_step(std::integral_constant<int, 0>{});
       one_step(std::integral_constant<int, 1>{});
@@ -315,10 +296,8 @@ __global__ __launch_bounds__(G::NTHR, G::MINW) void dconv3_pl_kernel(const PlArg
   const int i16 = lane & 15, kg = lane >> 4;
   const int half = wave >> 2, w4 = wave & 3;     // (tile of the unit this wave works on; wave within the tile's four)
   const int wc = w4 / G::WP, wp = w4 % G::WP;
-#ifndef PL_NO_SCALE
   const int ex_x = __builtin_amdgcn_readfirstlane(a.x_rec[CS_REC_EXP]);
   const int ex_w = __builtin_amdgcn_readfirstlane(a.w_rec[1]);
-#endif
   auto prow = [&](int pt) { return (wp * G::PB + pt) / G::TPW; };
   auto pcol = [&](int pt) { return ((wp * G::PB + pt) % G::TPW) * 16 + i16; };
   int xa[G::PB], xs1[G::PB];     // lane's fragment address in an image: groups 0-3 by kg (steps 0-8) / group kg & 1 (steps 9-13)
@@ -377,35 +356,25 @@ __global__ __launch_bounds__(G::NTHR, G::MINW) void dconv3_pl_kernel(const PlArg
 #pragma unroll
         for (int ct = 0; ct < G::CB; ++ct) {
           f32x4 c = acc[ct][pt];
-#ifdef PL_NO_MFMA       // (timing-only: one product instead of three)
-          c = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[ct][0], xf[pt][1] + xf[pt][0], c, 0, 0, 0);
-#else
           c = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[ct][0], xf[pt][1], c, 0, 0, 0);   // h l
           c = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[ct][1], xf[pt][0], c, 0, 0, 0);   // l h
           c = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[ct][0], xf[pt][0], c, 0, 0, 0);   // h h
-#endif
           acc[ct][pt] = c;
-#ifndef PL_NO_DSREAD
           if (pt == G::PB - 1) {                    // the next step's weight fragments behind the last use of these registers
             __builtin_amdgcn_sched_barrier(0);
             wread1(s3n, ct);
             __builtin_amdgcn_sched_barrier(0);
           }
-#endif
         }
-#ifndef PL_NO_DSREAD
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (LS + 1 < NS) xread1(std::integral_constant<int, WS0 + LS + 1>{}, xbase, pt);
         else xread1(std::integral_constant<int, WSN>{}, xbase ^ G::RING, pt);
         __builtin_amdgcn_sched_barrier(0);
-#endif
       }
       s3n = s3n == G::NWB - 1 ? 0 : s3n + 1;
       PL_WAIT_LGKM0();      // every fragment read of this step has returned before the barrier lets the helpers refill what it read
 
-#ifndef PL_NO_LOOPBAR
       __builtin_amdgcn_s_barrier();
-#endif
     };
     one_step(std::integral_constant<int, 0>{});
     one_step(std::integral_constant<int, 1>{});
@@ -440,7 +409,6 @@ __global__ __launch_bounds__(G::NTHR, G::MINW) void dconv3_pl_kernel(const PlArg
     }
 
     // ---- epilogue (no LDS, no barrier: the helpers keep prefetching the next tile) -----------------------------------------------------
-#ifndef PL_NO_SCALE
     if (ex_x + ex_w >= -120 && ex_x + ex_w <= 120) {     // back to the operands' scale: one exact multiplication by 2^-(e_x + e_w)
       const float sc = __builtin_ldexpf(1.f, -(ex_x + ex_w));
 #pragma unroll
@@ -455,7 +423,6 @@ __global__ __launch_bounds__(G::NTHR, G::MINW) void dconv3_pl_kernel(const PlArg
 #pragma unroll
           for (int r = 0; r < 4; ++r) acc[ct][pt][r] = __builtin_ldexpf(__builtin_ldexpf(acc[ct][pt][r], -ex_x), -ex_w);
     }
-#endif
     bool p_ok[G::PB];
     int nvalid = 0;
 #pragma unroll
@@ -509,11 +476,7 @@ __global__ __launch_bounds__(G::NTHR, G::MINW) void dconv3_pl_kernel(const PlArg
 #pragma unroll
         for (int pt = 0; pt < G::PB; ++pt) {
           acc[ct][pt] += bv;
-#ifdef PL_NO_STORE
-          if (p_ok[pt] && acc[ct][pt][0] == 123.456f) {
-#else
           if (p_ok[pt]) {
-#endif
             float* dst = a.y + (img0 + (long long)(y0 + prow(pt)) * a.W + x0 + pcol(pt)) * a.ldy + co0 + ct * 16;
             f32x4 v = acc[ct][pt];
             if (a.accumulate) v += *(const f32x4*)dst;

@@ -172,11 +172,7 @@ __global__ __launch_bounds__(G::NTHR, 2) void dwgrad3_pl_kernel(const WpArgs a) 
 
   auto tread = [&](int addr) { return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + addr)); };
   auto frag = [&](int addr, int hstride) {   // k = 0..3: the group's 4 pixels of tile row 2 ks, k = 4..7: of row 2 ks + 1
-#ifdef WP_NO_DSREAD
-    const s16x4 lo = {(short)addr, (short)lane, 1, 2}, hi = {(short)hstride, 3, (short)tid, 4};
-#else
     const s16x4 lo = tread(addr), hi = tread(addr + hstride);
-#endif
     const s16x8 v8 = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_bit_cast(h8, v8);
   };
@@ -209,9 +205,7 @@ __global__ __launch_bounds__(G::NTHR, 2) void dwgrad3_pl_kernel(const WpArgs a) 
 #pragma unroll 1
   for (int tile = t_begin; tile < t_end; ++tile) {
     // (its buffer held tile - 1, whose last fragment reads are behind the barrier that closed that tile)
-#ifndef WP_NO_DMA       // (differential-timing builds, tools/ab_wp.sh: wrong results, the time difference is the ingredient's cost)
     if (tile + G::NBUF - 1 < t_end) dma(tile + G::NBUF - 1, nbuf);
-#endif
     const int bo = buf * G::BUF;
 #pragma unroll
     for (int ks = 0; ks < G::NKS; ++ks) {
@@ -229,13 +223,9 @@ __global__ __launch_bounds__(G::NTHR, 2) void dwgrad3_pl_kernel(const WpArgs a) 
 #pragma unroll
           for (int mt = 0; mt < G::MT; ++mt) {
             f32x4 c = acc[mt][j];
-#ifdef WP_NO_MFMA
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mt][0] + af[mt][1], bf[1] + bf[0], c, 0, 0, 0);
-#else
             c = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mt][0], bf[1], c, 0, 0, 0);   // h l
             c = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mt][1], bf[0], c, 0, 0, 0);   // l h
             c = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mt][0], bf[0], c, 0, 0, 0);   // h h
-#endif
             acc[mt][j] = c;
           }
         }
@@ -252,17 +242,6 @@ __global__ __launch_bounds__(G::NTHR, 2) void dwgrad3_pl_kernel(const WpArgs a) 
 
   // ---- this block's partial sums: slab[split][o][ky][kx][c] --------------------------------------------------------------------
   float* out = a.slabs + (long long)split * a.slab_stride;
-#ifdef WP_NO_STORE
-  if (a.splits > 0) {
-    float t = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < G::MT; ++mt)
-#pragma unroll
-      for (int j = 0; j < G::NTW; ++j) t += acc[mt][j][0] + acc[mt][j][1] + acc[mt][j][2] + acc[mt][j][3];
-    if (t == 1.2345e-30f) out[0] = t;
-    return;
-  }
-#endif
 #pragma unroll
   for (int mt = 0; mt < G::MT; ++mt)
 #pragma unroll
@@ -304,21 +283,11 @@ __global__ __launch_bounds__(256) void dwgrad3_pl_reduce_kernel(const float* __r
 }
 
 using Wp48 = WpCfg<48, 48, 3, 1, 4, 4, 2>;   // one block: all 48 x 432 accumulators, tiles 4 x 16, two image buffers of 33 KB
-#ifdef WP_ALT96
-using Wp96 = WpCfg<48, 48, 1, 1, 4, 4, 2>;   // A/B: 48 co x (one filter row x 48 ci), tiles 4 x 16
-#elif defined(WP_ROWS3)
-// A/B: block = 96 co x (ALL THREE filter rows x 48 ci): 42 accumulators per wave (224 registers), a tile is 126 MFMAs per wave and dy is
-// fetched by 2 variants of a split instead of 6.  Standalone it wins (reduction included: 61.6 -> 59.0 us at 96 channels, 59.8 -> 58.3 at 192,
-// 66.7 -> 56.4 at 384; the kernel alone 61.7 -> 55.2 us in the step), but its slabs are 3 x (85 MB per layer; reduction 8.6 -> 21 us), and the
-// whole step LOSES 1.7 - 2 ms with it (tools/ab_lib_bench.sh, three alternating rounds on one box: 118.1 - 118.6 against 119.8 - 121.9 ms).
-using Wp96 = WpCfg<96, 48, 3, 2, 2, 2, 2>;
-#else
 // block = 96 co x (one filter row x 48 ci), tiles 2 x 16, two image buffers of 23 KB: THREE blocks fit a CU (catseg_debug_dwgrad3_pl_occupancy),
 // which is what hides the LDS-DMA round trip behind a 45-MFMA tile.  A third image buffer costs the third block: 60 -> 92 us (PMC: the same
-// wave cycles over 1.5 x the wall time), not adopted.  Differential builds (tools/ab_wp.sh) price its LDS-DMA at 14 of 53 us
-// (MFMAs alone 28, fragment reads 5, slab store 3).
+// wave cycles over 1.5 x the wall time), not adopted.  Differential builds (tools/ab_wp.sh, removed; last present in 0775e16) price
+// its LDS-DMA at 14 of 53 us (MFMAs alone 28, fragment reads 5, slab store 3).
 using Wp96 = WpCfg<96, 48, 1, 2, 2, 2, 2>;
-#endif
 
 struct WpPlan { int kind, variants, splits, TH; };
 

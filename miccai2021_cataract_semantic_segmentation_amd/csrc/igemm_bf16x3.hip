@@ -279,21 +279,13 @@ __global__ __launch_bounds__(512, 2) void igemm_b3_kernel(const B3Args p) {
     for (int j = 0; j < NA; ++j) {
       const int c = achunk[j] * 8;
       const bool ok = tap_ok && ((amask[j] >> (ttap & 31)) & 1u) && (tck * 16 + c) < p.Cin;
-#ifdef B3G_BLOCKED   // address-only timing experiment (tools/ab_b3w.sh): activation planes [C/16][pixel][16]; values are garbage
-      pa[j] = ok ? p.a + ((long long)(tck * p.M + aoff[j] / p.lda + p.sign * (tky * p.dil * p.W + tkx * p.dil)) * 16 + (c & 8)) : zero;
-#else
       pa[j] = ok ? p.a + (aoff[j] + toff + c) : zero;
-#endif
     }
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
       const int c = bchunk[j] * 8;
       const bool ok = tap_ok && brow[j] < p.N && (tck * 16 + c) < p.Cin;
-#ifdef B3G_BLOCKED   // weight planes [K/16][N][16]
-      pb[j] = ok ? p.w + ((long long)((ttap * nck + tck) * p.N + brow[j]) * 16 + (c & 8)) : zero;
-#else
       pb[j] = ok ? p.w + ((long long)brow[j] * p.ldw + woff + c) : zero;
-#endif
     }
     if (++tck == nck) {
       tck = 0;
@@ -460,9 +452,6 @@ __global__ __launch_bounds__(512, 2) void igemm_b3_kernel(const B3Args p) {
 // compiler's own wait-count insertion knows the counters' state (inline asm is opaque to it)
 constexpr int waitcnt_imm(int vm, int lgkm) { return (vm & 15) | (7 << 4) | ((lgkm & 15) << 8) | ((vm >> 4) << 14); }
 
-#ifndef B3X_TAPS_INNER
-#define B3X_TAPS_INNER 1
-#endif
 template <bool BLK>
 __global__ __launch_bounds__(256, 1) void igemm_b3w_kernel(const B3Args p) {
   constexpr int TM = 4, TN = 4, WGN = 2;
@@ -560,7 +549,7 @@ __global__ __launch_bounds__(256, 1) void igemm_b3w_kernel(const B3Args p) {
   // plane shifted by a few pixels (L1 / L2 hits instead of nine passes over the whole plane through the fabric); planar planes keep
   // taps outer, chunks inner (consecutive K-steps walk along a pixel row's cache lines).
   auto advance = [&]() {
-    if (BLK && B3X_TAPS_INNER) {
+    if (BLK) {
       const int nx = tkx + 1, nt = ttap + 1;
       const bool wrapx = nx == p.kw, wrapt = nt == p.taps;
       tkx = wrapx ? 0 : nx;
@@ -605,36 +594,11 @@ __global__ __launch_bounds__(256, 1) void igemm_b3w_kernel(const B3Args p) {
     ra0 = rowa * 32 + ((h ^ ((rowa >> 3) & 1)) << 4);
     rb0 = 3 * PLANE_A + rowb * 32 + ((h ^ ((rowb >> 3) & 1)) << 4);
   }
-// (differential timing builds, tools/ab_b3w.sh: -DB3X_NO_PREP / _NO_DMA / _NO_READS / _NO_SYNC drop one ingredient of the K loop -- wrong
-//  results, the time difference is that ingredient's cost)
-#ifdef B3X_NO_DMA
-#define B3X_PIECE(f, i) do {} while (0)
-#else
-#define B3X_PIECE(f, i) piece(f, i)
-#endif
-#ifdef B3X_NO_PREP
-#define B3X_PREPA(j) do {} while (0)
-#define B3X_PREPB(j) do {} while (0)
-#define B3X_ADVANCE() do {} while (0)
-#else
-#define B3X_PREPA(j) prepA(j)
-#define B3X_PREPB(j) prepB(j)
-#define B3X_ADVANCE() advance()
-#endif
-#ifdef B3X_NO_READS
-#define B3X_READ(dst, base, off) do {} while (0)
-#else
-#define B3X_READ(dst, base, off) B3_DS_READ(dst, base, off)
-#endif
-#ifdef B3X_NO_SYNC
-#define B3X_SYNC() do {} while (0)
-#else
 #define B3X_SYNC()                                        \
   do {                                                    \
     __builtin_amdgcn_s_waitcnt(waitcnt_imm(12, 0));       \
     __builtin_amdgcn_s_barrier();                         \
   } while (0)
-#endif
 #define B3_DS_READ(dst, base, off) dst = *(const bf16x8*)((base) + (off))
 #define B3_READ_PLANE(slot, pl, A_, B_)                                                \
   do {                                                                                 \
@@ -741,30 +705,30 @@ __global__ __launch_bounds__(256, 1) void igemm_b3w_kernel(const B3Args p) {
       asm volatile("" ::: "memory");
       const char* aa_ = smem + nxt * SLAB + ra0;
       const char* bb_ = smem + nxt * SLAB + rb0;
-      B3X_READ(Al[0], aa_, 2 * PLANE_A + 0 * 1024); B3_MFMA(Ah, 0, Bm, 0);
-      B3X_READ(Al[1], aa_, 2 * PLANE_A + 1 * 1024); B3_MFMA(Ah, 0, Bm, 1);
-      B3X_READ(Al[2], aa_, 2 * PLANE_A + 2 * 1024); B3_MFMA(Ah, 0, Bm, 2);
-      B3X_READ(Al[3], aa_, 2 * PLANE_A + 3 * 1024); B3_MFMA(Ah, 0, Bm, 3);
-      B3X_READ(Bl[0], bb_, 2 * PLANE_B + 0 * 1024); B3_MFMA(Ah, 1, Bm, 0);
-      B3X_READ(Bl[1], bb_, 2 * PLANE_B + 1 * 1024); B3_MFMA(Ah, 1, Bm, 1);
-      B3X_READ(Bl[2], bb_, 2 * PLANE_B + 2 * 1024); B3_MFMA(Ah, 1, Bm, 2);
-      B3X_READ(Bl[3], bb_, 2 * PLANE_B + 3 * 1024); B3_MFMA(Ah, 1, Bm, 3);
-      B3X_PIECE(fill, 0); B3_MFMA(Ah, 2, Bm, 0);
-      B3X_PIECE(fill, 1); B3_MFMA(Ah, 2, Bm, 1);
-      B3X_PIECE(fill, 2); B3_MFMA(Ah, 2, Bm, 2);
-      B3X_PIECE(fill, 3); B3_MFMA(Ah, 2, Bm, 3);
-      B3X_PIECE(fill, 4); B3_MFMA(Ah, 3, Bm, 0);
-      B3X_PIECE(fill, 5); B3_MFMA(Ah, 3, Bm, 1);
-      B3X_PIECE(fill, 6); B3_MFMA(Ah, 3, Bm, 2);
-      B3X_PIECE(fill, 7); B3_MFMA(Ah, 3, Bm, 3);
-      B3X_READ(Ah[0], aa_, 0 * PLANE_A + 0 * 1024); B3_MFMA(Am, 0, Bh, 0);
-      B3X_READ(Ah[1], aa_, 0 * PLANE_A + 1 * 1024); B3_MFMA(Am, 0, Bh, 1);
-      B3X_READ(Ah[2], aa_, 0 * PLANE_A + 2 * 1024); B3_MFMA(Am, 0, Bh, 2);
-      B3X_READ(Ah[3], aa_, 0 * PLANE_A + 3 * 1024); B3_MFMA(Am, 0, Bh, 3);
-      B3X_PIECE(fill, 8); B3_MFMA(Am, 1, Bh, 0);
-      B3X_PIECE(fill, 9); B3_MFMA(Am, 1, Bh, 1);
-      B3X_PIECE(fill, 10); B3_MFMA(Am, 1, Bh, 2);
-      B3X_PIECE(fill, 11); B3_MFMA(Am, 1, Bh, 3);
+      B3_DS_READ(Al[0], aa_, 2 * PLANE_A + 0 * 1024); B3_MFMA(Ah, 0, Bm, 0);
+      B3_DS_READ(Al[1], aa_, 2 * PLANE_A + 1 * 1024); B3_MFMA(Ah, 0, Bm, 1);
+      B3_DS_READ(Al[2], aa_, 2 * PLANE_A + 2 * 1024); B3_MFMA(Ah, 0, Bm, 2);
+      B3_DS_READ(Al[3], aa_, 2 * PLANE_A + 3 * 1024); B3_MFMA(Ah, 0, Bm, 3);
+      B3_DS_READ(Bl[0], bb_, 2 * PLANE_B + 0 * 1024); B3_MFMA(Ah, 1, Bm, 0);
+      B3_DS_READ(Bl[1], bb_, 2 * PLANE_B + 1 * 1024); B3_MFMA(Ah, 1, Bm, 1);
+      B3_DS_READ(Bl[2], bb_, 2 * PLANE_B + 2 * 1024); B3_MFMA(Ah, 1, Bm, 2);
+      B3_DS_READ(Bl[3], bb_, 2 * PLANE_B + 3 * 1024); B3_MFMA(Ah, 1, Bm, 3);
+      piece(fill, 0); B3_MFMA(Ah, 2, Bm, 0);
+      piece(fill, 1); B3_MFMA(Ah, 2, Bm, 1);
+      piece(fill, 2); B3_MFMA(Ah, 2, Bm, 2);
+      piece(fill, 3); B3_MFMA(Ah, 2, Bm, 3);
+      piece(fill, 4); B3_MFMA(Ah, 3, Bm, 0);
+      piece(fill, 5); B3_MFMA(Ah, 3, Bm, 1);
+      piece(fill, 6); B3_MFMA(Ah, 3, Bm, 2);
+      piece(fill, 7); B3_MFMA(Ah, 3, Bm, 3);
+      B3_DS_READ(Ah[0], aa_, 0 * PLANE_A + 0 * 1024); B3_MFMA(Am, 0, Bh, 0);
+      B3_DS_READ(Ah[1], aa_, 0 * PLANE_A + 1 * 1024); B3_MFMA(Am, 0, Bh, 1);
+      B3_DS_READ(Ah[2], aa_, 0 * PLANE_A + 2 * 1024); B3_MFMA(Am, 0, Bh, 2);
+      B3_DS_READ(Ah[3], aa_, 0 * PLANE_A + 3 * 1024); B3_MFMA(Am, 0, Bh, 3);
+      piece(fill, 8); B3_MFMA(Am, 1, Bh, 0);
+      piece(fill, 9); B3_MFMA(Am, 1, Bh, 1);
+      piece(fill, 10); B3_MFMA(Am, 1, Bh, 2);
+      piece(fill, 11); B3_MFMA(Am, 1, Bh, 3);
        B3_MFMA(Am, 2, Bh, 0);
        B3_MFMA(Am, 2, Bh, 1);
        B3_MFMA(Am, 2, Bh, 2);
@@ -773,10 +737,10 @@ __global__ __launch_bounds__(256, 1) void igemm_b3w_kernel(const B3Args p) {
        B3_MFMA(Am, 3, Bh, 1);
        B3_MFMA(Am, 3, Bh, 2);
        B3_MFMA(Am, 3, Bh, 3);
-      B3X_READ(Bh[0], bb_, 0 * PLANE_B + 0 * 1024); B3_MFMA(Am, 0, Bm, 0);
-      B3X_READ(Bh[1], bb_, 0 * PLANE_B + 1 * 1024); B3_MFMA(Am, 0, Bm, 1);
-      B3X_READ(Bh[2], bb_, 0 * PLANE_B + 2 * 1024); B3_MFMA(Am, 0, Bm, 2);
-      B3X_READ(Bh[3], bb_, 0 * PLANE_B + 3 * 1024); B3_MFMA(Am, 0, Bm, 3);
+      B3_DS_READ(Bh[0], bb_, 0 * PLANE_B + 0 * 1024); B3_MFMA(Am, 0, Bm, 0);
+      B3_DS_READ(Bh[1], bb_, 0 * PLANE_B + 1 * 1024); B3_MFMA(Am, 0, Bm, 1);
+      B3_DS_READ(Bh[2], bb_, 0 * PLANE_B + 2 * 1024); B3_MFMA(Am, 0, Bm, 2);
+      B3_DS_READ(Bh[3], bb_, 0 * PLANE_B + 3 * 1024); B3_MFMA(Am, 0, Bm, 3);
        B3_MFMA(Am, 1, Bm, 0);
        B3_MFMA(Am, 1, Bm, 1);
        B3_MFMA(Am, 1, Bm, 2);
@@ -790,31 +754,31 @@ __global__ __launch_bounds__(256, 1) void igemm_b3w_kernel(const B3Args p) {
        B3_MFMA(Am, 3, Bm, 2);
        B3_MFMA(Am, 3, Bm, 3);
        B3_MFMA(Ah, 0, Bh, 0);
-      B3X_READ(Am[0], aa_, 1 * PLANE_A + 0 * 1024); B3_MFMA(Ah, 0, Bh, 1);
-      B3X_READ(Am[1], aa_, 1 * PLANE_A + 1 * 1024); B3_MFMA(Ah, 0, Bh, 2);
-      B3X_READ(Am[2], aa_, 1 * PLANE_A + 2 * 1024); B3_MFMA(Ah, 0, Bh, 3);
-      B3X_READ(Am[3], aa_, 1 * PLANE_A + 3 * 1024); B3_MFMA(Ah, 1, Bh, 0);
-      B3X_READ(Bm[0], bb_, 1 * PLANE_B + 0 * 1024); B3_MFMA(Ah, 1, Bh, 1);
-      B3X_READ(Bm[1], bb_, 1 * PLANE_B + 1 * 1024); B3_MFMA(Ah, 1, Bh, 2);
-      B3X_READ(Bm[2], bb_, 1 * PLANE_B + 2 * 1024); B3_MFMA(Ah, 1, Bh, 3);
-      B3X_READ(Bm[3], bb_, 1 * PLANE_B + 3 * 1024); B3_MFMA(Ah, 2, Bh, 0);
+      B3_DS_READ(Am[0], aa_, 1 * PLANE_A + 0 * 1024); B3_MFMA(Ah, 0, Bh, 1);
+      B3_DS_READ(Am[1], aa_, 1 * PLANE_A + 1 * 1024); B3_MFMA(Ah, 0, Bh, 2);
+      B3_DS_READ(Am[2], aa_, 1 * PLANE_A + 2 * 1024); B3_MFMA(Ah, 0, Bh, 3);
+      B3_DS_READ(Am[3], aa_, 1 * PLANE_A + 3 * 1024); B3_MFMA(Ah, 1, Bh, 0);
+      B3_DS_READ(Bm[0], bb_, 1 * PLANE_B + 0 * 1024); B3_MFMA(Ah, 1, Bh, 1);
+      B3_DS_READ(Bm[1], bb_, 1 * PLANE_B + 1 * 1024); B3_MFMA(Ah, 1, Bh, 2);
+      B3_DS_READ(Bm[2], bb_, 1 * PLANE_B + 2 * 1024); B3_MFMA(Ah, 1, Bh, 3);
+      B3_DS_READ(Bm[3], bb_, 1 * PLANE_B + 3 * 1024); B3_MFMA(Ah, 2, Bh, 0);
        B3_MFMA(Ah, 2, Bh, 1);
-      B3X_PREPA(0); B3_MFMA(Ah, 2, Bh, 2);
+      prepA(0); B3_MFMA(Ah, 2, Bh, 2);
        B3_MFMA(Ah, 2, Bh, 3);
        B3_MFMA(Ah, 3, Bh, 0);
-      B3X_PREPA(1); B3_MFMA(Ah, 3, Bh, 1);
+      prepA(1); B3_MFMA(Ah, 3, Bh, 1);
        B3_MFMA(Ah, 3, Bh, 2);
        B3_MFMA(Ah, 3, Bh, 3);
        B3_MFMA(Ah, 0, Bl, 0);
-      B3X_PREPB(0); B3_MFMA(Ah, 0, Bl, 1);
+      prepB(0); B3_MFMA(Ah, 0, Bl, 1);
        B3_MFMA(Ah, 0, Bl, 2);
        B3_MFMA(Ah, 0, Bl, 3);
        B3_MFMA(Ah, 1, Bl, 0);
-      B3X_PREPB(1); B3_MFMA(Ah, 1, Bl, 1);
+      prepB(1); B3_MFMA(Ah, 1, Bl, 1);
        B3_MFMA(Ah, 1, Bl, 2);
        B3_MFMA(Ah, 1, Bl, 3);
        B3_MFMA(Ah, 2, Bl, 0);
-      B3X_ADVANCE(); B3_MFMA(Ah, 2, Bl, 1);
+      advance(); B3_MFMA(Ah, 2, Bl, 1);
        B3_MFMA(Ah, 2, Bl, 2);
        B3_MFMA(Ah, 2, Bl, 3);
        B3_MFMA(Ah, 3, Bl, 0);
@@ -906,29 +870,11 @@ struct B3TArgs {
   const float* zero;
 };
 
-// (differential timing builds of the backward-weight kernel: -DB3T_NO_PREP / _NO_DMA / _NO_SYNC drop one ingredient of its K loop --
-//  wrong results, the time difference is that ingredient's cost)
-#ifdef B3T_NO_DMA
-#define B3T_PIECE(f, i) do {} while (0)
-#else
-#define B3T_PIECE(f, i) piece(f, i)
-#endif
-#ifdef B3T_NO_PREP
-#define B3T_PREPA() do {} while (0)
-#define B3T_PREPB(j) do {} while (0)
-#else
-#define B3T_PREPA() prepA()
-#define B3T_PREPB(j) prepB(j)
-#endif
-#ifdef B3T_NO_SYNC
-#define B3T_SYNC() do {} while (0)
-#else
 #define B3T_SYNC()                                           \
   do {                                                       \
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         \
     __builtin_amdgcn_s_barrier();                            \
   } while (0)
-#endif
 __global__ __launch_bounds__(256, 1) void igemm_b3t_kernel(const B3TArgs p) {
   constexpr int TM = 4, TN = 4;
   constexpr int PLANE = 16 * 256 * 2;             // bytes of one operand plane image: 16 pixel rows x 256 columns of bf16
@@ -1091,47 +1037,47 @@ __global__ __launch_bounds__(256, 1) void igemm_b3t_kernel(const B3TArgs p) {
       const char* aa_[TM]; const char* bb_[TN];
 #pragma unroll
       for (int t = 0; t < TM; ++t) { aa_[t] = smem + nxt * SLAB + ra[t]; bb_[t] = smem + nxt * SLAB + rb[t]; }
-      B3T_PIECE(fill, 0); B3_MFMA(Ah, 0, Bh, 0);
+      piece(fill, 0); B3_MFMA(Ah, 0, Bh, 0);
        B3_MFMA(Ah, 0, Bh, 1);
        B3_MFMA(Ah, 0, Bh, 2);
-      B3T_PIECE(fill, 1); B3_MFMA(Ah, 0, Bh, 3);
+      piece(fill, 1); B3_MFMA(Ah, 0, Bh, 3);
        B3_MFMA(Ah, 1, Bh, 0);
        B3_MFMA(Ah, 1, Bh, 1);
-      B3T_PIECE(fill, 2); B3_MFMA(Ah, 1, Bh, 2);
+      piece(fill, 2); B3_MFMA(Ah, 1, Bh, 2);
        B3_MFMA(Ah, 1, Bh, 3);
        B3_MFMA(Ah, 2, Bh, 0);
-      B3T_PIECE(fill, 3); B3_MFMA(Ah, 2, Bh, 1);
+      piece(fill, 3); B3_MFMA(Ah, 2, Bh, 1);
        B3_MFMA(Ah, 2, Bh, 2);
        B3_MFMA(Ah, 2, Bh, 3);
-      B3T_PIECE(fill, 4); B3_MFMA(Ah, 3, Bh, 0);
+      piece(fill, 4); B3_MFMA(Ah, 3, Bh, 0);
        B3_MFMA(Ah, 3, Bh, 1);
        B3_MFMA(Ah, 3, Bh, 2);
-      B3T_PIECE(fill, 5); B3_MFMA(Ah, 3, Bh, 3);
+      piece(fill, 5); B3_MFMA(Ah, 3, Bh, 3);
        B3_MFMA(Ah, 0, Bl, 0);
        B3_MFMA(Ah, 0, Bl, 1);
-      B3T_PIECE(fill, 6); B3_MFMA(Ah, 0, Bl, 2);
+      piece(fill, 6); B3_MFMA(Ah, 0, Bl, 2);
        B3_MFMA(Ah, 0, Bl, 3);
        B3_MFMA(Ah, 1, Bl, 0);
-      B3T_PIECE(fill, 7); B3_MFMA(Ah, 1, Bl, 1);
+      piece(fill, 7); B3_MFMA(Ah, 1, Bl, 1);
        B3_MFMA(Ah, 1, Bl, 2);
        B3_MFMA(Ah, 1, Bl, 3);
-      B3T_PIECE(fill, 8); B3_MFMA(Ah, 2, Bl, 0);
+      piece(fill, 8); B3_MFMA(Ah, 2, Bl, 0);
        B3_MFMA(Ah, 2, Bl, 1);
        B3_MFMA(Ah, 2, Bl, 2);
-      B3T_PIECE(fill, 9); B3_MFMA(Ah, 2, Bl, 3);
+      piece(fill, 9); B3_MFMA(Ah, 2, Bl, 3);
        B3_MFMA(Ah, 3, Bl, 0);
        B3_MFMA(Ah, 3, Bl, 1);
-      B3T_PIECE(fill, 10); B3_MFMA(Ah, 3, Bl, 2);
+      piece(fill, 10); B3_MFMA(Ah, 3, Bl, 2);
        B3_MFMA(Ah, 3, Bl, 3);
        B3_MFMA(Al, 0, Bh, 0);
-      B3T_PIECE(fill, 11); B3_MFMA(Al, 0, Bh, 1);
+      piece(fill, 11); B3_MFMA(Al, 0, Bh, 1);
        B3_MFMA(Al, 0, Bh, 2);
        B3_MFMA(Al, 0, Bh, 3);
-      B3T_PREPA(); B3_MFMA(Al, 1, Bh, 0);
+      prepA(); B3_MFMA(Al, 1, Bh, 0);
        B3_MFMA(Al, 1, Bh, 1);
-      B3T_PREPB(0); B3_MFMA(Al, 1, Bh, 2);
+      prepB(0); B3_MFMA(Al, 1, Bh, 2);
        B3_MFMA(Al, 1, Bh, 3);
-      B3T_PREPB(1); B3_MFMA(Al, 2, Bh, 0);
+      prepB(1); B3_MFMA(Al, 2, Bh, 0);
        B3_MFMA(Al, 2, Bh, 1);
        B3_MFMA(Al, 2, Bh, 2);
        B3_MFMA(Al, 2, Bh, 3);

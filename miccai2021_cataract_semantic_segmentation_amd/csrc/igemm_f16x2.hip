@@ -868,10 +868,7 @@ __global__ __launch_bounds__(256, 1) void igemm_h2t_kernel(const H2TArgs p) {
   constexpr int TM = 4, TN = 4;
   constexpr int PLANE = 16 * 256 * 2;             // bytes of one operand plane image: 16 pixel rows x 256 columns of fp16
   constexpr int SLAB = 4 * PLANE;                 // A planes 0..1, then B planes 0..1
-#ifndef H2T_NSLOT
-#define H2T_NSLOT 4
-#endif
-  constexpr int NSLOT = H2T_NSLOT;                // LDS-DMA runs NSLOT - 1 K-steps ahead
+  constexpr int NSLOT = 4;                        // LDS-DMA runs NSLOT - 1 K-steps ahead
   __shared__ __attribute__((aligned(16))) char smem[NSLOT * SLAB];
   typedef short s16x4 __attribute__((ext_vector_type(4)));
   typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
@@ -909,14 +906,10 @@ __global__ __launch_bounds__(256, 1) void igemm_h2t_kernel(const H2TArgs p) {
   bool bcv[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-#ifdef H2T_STAGE2
-    const int q = j * 256 + tid, krow = q >> 5, cl = (q & 31) ^ ((krow & 3) << 2);
-#else
     // LDS image of a plane: [group of 4 pixel rows][half of the 256 columns][pixel row & 3][16 chunks] -- one LDS-DMA instruction (64 lanes,
     // 1 KB of LDS) covers FOUR consecutive pixel rows x 16 chunks, so that with blocked planes a 16-channel chunk contributes 4 x 32 = 128
     // contiguous bytes per instruction (two rows x 32 chunks, the round-3 image, made that 64: +4 % on the kernel)
     const int q = j * 256 + tid, krow = ((q >> 7) << 2) | ((q >> 4) & 3), cl = ((((q >> 6) & 1) << 4) | (q & 15)) ^ ((krow & 3) << 2);
-#endif
     arow[j] = r_begin + krow;
     acol[j] = (m0 + cl * 8) < p.ldo ? m0 + cl * 8 : -1;
     brow[j] = r_begin + krow;
@@ -1010,13 +1003,8 @@ __global__ __launch_bounds__(256, 1) void igemm_h2t_kernel(const H2TArgs p) {
   int ra[TM], rb[TN];
   {
     const int g1 = (lane >> 4) & 1, q = (lane >> 2) & 3, pp = lane & 3;
-#ifdef H2T_STAGE2
-    const int rowb = (8 * h + q) * 512;               // pixel row 8h + q (+ 4 for the second read: + 2048 bytes)
-    const int hm = wm * 256, hn = wn * 256;
-#else
     const int rowb = h * 4096 + q * 256;              // pixel row 8h + q: row group 2h (+ 1 for the second read: + 2048 bytes), row q inside it
     const int hm = wm * 1024, hn = wn * 1024;         // the wave's half of the columns
-#endif
 #pragma unroll
     for (int t = 0; t < TM; ++t) ra[t] = rowb + hm + ((((t ^ q) << 2) + 2 * g1 + (pp >> 1)) << 4) + ((pp & 1) << 3);
 #pragma unroll
