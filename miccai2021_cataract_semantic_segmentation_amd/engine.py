@@ -915,9 +915,9 @@ class EngineNet(nn.Module):
         if bank is None or (bank is not False and (bank.flat is not fp.flat or bank.h2 != h2)):
             ws = []
             for m in self.modules():
-                if (isinstance(m, Conv2d) and not m.stem and m.kernel_size == (3, 3) and m.stride == (1, 1) and m.padding == (1, 1)
-                        and m.dilation == (1, 1) and m.groups == 1 and m.in_channels == m.out_channels
-                        and ops.lib.catseg_dconv3_supported(m.in_channels) and id(m.weight) in fp.offsets):
+                if (isinstance(m, Conv2d) and not m.stem and m.stride[0] == m.stride[1] and m.padding[0] == m.padding[1]
+                        and m.dilation[0] == m.dilation[1] and id(m.weight) in fp.offsets
+                        and ops.d3_layer(m.in_channels, m.out_channels, *m.kernel_size, m.stride[0], m.padding[0], m.dilation[0], m.groups)):
                     ws.append((m.weight.data, fp.offsets[id(m.weight)]))
             bank = ops.Dconv3Bank(fp.flat, ws, h2=h2) if ws else False
             self._d3bank = bank
@@ -934,13 +934,11 @@ class EngineNet(nn.Module):
                         and m.stride[0] == m.stride[1] and m.padding[0] == m.padding[1] and m.dilation[0] == m.dilation[1]):
                     continue
                 O, I, (kh, kw), st, pd, dl = m.out_channels, m.in_channels, m.kernel_size, m.stride[0], m.padding[0], m.dilation[0]
-                if (kh, kw) == (1, 1) and st == 1 and pd == 0:
-                    if ops.lib.catseg_pconv1_supported(O, I) and ops.lib.catseg_pconv1_supported(I, O):
+                if ops.p1_geometry(kh, kw, st, pd, 1):
+                    if ops.p1_layer(I, O, kh, kw, st, pd, 1) and ops.p1_layer(O, I, kh, kw, st, pd, 1):      # (forward and backward-data images)
                         ws.append((m.weight.data, fp.offsets[id(m.weight)], 1, 0, 1))
-                elif ops.G1 and not (kh == 3 and kw == 3 and st == 1 and pd == 1 and dl == 1 and I == O and ops.lib.catseg_dconv3_supported(I)):
-                    d = ops._g1_desc(I, O, kh, kw, st, pd, dl)
-                    if (ops.lib.catseg_gconv_supported(__import__("ctypes").byref(d))
-                            and ops.lib.catseg_pconv1_supported(I, ((kh + st - 1) // st) * ((kw + st - 1) // st) * O)):
+                elif ops.G1 and not ops.d3_layer(I, O, kh, kw, st, pd, dl, 1):
+                    if ops.g1_dgrad_layer(ops._g1_desc(I, O, kh, kw, st, pd, dl), I, O, kh, kw, st):
                         ws.append((m.weight.data, fp.offsets[id(m.weight)], st, pd, dl))
             bank = ops.P1Bank(fp.flat, ws) if ws else False
             self._p1bank = bank

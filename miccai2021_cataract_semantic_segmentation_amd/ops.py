@@ -5,6 +5,7 @@ contiguous and whose pixel stride ``ld = t.stride(2)`` may exceed C (a view into
 a wider concat buffer).  Conv weights are [O, I, kh, kw] tensors in
 channels_last memory format (physical OHWI).  Nothing here touches autograd.
 """
+import collections
 import ctypes
 
 import torch
@@ -107,10 +108,9 @@ class _Timed:
 
 # Arithmetic of the large convolutions: "fp32" = v_mfma_f32_32x32x2_f32 (an exact fp32 FMA chain), "bf16x3" = every fp32
 # operand split exactly into three bf16 planes, six bf16 MFMA partial products per block, fp32 accumulate (csrc/igemm_bf16x3.hip:
-# error vs an fp64 reference equal to or below the fp32 kernel's, 1.45-1.6x its speed on the layers it takes).  Only forward /
-# backward-data of dense 3x3-class convolutions with a long reduction and >= 192 output columns qualify; everything else runs
-# the fp32 kernels.  CATSEG_PRECISION=fp32 selects the exact fp32 path everywhere.
-import os as _os
+# error vs an fp64 reference equal to or below the fp32 kernel's, 1.45-1.6x its speed on the layers it takes).  Which kernel family
+# runs a layer is decided in ONE place, the route planner below (fwd_route / dgrad_route / wgrad_route); the thresholds it reads are the
+# module attributes of this file.  CATSEG_PRECISION=fp32 selects the exact fp32 path everywhere.
 PRECISION = _plan.get("precision")
 _b3_cache = {"key": None, "x": None, "planar": None, "blk": None}
 # thresholds of the layer selection (tests lower them to push small layers through the split-precision kernels)
@@ -154,10 +154,14 @@ B3_BLOCKED = True
 B3_PLANE_LIMIT = (1 << 32) - 64     # bytes of the three blocked planes of one operand (one 32-bit-offset buffer resource); tests lower it
 
 
+def _b3_blocked_shape(ncols, cred):
+    """the layer's extents suit the 256 x 256 kernel on blocked planes; cred: channels of the gathered operand (a multiple of 16)"""
+    return B3_BLOCKED and ncols > 192 and cred % 16 == 0
+
+
 def _b3_blocked_ok(ncols, cred, a_rows, w_rows, taps):
-    """cred: channels of the gathered operand (a multiple of 16); the three planes of an operand must stay below 4 GB (the
-    kernel addresses them through one 32-bit-offset buffer resource)"""
-    return (B3_BLOCKED and ncols > 192 and cred % 16 == 0 and 6 * a_rows * cred < B3_PLANE_LIMIT
+    """... and the three planes of an operand stay below 4 GB (the kernel addresses them through one 32-bit-offset buffer resource)"""
+    return (_b3_blocked_shape(ncols, cred) and 6 * a_rows * cred < B3_PLANE_LIMIT
             and 6 * w_rows * taps * cred < B3_PLANE_LIMIT)
 
 
@@ -268,9 +272,14 @@ DCONV3_MIN_ROWS = 2048
 _d3_wimg = {}
 
 
+def d3_layer(Cin, Cout, kh, kw, stride, pad, dil, groups):
+    """a layer of the direct 3x3 kernels by geometry and library support, whatever its map size and the plan (the planner's _d3_ok and the
+    engine's weight-image bank share it)"""
+    return bool(kh == 3 and kw == 3 and stride == 1 and pad == 1 and dil == 1 and groups == 1 and Cin == Cout and lib.catseg_dconv3_supported(Cin))
+
+
 def _d3_ok(rows, Cin, Cout, kh, kw, stride, pad, dil, groups):
-    return (DCONV3 and PRECISION == "bf16x3" and kh == 3 and kw == 3 and stride == 1 and pad == 1 and dil == 1 and groups == 1
-            and Cin == Cout and rows >= DCONV3_MIN_ROWS and lib.catseg_dconv3_supported(Cin))
+    return DCONV3 and PRECISION == "bf16x3" and rows >= DCONV3_MIN_ROWS and d3_layer(Cin, Cout, kh, kw, stride, pad, dil, groups)
 
 
 # Arithmetic of the direct trunk kernels' forward / backward-data: "f16x2" = two fp16 planes, three products (csrc/dconv3_f16x2.hip) for
@@ -481,9 +490,19 @@ P1_OPS = _plan.get("p1_ops")
 _p1_wimg = {}
 
 
+def p1_geometry(kh, kw, stride, pad, groups):
+    """a pointwise layer by geometry"""
+    return kh == 1 and kw == 1 and stride == 1 and pad == 0 and groups == 1
+
+
+def p1_layer(Cin, Cout, kh, kw, stride, pad, groups):
+    """a layer of the pointwise kernel (forward: N = Cout columns from K = Cin; backward-data: the same question with the two exchanged) by
+    geometry and library support (shared by the planner and the engine's weight-image bank)"""
+    return bool(p1_geometry(kh, kw, stride, pad, groups) and lib.catseg_pconv1_supported(Cout, Cin))
+
+
 def _p1_ok(rows, Cin, Cout, kh, kw, stride, pad, dil, groups):
-    return (P1 and _trunk_h2() and kh == 1 and kw == 1 and stride == 1 and pad == 0 and groups == 1 and rows >= P1_MIN_ROWS
-            and not _b3_wide_1x1(rows, Cout, 1, Cin))
+    return P1 and _trunk_h2() and p1_geometry(kh, kw, stride, pad, groups) and rows >= P1_MIN_ROWS and not _b3_wide_1x1(rows, Cout, 1, Cin)
 
 
 _P1_ENTRY = [("w", "<i8"), ("img", "<i8"), ("O", "<i4"), ("I", "<i4"), ("kh", "<i4"), ("kw", "<i4"), ("t", "<i4"), ("ky0", "<i4"), ("kys", "<i4"),
@@ -566,6 +585,14 @@ G1_OPS = _plan.get("g1_ops")
 def _g1_ok(rows, Cin, Cout, kh, kw, stride, pad, dil, groups):
     return (G1 and _trunk_h2() and groups == 1 and (kh * kw > 1 or stride > 1) and rows >= G1_MIN_ROWS and Cin % 8 == 0 and Cin >= G1_MIN_CIN
             and not _b3_eligible(rows, Cout, kh * kw, Cin, stride == 1))
+
+
+def g1_dgrad_layer(desc, Cin, Cout, kh, kw, stride):
+    """backward-data of a gather layer by library support: desc (the layer's descriptor, or _g1_desc's shape-independent one) is a gather
+    launch, and its parity-class launches are pointwise GEMMs with N = Cin, K = (taps of a class) * Cout (shared by the planner and the
+    engine's weight-image bank)"""
+    return bool(lib.catseg_gconv_supported(ctypes.byref(desc))
+                and lib.catseg_pconv1_supported(Cin, ((kh + stride - 1) // stride) * ((kw + stride - 1) // stride) * Cout))
 
 
 def g1_weight_image(w, backward_data, stride, pad, dil):
@@ -788,6 +815,140 @@ def _refuse_h2_only(t, what):
         raise RuntimeError("a tensor that exists only as blocked f16x2 planes reached %s, which reads fp32 (its fp32 tensor was never written)" % what)
 
 
+# ---------------------------------------------------------------------------------------------- the route planner
+# Which kernel family runs a convolution, per direction: fwd_route / dgrad_route / wgrad_route map a Layer (shapes, the flags of the call and
+# facts about the operands -- no tensor data, nothing is launched) to a Route.  Every rung's condition is written here and nowhere else;
+# the rungs are tried in the order they are written.  conv_fwd / conv_bwd_data / conv_bwd_weight plan, then launch; the predictors
+# (h2_dy_route, concat_planes_route, conv_fwd_fused, the h2-only guards) ask the same functions with the operand facts they assume.
+#   d3p  direct 3x3 trunk kernel on producer-written fp16 x 2 planes (dconv3_pl.hip)         s2p  gather launches of pconv1.hip
+#   d3h  direct 3x3 trunk kernel, f16x2, split in the kernel from an amax record             h2   blocked-plane GEMM, f16x2 (igemm_f16x2.hip)
+#   d3   direct 3x3 trunk kernel, bf16x3 (no record needed)                                  b3   bf16x3 GEMM, blocked or planar planes
+#   p1   pointwise kernel (pconv1.hip)                                                       f32  fp32 implicit GEMM (igemm.hip)
+# The thresholds are read from this module's attributes at call time (tests, bench.py and the A/B tools assign to them after import).
+Route = collections.namedtuple("Route", "kind blocked")     # blocked: the GEMM reads blocked planes (h2 / b3 only)
+D3P, D3H, D3, P1R, S2P, F32 = (Route(k, False) for k in ("d3p", "d3h", "d3", "p1", "s2p", "f32"))
+H2_BLOCKED = Route("h2", True)      # the one route that can read planes registered for a tensor (register_h2_planes)
+
+
+class Layer:
+    """what the planner knows of one convolution call.  xshape = (B, H, W, Cin) of the input side, ldx / ldy the pixel strides of the tensors
+    on the input side (x, dx) and the output side (y, dy); yshape: dy's shape where the caller holds one (default: what the geometry gives).
+    Flags: stem4, exact, zero_to, bias (present), w4d (the weight / its gradient is a 4-D tensor).  Operand facts: x_amax / dy_amax (the
+    tensor carries an amax record), x_planes (producer-written planes)."""
+    __slots__ = ("xshape", "B", "H", "W", "Cin", "Cout", "kh", "kw", "stride", "pad", "dil", "groups", "ldx", "ldy", "yshape", "rows_i", "rows_o",
+                 "stem4", "exact", "zero_to", "bias", "w4d", "x_amax", "x_planes", "dy_amax")
+
+    def __init__(self, xshape, Cout, kh, kw, stride=1, pad=0, dil=1, groups=1, ldx=None, ldy=None, yshape=None, stem4=False, exact=False,
+                 zero_to=0, bias=False, w4d=True, x_amax=False, x_planes=False, dy_amax=False):
+        self.xshape = tuple(xshape)
+        self.B, self.H, self.W, self.Cin = B, H, W, Cin = self.xshape
+        self.Cout, self.kh, self.kw, self.stride, self.pad, self.dil, self.groups = Cout, kh, kw, stride, pad, dil, groups
+        self.ldx, self.ldy = ldx or (Cin + 3) // 4 * 4, ldy or (Cout + 3) // 4 * 4
+        self.yshape = tuple(yshape) if yshape is not None else (B, conv_out_size(H, kh, stride, pad, dil), conv_out_size(W, kw, stride, pad, dil), Cout)
+        self.rows_i, self.rows_o = B * H * W, 1
+        for n in self.yshape[:-1]:
+            self.rows_o *= n
+        self.stem4, self.exact, self.zero_to, self.bias, self.w4d = stem4, exact, zero_to, bias, w4d
+        self.x_amax, self.x_planes, self.dy_amax = x_amax, x_planes, dy_amax
+
+    def geom(self, transposed=False):
+        """the argument tail of the _d3_ok / _p1_ok / _g1_ok predicates; transposed: input and output channels exchanged (backward-data as a forward)"""
+        cc = (self.Cout, self.Cin) if transposed else (self.Cin, self.Cout)
+        return cc + (self.kh, self.kw, self.stride, self.pad, self.dil, self.groups)
+
+    def desc(self):
+        return make_desc(self.xshape, self.ldx, self.Cout, self.ldy, self.kh, self.kw, self.stride, self.pad, self.dil)
+
+    def y_fits(self):
+        """the output-side tensor has the size the geometry gives (a caller may hand backward a cropped or padded dy)"""
+        d = self.desc()
+        return d.Ho == self.yshape[1] and d.Wo == self.yshape[2]
+
+
+def _small(rows, ld):
+    """a tensor the pointwise / gather kernels can address (32-bit byte offsets)"""
+    return rows * ld * 4 < B3_PLANE_LIMIT
+
+
+def _fwd_gemm_ok(L):
+    return (not L.exact and "fwd" in B3_OPS and not L.stem4 and L.groups == 1 and L.w4d
+            and _b3_eligible(L.rows_o, L.Cout, L.kh * L.kw, L.Cin))
+
+
+def fwd_route(L):
+    taps = L.kh * L.kw
+    dense = not L.exact and not L.stem4 and L.zero_to == 0 and L.w4d      # the direct / pointwise / gather kernels: no exact operands, no padded output
+    if dense and _d3_ok(L.rows_o, *L.geom()):
+        if not L.bias and planes_ok(L.Cin, L.rows_o) and (L.x_planes or L.x_amax):
+            return D3P
+        return D3H if L.x_amax and _trunk_h2() else D3
+    if (dense and "fwd" in P1_OPS and L.x_amax and _p1_ok(L.rows_o, *L.geom()) and lib.catseg_pconv1_supported(L.Cout, L.Cin)
+            and _small(L.rows_o, L.ldx)):
+        return P1R
+    if (dense and "fwd" in G1_OPS and L.x_amax and _g1_ok(L.rows_o, *L.geom()) and _small(L.rows_i, L.ldx)
+            and lib.catseg_gconv_supported(ctypes.byref(L.desc()))):
+        return S2P
+    if _fwd_gemm_ok(L):
+        blk = _b3_blocked_ok(max(L.zero_to, L.Cout), L.Cin, L.rows_i, L.Cout, taps)
+        return Route("h2" if blk and _h2() else "b3", blk)
+    return F32
+
+
+def dgrad_route(L):
+    taps, cred = L.kh * L.kw, (L.Cout + 7) // 8 * 8
+    if L.w4d and _d3_ok(L.rows_i, *L.geom()):
+        return D3H if L.dy_amax and _trunk_h2() else D3
+    if (L.w4d and "dgrad" in P1_OPS and L.dy_amax and _p1_ok(L.rows_i, *L.geom(transposed=True)) and lib.catseg_pconv1_supported(L.Cin, L.Cout)
+            and _small(L.rows_o, L.ldy)):
+        return P1R
+    elig = _b3_eligible(L.rows_i, L.Cin, taps, cred, L.stride == 1)      # (the gather rung leaves these layers to the GEMM rung)
+    if (L.w4d and "dgrad" in G1_OPS and L.dy_amax and L.Cout % 8 == 0 and L.Cin >= G1_DGRAD_MIN_CIN and _g1_ok(L.rows_o, *L.geom())
+            and not elig and _small(L.rows_o, L.ldy) and g1_dgrad_layer(L.desc(), L.Cin, L.Cout, L.kh, L.kw, L.stride) and L.y_fits()):
+        return S2P
+    if L.groups == 1 and "dgrad" in B3_OPS and elig:
+        blk = _b3_blocked_ok(L.Cin, (L.Cout + 15) // 16 * 16, L.rows_o, L.Cin, taps)
+        return Route("h2" if blk and _h2() else "b3", blk)
+    return F32
+
+
+def _wgrad_gemm_ok(L):
+    """backward-weight runs the split-precision implicit GEMM (igemm_h2t / igemm_b3t) on planes of x and dy"""
+    taps = L.kh * L.kw
+    return bool(L.groups == 1 and "wgrad" in B3_OPS and not L.stem4 and PRECISION == "bf16x3" and L.Cin % 8 == 0 and
+                L.rows_i * L.Cin < B3_INDEX_LIMIT and L.rows_o * ((L.Cout + 7) // 8 * 8) < B3_INDEX_LIMIT and
+                ((B3_MIN_TAPS <= taps and taps * L.Cin >= B3_MIN_K and L.Cout >= B3_MIN_N and L.rows_o >= B3_MIN_WGRAD_ROWS)
+                 or (L.stride == 1 and _b3_wide_1x1(L.rows_o, L.Cout, taps, L.Cin))))
+
+
+def _wgrad_h2_ok(L):
+    """... on two fp16 planes per operand, each operand's planes behind one 32-bit-offset buffer resource"""
+    pad = 16 if H2T_BLOCKED else 8
+    return bool(_h2() and 4 * L.rows_i * ((L.Cin + pad - 1) // pad * pad) < B3_PLANE_LIMIT
+                and 4 * L.rows_o * ((L.Cout + pad - 1) // pad * pad) < B3_PLANE_LIMIT)
+
+
+def wgrad_route(L):
+    if not L.stem4 and _d3_ok(L.rows_o, *L.geom()) and lib.catseg_dwgrad3_supported(L.Cin):
+        return D3H if L.x_amax and L.dy_amax and _trunk_h2() else D3
+    recs = not L.stem4 and L.w4d and L.x_amax and L.dy_amax and _small(L.rows_i, L.ldx) and _small(L.rows_o, L.ldy)
+    if (recs and "wgrad" in P1_OPS and min(L.Cout, L.Cin) >= P1_WGRAD_MIN_DIM and _p1_ok(L.rows_o, *L.geom())
+            and lib.catseg_pconv1_wgrad_supported(L.Cout, L.Cin)):
+        return P1R
+    gemm = _wgrad_gemm_ok(L)
+    if (recs and "wgrad" in G1_OPS and _g1_ok(L.rows_o, *L.geom()) and not gemm and lib.catseg_gconv_wgrad_supported(ctypes.byref(L.desc()))
+            and L.y_fits()):
+        return S2P
+    if gemm:
+        return Route("h2", H2T_BLOCKED) if _wgrad_h2_ok(L) else Route("b3", False)
+    return F32
+
+
+def _h2_only_guard(x, route, what):
+    """a tensor that exists only as blocked f16x2 planes may only take the route that reads them"""
+    if getattr(x, "_h2_only", False) and route != H2_BLOCKED:
+        _refuse_h2_only(x, what)
+
+
 def conv_fwd(x, w_ptr_tensor, bias, Cout, kh, kw, stride=1, pad=0, dil=1, out=None, zero_to=0, stem4=False, groups=1, bn_stats=False, train=False,
              exact=False):
     """train=True (the engine's recorded forward): a backward pass will follow -- the split planes of x are written in both layouts
@@ -808,64 +969,54 @@ def conv_fwd(x, w_ptr_tensor, bias, Cout, kh, kw, stride=1, pad=0, dil=1, out=No
     if bn_stats:
         part = _bn_part_buffer(3 * ((rows + 63) // 64) * Cout, x.device)
         tr, nt = ctypes.c_int(0), ctypes.c_int(0)
-    if not exact and not stem4 and zero_to == 0 and w_ptr_tensor.dim() == 4 and _d3_ok(rows, Cin, Cout, kh, kw, stride, pad, dil, groups):
-        if bias is None and planes_ok(Cin, rows) and (planes_of(x) is not None or amax_of(x) is not None):
-            xp = planes_of(x)
-            if xp is None:      # a tensor whose producer wrote no planes (the first block behind a transition): one split pass, kept for backward
-                xp = planes_from_f32(x, rec=amax_of(x))
-                x._planes = xp
-            yrec = new_amax(x.device)
-            with _Timed("fwd_d3p", flops):
-                res = dconv3_pl(xp, dconv3_weight_image(w_ptr_tensor, h2=True), None, out=out, bn_stats=bn_stats, out_rec=yrec)
-            (res[0] if bn_stats else res)._yrec = yrec
-            return res
+    route = fwd_route(Layer(x.shape, Cout, kh, kw, stride, pad, dil, groups, ld_of(x), ld_of(out), stem4=stem4, exact=exact, zero_to=zero_to,
+                            bias=bias is not None, w4d=w_ptr_tensor.dim() == 4, x_amax=amax_of(x) is not None, x_planes=planes_of(x) is not None))
+    _h2_only_guard(x, route, "a convolution forward outside the blocked f16x2 route")
+    if route == D3P:
+        xp = planes_of(x)
+        if xp is None:      # a tensor whose producer wrote no planes (the first block behind a transition): one split pass, kept for backward
+            xp = planes_from_f32(x, rec=amax_of(x))
+            x._planes = xp
+        yrec = new_amax(x.device)
+        with _Timed("fwd_d3p", flops):
+            res = dconv3_pl(xp, dconv3_weight_image(w_ptr_tensor, h2=True), None, out=out, bn_stats=bn_stats, out_rec=yrec)
+        (res[0] if bn_stats else res)._yrec = yrec
+        return res
+    if route in (D3H, D3):
         _refuse_placeholder(x, "the in-kernel-split direct 3x3 kernel")
-        rec = amax_of(x) if _trunk_h2() else None
+        rec = amax_of(x) if route == D3H else None
         wimg = dconv3_weight_image(w_ptr_tensor, h2=rec is not None)
         with _Timed("fwd_d3h" if rec is not None else "fwd_d3", flops):
             res = dconv3(x, wimg, bias, out=out, bn_stats=bn_stats, x_amax=rec)
         return res
     _refuse_placeholder(x, "a convolution forward outside the planes route")
-    if getattr(x, "_h2_only", False) and not (not exact and "fwd" in B3_OPS and not stem4 and groups == 1 and w_ptr_tensor.dim() == 4 and amax_of(x) is None
-                                               and _b3_eligible(rows, Cout, kh * kw, Cin) and _h2()
-                                               and _b3_blocked_ok(max(zero_to, Cout), Cin, B * H * W, Cout, kh * kw)):
-        _refuse_h2_only(x, "a convolution forward outside the blocked f16x2 route")
-    if (not exact and not stem4 and zero_to == 0 and w_ptr_tensor.dim() == 4 and "fwd" in P1_OPS and amax_of(x) is not None
-            and _p1_ok(rows, Cin, Cout, kh, kw, stride, pad, dil, groups) and lib.catseg_pconv1_supported(Cout, Cin)
-            and rows * ld_of(x) * 4 < B3_PLANE_LIMIT):
+    if route == P1R:
         with _Timed("fwd_p1", flops):
             res = pconv1(x, p1_weight_image(w_ptr_tensor), bias, Cout, out, bn_stats=bn_stats)
         drop_amax(out)
         return res
-    if (not exact and not stem4 and zero_to == 0 and w_ptr_tensor.dim() == 4 and "fwd" in G1_OPS and amax_of(x) is not None
-            and _g1_ok(rows, Cin, Cout, kh, kw, stride, pad, dil, groups) and rows_of(x) * ld_of(x) * 4 < B3_PLANE_LIMIT):
+    if route == S2P:
         d = make_desc(x.shape, ld_of(x), Cout, ld_of(out), kh, kw, stride, pad, dil)
-        if lib.catseg_gconv_supported(ctypes.byref(d)):
-            if bn_stats:
-                part = _bn_part_buffer(3 * ((rows + 255) // 256) * Cout, x.device)
-            wimg = g1_weight_image(w_ptr_tensor, False, stride, pad, dil)
-            with _Timed("fwd_s2p", flops):
-                check(lib.catseg_gconv_fwd(ctypes.byref(d), ptr(x), ptr(amax_of(x)), ptr(wimg[0]), ptr(wimg[1]), ptr(bias), ptr(out), ptr(part),
-                                           part.numel() if part is not None else 0, ctypes.byref(tr) if bn_stats else None,
-                                           ctypes.byref(nt) if bn_stats else None, stream()))
-            drop_amax(out)
-            if bn_stats:
-                return out, ((part, nt.value, tr.value) if tr.value > 0 else None)
-            return out
-    if not exact and "fwd" in B3_OPS and not stem4 and groups == 1 and w_ptr_tensor.dim() == 4 and _b3_eligible(rows, Cout, kh * kw, Cin):
+        if bn_stats:
+            part = _bn_part_buffer(3 * ((rows + 255) // 256) * Cout, x.device)
+        wimg = g1_weight_image(w_ptr_tensor, False, stride, pad, dil)
+        with _Timed("fwd_s2p", flops):
+            check(lib.catseg_gconv_fwd(ctypes.byref(d), ptr(x), ptr(amax_of(x)), ptr(wimg[0]), ptr(wimg[1]), ptr(bias), ptr(out), ptr(part),
+                                       part.numel() if part is not None else 0, ctypes.byref(tr) if bn_stats else None,
+                                       ctypes.byref(nt) if bn_stats else None, stream()))
+        drop_amax(out)
+    elif route.kind == "h2":
         d = make_desc(x.shape, Cin, Cout, ld_of(out), kh, kw, stride, pad, dil)
-        blk = _b3_blocked_ok(max(zero_to, Cout), Cin, B * H * W, Cout, kh * kw)
-        if blk and _h2():
-            with _Timed("split3", 0.0):
-                xp, xsc = _split3_cached(x, "h2", both=train and not H2T_BLOCKED, keep=train)
-                wp, wsc = split2h_weight_blocked(w_ptr_tensor)
-            with _Timed("fwd_h2", flops):
-                check(lib.catseg_conv2d_fwd_f16x2_blocked(ctypes.byref(d), ptr(xp), ptr(xsc), ptr(wp), ptr(wsc), ptr(bias), ptr(out), zero_to,
-                                                          ptr(part), part.numel() if part is not None else 0,
-                                                          ctypes.byref(tr) if bn_stats else None, ctypes.byref(nt) if bn_stats else None, stream()))
-            if bn_stats:
-                return out, ((part, nt.value, tr.value) if tr.value > 0 else None)
-            return out
+        with _Timed("split3", 0.0):
+            xp, xsc = _split3_cached(x, "h2", both=train and not H2T_BLOCKED, keep=train)
+            wp, wsc = split2h_weight_blocked(w_ptr_tensor)
+        with _Timed("fwd_h2", flops):
+            check(lib.catseg_conv2d_fwd_f16x2_blocked(ctypes.byref(d), ptr(xp), ptr(xsc), ptr(wp), ptr(wsc), ptr(bias), ptr(out), zero_to,
+                                                      ptr(part), part.numel() if part is not None else 0,
+                                                      ctypes.byref(tr) if bn_stats else None, ctypes.byref(nt) if bn_stats else None, stream()))
+    elif route.kind == "b3":
+        d = make_desc(x.shape, Cin, Cout, ld_of(out), kh, kw, stride, pad, dil)
+        blk = route.blocked
         with _Timed("split3", 0.0):
             xp = _split3_cached(x, "blk" if blk else "planar", both=blk and train, keep=train)
             wp = split3_weight_blocked(w_ptr_tensor) if blk else split3_weight(w_ptr_tensor)
@@ -927,8 +1078,10 @@ def conv_bwd_data(dy, w, xshape, kh, kw, stride=1, pad=0, dil=1, out=None, accum
         accumulate = False
     drop_amax(out)
     flops = 2.0 * rows_of(dy) * Cout * (Cin // groups) * kh * kw
-    if w.dim() == 4 and _d3_ok(B * H * W, Cin, Cout, kh, kw, stride, pad, dil, groups):
-        rec = amax_of(dy) if _trunk_h2() else None
+    route = dgrad_route(Layer(xshape, Cout, kh, kw, stride, pad, dil, groups, ld_of(out), ld_of(dy), yshape=dy.shape, w4d=w.dim() == 4,
+                              dy_amax=amax_of(dy) is not None))
+    if route in (D3H, D3):
+        rec = amax_of(dy) if route == D3H else None
         wimg = dconv3_weight_image(w, backward_data=True, h2=rec is not None)
         kind = "dgrad_d3h" if rec is not None else "dgrad_d3"
         if bn_src is not None and BN_BWD_FUSE and not accumulate:
@@ -945,69 +1098,37 @@ def conv_bwd_data(dy, w, xshape, kh, kw, stride=1, pad=0, dil=1, out=None, accum
             return out, (part, nt)
         with _Timed(kind, flops):
             dconv3(dy, wimg, None, out=out, accumulate=accumulate, x_amax=rec)
-        return out
-    if (w.dim() == 4 and "dgrad" in P1_OPS and amax_of(dy) is not None and _p1_ok(B * H * W, Cout, Cin, kh, kw, stride, pad, dil, groups)
-            and lib.catseg_pconv1_supported(Cin, Cout) and rows_of(dy) * ld_of(dy) * 4 < B3_PLANE_LIMIT):
+    elif route == P1R:
         with _Timed("dgrad_p1", flops):
             pconv1(dy, p1_weight_image(w, transposed=True), None, Cin, out, accumulate=accumulate)
-        return out
-    if (w.dim() == 4 and "dgrad" in G1_OPS and amax_of(dy) is not None and Cout % 8 == 0 and Cin >= G1_DGRAD_MIN_CIN and _g1_ok(rows_of(dy), Cin, Cout, kh, kw, stride, pad, dil, groups)
-            and not _b3_eligible(B * H * W, Cin, kh * kw, (Cout + 7) // 8 * 8, stride == 1) and rows_of(dy) * ld_of(dy) * 4 < B3_PLANE_LIMIT):
+    elif route == S2P:
         d = make_desc(xshape, ld_of(out), Cout, ld_of(dy), kh, kw, stride, pad, dil)
-        dT = _g1_desc(Cout, Cin, kh, kw, stride, pad, dil)      # (the class launches are GEMMs with N = Cin, K = taps * Cout)
-        if (lib.catseg_gconv_supported(ctypes.byref(d)) and lib.catseg_pconv1_supported(Cin, ((kh + stride - 1) // stride) * ((kw + stride - 1) // stride) * Cout)
-                and d.Ho == dy.shape[1] and d.Wo == dy.shape[2]):
-            wimg = g1_weight_image(w, True, stride, pad, dil)
-            with _Timed("dgrad_s2p", flops):
-                check(lib.catseg_gconv_bwd_data(ctypes.byref(d), ptr(dy), ptr(amax_of(dy)), ptr(wimg[0]), ptr(wimg[1]), ptr(out),
-                                                1 if accumulate else 0, stream()))
-            del dT
-            return out
-    if groups == 1 and "dgrad" in B3_OPS and _b3_eligible(B * H * W, Cin, kh * kw, (Cout + 7) // 8 * 8, stride == 1):
+        wimg = g1_weight_image(w, True, stride, pad, dil)
+        with _Timed("dgrad_s2p", flops):
+            check(lib.catseg_gconv_bwd_data(ctypes.byref(d), ptr(dy), ptr(amax_of(dy)), ptr(wimg[0]), ptr(wimg[1]), ptr(out),
+                                            1 if accumulate else 0, stream()))
+    elif route.kind == "h2":
         d = make_desc(xshape, ld_of(out), Cout, (Cout + 7) // 8 * 8, kh, kw, stride, pad, dil)
-        blk = _b3_blocked_ok(Cin, (Cout + 15) // 16 * 16, rows_of(dy), Cin, kh * kw)
-        if blk and _h2():
-            with _Timed("split3", 0.0):
-                dyp, dysc = _split3_cached_dy(dy, "h2")
-                wtp, wtsc = split2h_weight_t_blocked(w)
-            with _Timed("dgrad_h2", flops):
-                check(lib.catseg_conv2d_bwd_data_f16x2_blocked(ctypes.byref(d), ptr(dyp), ptr(dysc), ptr(wtp), ptr(wtsc), ptr(out),
-                                                               1 if accumulate else 0, stream()))
-            return out
+        with _Timed("split3", 0.0):
+            dyp, dysc = _split3_cached_dy(dy, "h2")
+            wtp, wtsc = split2h_weight_t_blocked(w)
+        with _Timed("dgrad_h2", flops):
+            check(lib.catseg_conv2d_bwd_data_f16x2_blocked(ctypes.byref(d), ptr(dyp), ptr(dysc), ptr(wtp), ptr(wtsc), ptr(out),
+                                                           1 if accumulate else 0, stream()))
+    elif route.kind == "b3":
+        d = make_desc(xshape, ld_of(out), Cout, (Cout + 7) // 8 * 8, kh, kw, stride, pad, dil)
+        blk = route.blocked
         with _Timed("split3", 0.0):
             dyp = _split3_cached_dy(dy, "blk" if blk else "planar")
             wtp = split3_weight_t_blocked(w) if blk else split3_weight_t(w)
         with _Timed("dgrad_b3", flops):
             fn = lib.catseg_conv2d_bwd_data_bf16x3_blocked if blk else lib.catseg_conv2d_bwd_data_bf16x3
             check(fn(ctypes.byref(d), ptr(dyp), ptr(wtp), ptr(out), 1 if accumulate else 0, stream()))
-        return out
-    d = make_desc(xshape, ld_of(out), Cout, ld_of(dy), kh, kw, stride, pad, dil, False, groups)
-    with _Timed("dgrad", flops):
-        check(lib.catseg_conv2d_bwd_data(ctypes.byref(d), ptr(dy), ptr(w), ptr(out), 1 if accumulate else 0, stream()))
+    else:
+        d = make_desc(xshape, ld_of(out), Cout, ld_of(dy), kh, kw, stride, pad, dil, False, groups)
+        with _Timed("dgrad", flops):
+            check(lib.catseg_conv2d_bwd_data(ctypes.byref(d), ptr(dy), ptr(w), ptr(out), 1 if accumulate else 0, stream()))
     return out
-
-
-def _wgrad_split_route(x, dy, kh, kw, stride, stem4, groups):
-    """backward-weight of this layer runs the split-precision implicit GEMM (igemm_h2t / igemm_b3t) on planes of x and dy"""
-    Cout, Cin = dy.shape[-1], x.shape[-1]
-    return bool(groups == 1 and "wgrad" in B3_OPS and not stem4 and PRECISION == "bf16x3" and Cin % 8 == 0 and
-                rows_of(x) * Cin < B3_INDEX_LIMIT and rows_of(dy) * ((Cout + 7) // 8 * 8) < B3_INDEX_LIMIT and
-                ((B3_MIN_TAPS <= kh * kw and kh * kw * Cin >= B3_MIN_K and Cout >= B3_MIN_N and rows_of(dy) >= B3_MIN_WGRAD_ROWS)
-                 or (stride == 1 and _b3_wide_1x1(rows_of(dy), Cout, kh * kw, Cin))))
-
-
-def _wgrad_dgrad_blk(x, dy, kh, kw, stride):
-    """the layer's backward-data will read BLOCKED planes of dy: the backward-weight's split pass writes them as well"""
-    Cout, Cin = dy.shape[-1], x.shape[-1]
-    return bool(stride == 1 and "dgrad" in B3_OPS and _b3_eligible(rows_of(x), Cin, kh * kw, (Cout + 7) // 8 * 8)
-                and _b3_blocked_ok(Cin, (Cout + 15) // 16 * 16, rows_of(dy), Cin, kh * kw))
-
-
-def _wgrad_h2_route(x, dy):
-    Cout, Cin = dy.shape[-1], x.shape[-1]
-    pad = 16 if H2T_BLOCKED else 8
-    return bool(_h2() and 4 * rows_of(x) * ((Cin + pad - 1) // pad * pad) < B3_PLANE_LIMIT
-                and 4 * rows_of(dy) * ((Cout + pad - 1) // pad * pad) < B3_PLANE_LIMIT)
 
 
 def _wgrad_h2_planes(x, dy, dgrad_blk):
@@ -1026,68 +1147,54 @@ def conv_bwd_weight(x, dy, dw, dbias, kh, kw, stride=1, pad=0, dil=1, stem4=Fals
     Cout, Cin = dy.shape[-1], x.shape[-1]
     _refuse_placeholder(x, "conv_bwd_weight (fp32 input)")
     _refuse_placeholder(dy, "conv_bwd_weight (fp32 output gradient)")
-    if getattr(x, "_h2_only", False) and not (H2T_BLOCKED and not stem4 and amax_of(x) is None and _wgrad_split_route(x, dy, kh, kw, stride, stem4, groups)
-                                               and _wgrad_h2_route(x, dy)
-                                               and not (_d3_ok(rows_of(dy), Cin, Cout, kh, kw, stride, pad, dil, groups) and lib.catseg_dwgrad3_supported(Cin))):
-        _refuse_h2_only(x, "conv_bwd_weight outside the blocked f16x2 route")
+    L = Layer(x.shape, Cout, kh, kw, stride, pad, dil, groups, ld_of(x), ld_of(dy), yshape=dy.shape, stem4=stem4, w4d=dw.dim() == 4,
+              x_amax=amax_of(x) is not None, dy_amax=amax_of(dy) is not None)
+    route = wgrad_route(L)
+    _h2_only_guard(x, route, "conv_bwd_weight outside the blocked f16x2 route")
     flops = 2.0 * rows_of(dy) * Cout * (3 if stem4 else Cin // groups) * kh * kw
-    if (not stem4 and x.dim() == 4 and _d3_ok(rows_of(dy), Cin, Cout, kh, kw, stride, pad, dil, groups)
-            and lib.catseg_dwgrad3_supported(Cin)):
+    if route in (D3H, D3):
         dwgrad3(x, dy, dw, dbias, flops)
         return dw
-    if (not stem4 and x.dim() == 4 and dw.dim() == 4 and "wgrad" in P1_OPS and amax_of(x) is not None and amax_of(dy) is not None
-            and min(Cout, Cin) >= P1_WGRAD_MIN_DIM
-            and _p1_ok(rows_of(dy), Cin, Cout, kh, kw, stride, pad, dil, groups) and lib.catseg_pconv1_wgrad_supported(Cout, Cin)
-            and rows_of(x) * ld_of(x) * 4 < B3_PLANE_LIMIT and rows_of(dy) * ld_of(dy) * 4 < B3_PLANE_LIMIT):
+    if route == P1R:
         need = lib.catseg_pconv1_wgrad_workspace(rows_of(dy), Cout, Cin)
         ws = workspace(need + 256 * Cout * 4, x.device)
         with _Timed("wgrad_p1", flops):
             check(lib.catseg_pconv1_wgrad(rows_of(dy), Cout, Cin, ptr(dy), ld_of(dy), ptr(amax_of(dy)), ptr(x), ld_of(x), ptr(amax_of(x)), ptr(dw),
                                           ptr(ws), need, stream()))
-        if dbias is not None:
-            check(lib.catseg_bias_grad(ptr(dy), ld_of(dy), rows_of(dy), Cout, ptr(dbias), ptr(ws), ws.numel(), stream()))
-        return dw
-    if (not stem4 and x.dim() == 4 and dw.dim() == 4 and "wgrad" in G1_OPS and amax_of(x) is not None and amax_of(dy) is not None
-            and _g1_ok(rows_of(dy), Cin, Cout, kh, kw, stride, pad, dil, groups) and not _wgrad_split_route(x, dy, kh, kw, stride, stem4, groups)
-            and rows_of(x) * ld_of(x) * 4 < B3_PLANE_LIMIT and rows_of(dy) * ld_of(dy) * 4 < B3_PLANE_LIMIT):
+    elif route == S2P:
         d = make_desc(x.shape, ld_of(x), Cout, ld_of(dy), kh, kw, stride, pad, dil)
-        if lib.catseg_gconv_wgrad_supported(ctypes.byref(d)) and d.Ho == dy.shape[1] and d.Wo == dy.shape[2]:
-            need = lib.catseg_gconv_wgrad_workspace(ctypes.byref(d))
-            ws = workspace(need + 256 * Cout * 4, x.device)
-            with _Timed("wgrad_s2p", flops):
-                check(lib.catseg_gconv_bwd_weight(ctypes.byref(d), ptr(dy), ptr(amax_of(dy)), ptr(x), ptr(amax_of(x)), ptr(dw), ptr(ws), need, stream()))
-            if dbias is not None:
-                check(lib.catseg_bias_grad(ptr(dy), ld_of(dy), rows_of(dy), Cout, ptr(dbias), ptr(ws), ws.numel(), stream()))
-            return dw
-    if _wgrad_split_route(x, dy, kh, kw, stride, stem4, groups):
+        need = lib.catseg_gconv_wgrad_workspace(ctypes.byref(d))
+        ws = workspace(need + 256 * Cout * 4, x.device)
+        with _Timed("wgrad_s2p", flops):
+            check(lib.catseg_gconv_bwd_weight(ctypes.byref(d), ptr(dy), ptr(amax_of(dy)), ptr(x), ptr(amax_of(x)), ptr(dw), ptr(ws), need, stream()))
+    elif route.kind in ("h2", "b3"):
         d = make_desc(x.shape, Cin, Cout, (Cout + 7) // 8 * 8, kh, kw, stride, pad, dil)
         ws = workspace(lib.catseg_conv2d_bwd_weight_bf16x3_workspace(ctypes.byref(d)) + 256 * Cout * 4, x.device)
-        dgrad_blk = _wgrad_dgrad_blk(x, dy, kh, kw, stride)
-        if _wgrad_h2_route(x, dy):
+        dgrad_blk = dgrad_route(L).blocked     # the layer's backward-data will read BLOCKED planes of dy: this split pass writes them as well
+        if route.kind == "h2":
             # two fp16 planes per operand (csrc/igemm_f16x2.hip; each operand's planes behind one 32-bit-offset buffer resource); dy's
             # blocked planes for this layer's backward-data from the same pass
-            wsb = workspace(lib.catseg_conv2d_bwd_weight_f16x2_workspace(ctypes.byref(d)) + 256 * Cout * 4, x.device)
+            ws = workspace(lib.catseg_conv2d_bwd_weight_f16x2_workspace(ctypes.byref(d)) + 256 * Cout * 4, x.device)
             with _Timed("split3", 0.0):
                 xp, xsc, dyp, dysc = _wgrad_h2_planes(x, dy, dgrad_blk)
             with _Timed("wgrad_h2", flops):
                 fn = lib.catseg_conv2d_bwd_weight_f16x2_blocked if H2T_BLOCKED else lib.catseg_conv2d_bwd_weight_f16x2
-                check(fn(ctypes.byref(d), ptr(xp), ptr(xsc), ptr(dyp), ptr(dysc), ptr(dw), ptr(wsb), wsb.numel(), stream()))
-            if dbias is not None:
-                check(lib.catseg_bias_grad(ptr(dy), ld_of(dy), rows_of(dy), Cout, ptr(dbias), ptr(wsb), wsb.numel(), stream()))
-            return dw
-        with _Timed("split3", 0.0):
-            xp = _split3_cached(x, "planar")
-            dyp = _split3_cached_dy(dy, "planar", both=dgrad_blk)
-        with _Timed("wgrad_b3", flops):
-            check(lib.catseg_conv2d_bwd_weight_bf16x3(ctypes.byref(d), ptr(xp), ptr(dyp), ptr(dw), ptr(ws), ws.numel(), stream()))
-        if dbias is not None:
-            check(lib.catseg_bias_grad(ptr(dy), ld_of(dy), rows_of(dy), Cout, ptr(dbias), ptr(ws), ws.numel(), stream()))
+                check(fn(ctypes.byref(d), ptr(xp), ptr(xsc), ptr(dyp), ptr(dysc), ptr(dw), ptr(ws), ws.numel(), stream()))
+        else:
+            with _Timed("split3", 0.0):
+                xp = _split3_cached(x, "planar")
+                dyp = _split3_cached_dy(dy, "planar", both=dgrad_blk)
+            with _Timed("wgrad_b3", flops):
+                check(lib.catseg_conv2d_bwd_weight_bf16x3(ctypes.byref(d), ptr(xp), ptr(dyp), ptr(dw), ptr(ws), ws.numel(), stream()))
+    else:
+        d = make_desc(x.shape, ld_of(x), Cout, ld_of(dy), kh, kw, stride, pad, dil, stem4, groups)
+        need = lib.catseg_conv2d_bwd_weight_workspace(ctypes.byref(d))
+        ws = workspace(need, x.device)
+        with _Timed("wgrad", flops):
+            check(lib.catseg_conv2d_bwd_weight(ctypes.byref(d), ptr(x), ptr(dy), ptr(dw), ptr(dbias), ptr(ws), ws.numel(), stream()))
         return dw
-    d = make_desc(x.shape, ld_of(x), Cout, ld_of(dy), kh, kw, stride, pad, dil, stem4, groups)
-    need = lib.catseg_conv2d_bwd_weight_workspace(ctypes.byref(d))
-    ws = workspace(need, x.device)
-    with _Timed("wgrad", flops):
-        check(lib.catseg_conv2d_bwd_weight(ctypes.byref(d), ptr(x), ptr(dy), ptr(dw), ptr(dbias), ptr(ws), ws.numel(), stream()))
+    if dbias is not None:
+        check(lib.catseg_bias_grad(ptr(dy), ld_of(dy), rows_of(dy), Cout, ptr(dbias), ptr(ws), ws.numel(), stream()))
     return dw
 
 
@@ -1318,8 +1425,7 @@ CONCAT_PLANES = _plan.get("concat_planes")
 def concat_planes_route(ys, consumers):
     """True when every consumer (the Conv2d modules that read the concatenation of `ys` at ys[0]'s size) runs forward AND backward-weight on
     blocked f16x2 planes of its input: the concatenation then never needs to exist in fp32"""
-    import types
-    if not (CONCAT_PLANES and H2T_BLOCKED and _h2() and PRECISION == "bf16x3" and consumers and 1 <= len(ys) <= 4):
+    if not (CONCAT_PLANES and consumers and 1 <= len(ys) <= 4):
         return False
     if not all(y.is_cuda and y.dim() == 4 and y.shape[-1] % 16 == 0 and ld_of(y) % 4 == 0 and amax_of(y) is not None and y.shape[0] == ys[0].shape[0]
                for y in ys):
@@ -1328,19 +1434,14 @@ def concat_planes_route(ys, consumers):
     Cin, rows = sum(y.shape[-1] for y in ys), B * H * W
     if 4 * rows * Cin >= B3_PLANE_LIMIT:
         return False
-    x = types.SimpleNamespace(shape=(B, H, W, Cin))
     for conv in consumers:
         kh, kw = conv.kernel_size
         st, pd, dl, Cout = conv.stride[0], conv.padding[0], conv.dilation[0], conv.out_channels
         if (conv.in_channels != Cin or getattr(conv, "exact_operands", False) or getattr(conv, "stem", False) or conv.groups != 1
                 or conv_out_size(H, kh, st, pd, dl) != H or conv_out_size(W, kw, st, pd, dl) != W):
             return False
-        if _d3_ok(rows, Cin, Cout, kh, kw, st, pd, dl, 1):
-            return False
-        if not ("fwd" in B3_OPS and _b3_eligible(rows, Cout, kh * kw, Cin) and _b3_blocked_ok(Cout, Cin, rows, Cout, kh * kw)):
-            return False
-        dy = types.SimpleNamespace(shape=(B, H, W, Cout))
-        if not (_wgrad_split_route(x, dy, kh, kw, st, False, 1) and _wgrad_h2_route(x, dy)):
+        L = Layer((B, H, W, Cin), Cout, kh, kw, st, pd, dl, bias=conv.bias is not None)      # (the concatenation carries no amax record and no planes)
+        if fwd_route(L) != H2_BLOCKED or wgrad_route(L) != H2_BLOCKED:
             return False
     return True
 
@@ -1375,31 +1476,15 @@ HEAD_DY_PLANES = _plan.get("head_dy_planes")
 
 
 def h2_dy_route(x, y, w, kh, kw, stride, pad, dil, groups, need_dx):
-    """True when conv_bwd_weight / conv_bwd_data would BOTH run this layer on the blocked f16x2 planes of dy (the conditions below repeat
-    their route selection in its order; tests/test_heads_dy_planes_gpu.py pins the two against each other)"""
-    if not (HEAD_DY_PLANES and H2T_BLOCKED and _h2() and x.is_cuda and x.dim() == 4 and y.dim() == 4 and w.dim() == 4 and groups == 1):
+    """True when conv_bwd_weight / conv_bwd_data would BOTH run this layer on the blocked f16x2 planes of dy, whether or not x and dy
+    carry amax records (asked with records: that is when the pointwise / gather routes could take the layer instead)"""
+    if not (HEAD_DY_PLANES and x.is_cuda and x.dim() == 4 and y.dim() == 4 and w.dim() == 4):
         return False
-    Cout, Cin, taps = y.shape[-1], x.shape[-1], kh * kw
-    rows_o, rows_i = rows_of(y), rows_of(x)
-    if Cout % 64 != 0 or 4 * rows_o * Cout >= B3_PLANE_LIMIT:
+    Cout = y.shape[-1]
+    if Cout % 64 != 0 or 4 * rows_of(y) * Cout >= B3_PLANE_LIMIT:
         return False
-    # backward-weight: direct trunk kernel, pointwise kernel (the gather kernel is excluded by _wgrad_split_route), then the split route
-    if _d3_ok(rows_o, Cin, Cout, kh, kw, stride, pad, dil, groups) and lib.catseg_dwgrad3_supported(Cin):
-        return False
-    if ("wgrad" in P1_OPS and min(Cout, Cin) >= P1_WGRAD_MIN_DIM and _p1_ok(rows_o, Cin, Cout, kh, kw, stride, pad, dil, groups)
-            and lib.catseg_pconv1_wgrad_supported(Cout, Cin)):
-        return False
-    if not (_wgrad_split_route(x, y, kh, kw, stride, False, groups) and _wgrad_h2_route(x, y)):
-        return False
-    if need_dx:
-        if _d3_ok(rows_i, Cin, Cout, kh, kw, stride, pad, dil, groups):
-            return False
-        if "dgrad" in P1_OPS and _p1_ok(rows_i, Cout, Cin, kh, kw, stride, pad, dil, groups) and lib.catseg_pconv1_supported(Cin, Cout):
-            return False
-        if not (stride == 1 and "dgrad" in B3_OPS and _b3_eligible(rows_i, Cin, taps, (Cout + 7) // 8 * 8, True)
-                and _b3_blocked_ok(Cin, (Cout + 15) // 16 * 16, rows_o, Cin, taps)):
-            return False
-    return True
+    L = Layer(x.shape, Cout, kh, kw, stride, pad, dil, groups, yshape=y.shape, x_amax=True, dy_amax=True)
+    return wgrad_route(L) == H2_BLOCKED and (not need_dx or dgrad_route(L) == H2_BLOCKED)
 
 
 def bn_backward_h2(dz, y, stats, gamma, relu, dgamma, dbeta, beta, dbias=None):
@@ -1951,8 +2036,8 @@ def conv_fwd_fused(x, w, bias, residual, relu, Cout, kh, kw, stride=1, pad=0, di
     if out is None:
         out = new_act(B, Ho, Wo, Cout, x.device)
     flops = 2.0 * B * Ho * Wo * Cout * (3 if stem4 else Cin // groups) * kh * kw
-    if ("fwd" in B3_OPS and not stem4 and groups == 1 and w.numel() == Cout * kh * kw * Cin and _b3_eligible(B * Ho * Wo, Cout, kh * kw, Cin)
-            and B3_BLOCKED and Cout > 192 and Cin % 16 == 0 and 6 * Cout * kh * kw * Cin < (1 << 32) - 64):
+    if (_fwd_gemm_ok(Layer(x.shape, Cout, kh, kw, stride, pad, dil, groups, stem4=stem4, w4d=w.numel() == Cout * kh * kw * Cin))
+            and _b3_blocked_shape(Cout, Cin) and 6 * Cout * kh * kw * Cin < (1 << 32) - 64):
         # the bf16x3 kernel with the fused epilogue; the batch is cut so that the three blocked planes of a piece stay below 4 GB
         # (UPerNet's 3x3 2048 -> 512 on a 4 x 272 x 480 map: 6.4 GB of planes in one piece)
         per_img = 6 * H * W * Cin
