@@ -467,7 +467,9 @@ int catseg_adaptive_avgpool_bwd(const float* dy, float* dx, int lddx, int B, int
 
 /* ---- softmax ------------------------------------------------------------------------------ */
 /* F.softmax(probs.view(B,K,N), dim=2) at models/OCR.py:165, on NHWC logits [B][N][ld]:
- * per (b, k) over the N pixels, K <= 32.  Columns [K, ld) of the output are zeroed. */
+ * per (b, k) over the N pixels, K <= 32.  Columns [K, ld) of the output are zeroed.
+ * _bwd: dx (+)= y * (dy - sum_n dy y) in columns [0, K); columns [K, ld) of dx are WRITTEN ZERO, also when accumulate != 0
+ * (the pad columns of a class-logit buffer stay zero whatever was there). */
 size_t catseg_softmax_spatial_workspace(int B, int N);
 int catseg_softmax_spatial_fwd(const float* x, float* y, int B, int N, int K, int ld, void* workspace,
                                size_t workspace_bytes, catseg_stream_t stream);
@@ -480,6 +482,14 @@ int catseg_softmax_rows_bwd(const float* y, const float* dy, float* dx, long lon
                             float scale, catseg_stream_t stream);
 
 /* ---- losses ------------------------------------------------------------------------------- */
+/* The per-pixel kernels of this section and catseg_confusion_matrix stage 256 pixel rows of K | 1 floats in LDS: with S = 1024 * (K | 1)
+ * bytes, Lovasz forward and cross entropy ask for S (+ up to 1 KB static), OHEM for S + 8 KB, Lovasz backward for 2 S + 1 KB, the
+ * confusion matrix for S + 4 K^2.  That passes the 64 KB a block gets by default from K = 32 (Lovasz backward), K = 54 (confusion
+ * matrix), K = 56 (OHEM), K = 64 (Lovasz forward, cross entropy).  Every entry point accepts 1 <= K <= 64: beyond 64 KB it opts in
+ * (hipFuncSetAttribute) up to the device's opt-in maximum, which catseg_lds_limits reports (an MI355X reports 163840 bytes, by default and after opting in: every K <= 64 is served,
+ * Lovasz backward at K = 64 with 131 KB = one block per CU).  On a device whose maximum is smaller the call returns CATSEG_EINVAL with a
+ * message BEFORE launching anything: outputs and workspace are untouched. */
+int catseg_lds_limits(int* per_block, int* per_block_optin); /* bytes of LDS per block: by default / after opting in */
 /* LovaszSoftmax.forward (losses/LovaszSoftmax.py:19-61, per_image=False, classes 'present',
  * nothing ignored) fused with its autograd backward.  logits [P][K] (ld = K, compact),
  * labels int64 [P].  loss_out[0] = loss; dlogits (may be NULL) = weight * dloss/dlogits. */
@@ -494,7 +504,9 @@ int catseg_lovasz_softmax_fwd(const float* logits, const int64_t* labels, long l
                               int want_grad, void* workspace, size_t workspace_bytes, catseg_stream_t stream);
 int catseg_lovasz_softmax_bwd(const float* logits, long long P, int K, float weight, const float* upstream, float* dlogits,
                               int accumulate_dlogits, void* workspace, size_t workspace_bytes, catseg_stream_t stream);
-/* nn.CrossEntropyLoss(ignore_index) (losses/LossWrapper.py:17-24) fused with backward */
+/* nn.CrossEntropyLoss(ignore_index) (losses/LossWrapper.py:17-24) fused with backward.  A label outside [0, K) is IGNORED whether or not it
+ * equals ignore_index (torch raises on such a label; here it contributes neither to the sum nor to the count, and its gradient row is 0).
+ * No valid pixel at all: loss = NaN (0 / 0, as torch), dlogits all zero. */
 size_t catseg_ce_workspace(long long P);
 int catseg_cross_entropy(const float* logits, const int64_t* labels, long long P, int K, long long ignore_index,
                          float weight, float* loss_out, float* dlogits, void* workspace,
@@ -567,10 +579,14 @@ int catseg_resize_nearest(const float* src, int lds, float* dst, int ldd, int B,
 
 /* ---- metrics / optimiser ------------------------------------------------------------------ */
 /* t_get_confusion_matrix (utils/torch_utils.py:221-241): cm[pred*K + gt] += 1 (int32, K x K),
- * labels >= K are dropped; cm is accumulated into (zero it first for a fresh matrix). */
+ * labels outside [0, K) (>= K or negative) are dropped; pred = the FIRST maximal logit of the row (torch.argmax); cm is accumulated
+ * into (zero it first for a fresh matrix). */
 int catseg_confusion_matrix(const float* logits, const int64_t* labels, long long P, int K, int32_t* cm,
                             catseg_stream_t stream);
-/* torch.optim.Adam(lr) step over a flat parameter buffer (managers/BaseManager.py:441) */
+/* torch.optim.Adam(lr) step over a flat parameter buffer (managers/BaseManager.py:441): g' = grad_scale * g, m = beta1 m + (1 - beta1) g',
+ * v = beta2 v + (1 - beta2) g'^2, p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps).  lr, beta1, beta2, eps are the
+ * float values passed (1 - beta is formed from the float: exact), the bias corrections are formed in double.  p, g, m, v 16-byte aligned
+ * (CATSEG_EINVAL otherwise, nothing written); any n >= 1. */
 int catseg_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1,
                      float beta2, float eps, int step, float grad_scale, catseg_stream_t stream);
 /* the same step with its step-dependent scalars in DEVICE memory -- hyper = {lr, 1 - beta1^step, sqrt(1 - beta2^step), grad_scale}, the

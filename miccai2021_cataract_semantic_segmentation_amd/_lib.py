@@ -211,6 +211,7 @@ _SIGS = {
     "catseg_gconv_bwd_weight": (I, [P, P, P, P, P, P, P, SZ, P]),
     "catseg_adam_hyper": (None, [F, F, F, I, F, P]),
     "catseg_adam_step_dev": (I, [P, P, P, P, L, P, F, F, F, P]),
+    "catseg_lds_limits": (I, [P, P]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header / library mismatch

@@ -89,6 +89,53 @@ __device__ __forceinline__ bool cs_quad_walk(int cpt, long long& r, int& c, long
 static inline bool cs_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 static inline size_t cs_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// A block gets 64 KB of LDS (static + dynamic) without asking; a kernel that wants more has to opt in with hipFuncSetAttribute, up to the
+// device's opt-in maximum (hipDeviceAttributeSharedMemPerBlockOptin).  Call this for EVERY kernel of an entry point before its first launch:
+// CATSEG_OK = `kernel` may be launched with `dyn_bytes` of dynamic LDS; CATSEG_EINVAL (message set, nothing launched) = the device cannot
+// serve the request.  Requests up to CS_LDS_QUICK bytes return at once (no kernel here holds more than 8 KB of static LDS).
+constexpr size_t CS_LDS_DEFAULT = 64 * 1024, CS_LDS_QUICK = 56 * 1024;
+inline int cs_lds_limits(int* per_block, int* per_block_optin) {
+  int dev = 0, a = 0, b = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&a, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess ||
+      hipDeviceGetAttribute(&b, hipDeviceAttributeSharedMemPerBlockOptin, dev) != hipSuccess) {
+    (void)hipGetLastError();
+    catseg_set_error("cannot read the device's LDS limits");
+    return CATSEG_EHIP;
+  }
+  *per_block = a;
+  *per_block_optin = b > a ? b : a;
+  return CATSEG_OK;
+}
+template <typename Kernel>
+int cs_lds_reserve(Kernel* kernel, size_t dyn_bytes, const char* what) {
+  if (dyn_bytes <= CS_LDS_QUICK) return CATSEG_OK;
+  hipFuncAttributes fa;
+  if (hipFuncGetAttributes(&fa, (const void*)kernel) != hipSuccess) {
+    (void)hipGetLastError();
+    catseg_set_error("%s: cannot read the kernel's attributes", what);
+    return CATSEG_EINVAL;
+  }
+  const size_t total = dyn_bytes + fa.sharedSizeBytes;
+  if (total <= CS_LDS_DEFAULT) return CATSEG_OK;
+  int per_block = 0, optin = 0;
+  if (cs_lds_limits(&per_block, &optin) != CATSEG_OK) return CATSEG_EINVAL;
+  if (total > (size_t)optin) {
+    catseg_set_error("%s: needs %zu bytes of LDS per block, the device allows %d: too many classes", what, total, optin);
+    return CATSEG_EINVAL;
+  }
+  if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    catseg_set_error("%s: cannot raise the dynamic LDS limit to %zu bytes", what, dyn_bytes);
+    return CATSEG_EINVAL;
+  }
+  return CATSEG_OK;
+}
+#define CS_LDS_RESERVE(kernel, bytes, what)                        \
+  do {                                                             \
+    const int rc__ = cs_lds_reserve(kernel, bytes, what);          \
+    if (rc__ != CATSEG_OK) return rc__;                            \
+  } while (0)
+
 // 64-wide wavefront reductions (CDNA: wave = 64 lanes)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -829,6 +829,14 @@ int lovasz_run(const float* logits, const int64_t* labels, long long P, int K, f
   const long long ntiles = (P + TILE - 1) / TILE;
   const int nb = (int)((P + PIX - 1) / PIX);
   const size_t shb = (size_t)PIX * (K | 1) * 4;
+  // the staged rows pass 64 KB of LDS from K = 32 on (backward: two images): opt in, or refuse, before the first launch
+  if (g_prune) {
+    CS_LDS_RESERVE(lv_minfg_kernel, shb, "lovasz");
+    CS_LDS_RESERVE(lv_compact1_kernel, shb, "lovasz");
+  } else {
+    CS_LDS_RESERVE(lv_prep_kernel, shb, "lovasz");
+  }
+  if (dlogits) CS_LDS_RESERVE(lv_backward_kernel, 2 * shb, "lovasz backward");
   if (hipMemsetAsync(w.counts, 0, (MAXK + 4) * 4, st) != hipSuccess) { catseg_set_error("lovasz: memset failed"); return CATSEG_EHIP; }
   hipLaunchKernelGGL(label_hist_kernel, dim3(nb < 1024 ? nb : 1024), dim3(256), 0, st, labels, P, K, w.counts);
   hipLaunchKernelGGL(present_kernel, dim3(1), dim3(64), 0, st, K, w.counts);
@@ -893,6 +901,7 @@ extern "C" int catseg_lovasz_softmax_bwd(const float* logits, long long P, int K
   lv_layout(P, K, (char*)workspace, &w);
   const int nb = (int)((P + PIX - 1) / PIX);
   const size_t shb = (size_t)PIX * (K | 1) * 4;
+  CS_LDS_RESERVE(lv_backward_kernel, 2 * shb, "lovasz backward");
   // (the workspace holds what THIS process' _fwd call left: catseg_debug_set_lovasz_prune must not change between the two calls)
   hipLaunchKernelGGL(lv_backward_kernel, dim3(nb), dim3(PIX), 2 * shb, (hipStream_t)stream, logits, P, K, (const uint32_t*)w.counts, (const float*)w.dprob, weight,
                      dlogits, accumulate_dlogits, upstream, g_prune ? (const unsigned long long*)w.actmask : nullptr, (const uint32_t*)w.blkcnt, (long long)nb);
@@ -915,6 +924,8 @@ extern "C" int catseg_cross_entropy(const float* logits, const int64_t* labels, 
   const size_t shb = (size_t)PIX * (K | 1) * 4;
   float* inv = (float*)workspace;
   float* part = inv + 64;
+  CS_LDS_RESERVE(ce_fwd_kernel, shb, "ce");
+  if (dlogits) CS_LDS_RESERVE(ce_bwd_kernel, shb, "ce backward");
   hipLaunchKernelGGL(ce_fwd_kernel, dim3(nb), dim3(PIX), shb, st, logits, labels, P, K, ignore_index, part);
   hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)part, (long long)nb, weight, loss_out, inv);
   if (dlogits) hipLaunchKernelGGL(ce_bwd_kernel, dim3(nb), dim3(PIX), shb, st, logits, labels, P, K, ignore_index, weight, (const float*)inv, dlogits);
@@ -927,6 +938,7 @@ extern "C" int catseg_confusion_matrix(const float* logits, const int64_t* label
   CS_REQUIRE(P > 0 && K > 0 && K <= MAXK, "confusion: bad args");
   const int nb = (int)((P + PIX - 1) / PIX);
   const size_t shb = (size_t)PIX * (K | 1) * 4 + (size_t)K * K * 4;
+  CS_LDS_RESERVE(confusion_kernel, shb, "confusion");
   hipLaunchKernelGGL(confusion_kernel, dim3(nb), dim3(PIX), shb, (hipStream_t)stream, logits, labels, P, K, cm);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
@@ -962,4 +974,9 @@ extern "C" int catseg_adam_step_dev(float* p, const float* g, float* m, float* v
                      hyper);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
+}
+
+extern "C" int catseg_lds_limits(int* per_block, int* per_block_optin) {
+  CS_REQUIRE(per_block && per_block_optin, "lds limits: null pointer");
+  return cs_lds_limits(per_block, per_block_optin);
 }

@@ -244,6 +244,8 @@ extern "C" int catseg_ohem_cross_entropy(const float* logits, const int64_t* lab
   carve(P, workspace, &w);
   const long long nb = (P + PIX - 1) / PIX;
   const size_t shb = (size_t)PIX * (K | 1) * 4;
+  CS_LDS_RESERVE(ohem_prep_kernel, shb, "ohem");
+  if (dlogits) CS_LDS_RESERVE(ohem_bwd_kernel, shb, "ohem backward");
   if (hipMemsetAsync(w.hist, 0, NBIN * 4 + 64, st) != hipSuccess) { catseg_set_error("ohem: memset failed"); return CATSEG_EHIP; }
   hipLaunchKernelGGL(ohem_prep_kernel, dim3(nb), dim3(PIX), shb, st, logits, labels, P, K, ignore_index, w.keys, w.loss, w.hist);
   const int hb = (int)(nb < 2048 ? nb : 2048);

@@ -1,0 +1,673 @@
+"""The loss, metric, optimiser and pointwise kernels at the shapes where they leave their simplest path: stride loops behind a capped
+grid, multi-chunk merges, tails, padded row pitches, labels outside the class range, more classes than the datasets have.
+
+Every comparison is against a float64 CPU reference of the same operation written here (never another kernel of the library, never a
+recorded value).  The bound of a floating-point comparison is measured, not chosen: the same reference lines run in float32 on the CPU give
+the yardstick `e32 = max |ref32 - ref64|`, and the kernel may be off by at most 4 x e32, with a floor of 4 ulp (2^-23) of the reference's
+scale where the float32 CPU result happens to be exact -- both scaled as close() of test_kernels_gpu.py scales an error, by max |ref64|.
+Integer results, pad columns, round trips and the device-scalar Adam are exact equality."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+EPS32 = 2.0 ** -23
+WORST = {}      # kernel -> (worst ratio of the kernel's error to the yardstick, case): printed by every check (run with -s to collect)
+
+
+@pytest.fixture(scope="module")
+def ops():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from miccai2021_cataract_semantic_segmentation_amd import ops as o
+    return o
+
+
+def gen(*seed):
+    return torch.Generator().manual_seed(sum((i + 1) * int(s) for i, s in enumerate(seed)) % (2 ** 31))
+
+
+def within(kernel, case, got, ref64, ref32):
+    """max |got - ref64| <= max(4 max |ref32 - ref64|, 4 ulp of max |ref64|)"""
+    got, ref64, ref32 = got.detach().cpu().double(), ref64.detach().double(), ref32.detach().double()
+    assert got.shape == ref64.shape == ref32.shape, (got.shape, ref64.shape, ref32.shape)
+    assert torch.isfinite(ref64).all() and torch.isfinite(ref32).all(), "%s %s: the reference is not finite" % (kernel, case)
+    assert torch.isfinite(got).all(), "%s %s: the kernel wrote inf / nan" % (kernel, case)
+    scale = ref64.abs().max().item() + 1e-12
+    err, e32 = (got - ref64).abs().max().item(), (ref32 - ref64).abs().max().item()
+    yard = max(e32, EPS32 * scale)
+    ratio = err / yard
+    if ratio > WORST.get(kernel, (-1.0, None))[0]:
+        WORST[kernel] = (ratio, case)
+    print("RATIO %-22s %-40s err %.3e  fp32-cpu %.3e  scale %.3e  ratio %.3f  (worst so far %.3f)" % (kernel, case, err, e32, scale, ratio, WORST[kernel][0]))
+    assert err <= 4 * yard, "%s %s: max abs err %g > 4 x yardstick %g (fp32 CPU err %g, ref scale %g)" % (kernel, case, err, yard, e32, scale)
+
+
+# ---------------------------------------------------------------------------------------------- 1. softmax over pixels
+SP_CHUNK = 512      # pixels per block in csrc/pointwise.hip: N > 512 = several chunks merged by (max, sum-exp) rescaling
+SPATIAL = [
+    # N, K, ld, B
+    (1, 1, 4, 1), (7, 8, 8, 3), (8, 25, 32, 1), (9, 32, 32, 1), (511, 8, 40, 1), (512, 25, 28, 3), (513, 32, 40, 1), (519, 1, 32, 1),
+    (4096, 25, 40, 3), (32640, 25, 32, 1), (32640, 32, 40, 3),
+]
+
+
+def spatial_id(c):
+    N, K, ld, B = c
+    nch = (N + SP_CHUNK - 1) // SP_CHUNK
+    tags = ["N%d" % N, "K%d" % K, "ld%d" % ld, "B%d" % B, "chunks%d" % nch]
+    if N % SP_CHUNK and N % SP_CHUNK < 8:
+        tags.append("emptylanes")
+    if ld > 32:
+        tags.append("2ndcolpass")
+    return "-".join(tags)
+
+
+def spatial_inputs(N, K, ld, B):
+    g = gen(N, K, ld, B)
+    nch = (N + SP_CHUNK - 1) // SP_CHUNK
+    x = 3 * torch.randn(B, N, K, generator=g)
+    # chunk maxima tens apart, per chunk and per column: every expf(m - mn) of the merge is far from 1
+    off = (torch.randint(0, 3, (B, nch, K), generator=g) - 1).float() * 60
+    x = x + off.repeat_interleave(SP_CHUNK, 1)[:, :N]
+    dy = torch.randn(B, N, K, generator=g)
+    base = torch.randn(B, N, ld, generator=g)
+    return x, dy, base
+
+
+def spatial_ref(x, dy, dt):
+    xr = x.to(dt).requires_grad_()
+    y = torch.softmax(xr, dim=1)
+    (y * dy.to(dt)).sum().backward()
+    return y.detach(), xr.grad
+
+
+@pytest.mark.parametrize("case", SPATIAL, ids=spatial_id)
+def test_softmax_over_pixels(ops, case):
+    N, K, ld, B = case
+    cid = spatial_id(case)
+    x, dy, base = spatial_inputs(*case)
+    y64, dx64 = spatial_ref(x, dy, torch.float64)
+    y32, dx32 = spatial_ref(x, dy, torch.float32)
+    xd = torch.full((B, N, ld), 123.0, device="cuda")          # the pad columns of the input are not part of the operation
+    xd[..., :K] = x.cuda()
+    yd = ops.softmax_spatial_fwd(xd, K)
+    within("softmax_spatial_fwd", cid, yd[..., :K], y64, y32)
+    assert float(yd[..., K:].abs().sum()) == 0.0 if ld > K else True, "pad columns of y are not zero"
+    # every column sums to 1 over the pixels: s, 1 / s and the product round once each, expf is good to 2 ulp -> 4 ulp, x 4 as everywhere
+    dev_k = (yd[..., :K].cpu().double().sum(1) - 1).abs().max().item()
+    dev_32 = (y32.double().sum(1) - 1).abs().max().item()
+    assert dev_k <= max(4 * dev_32, 16 * EPS32), "%s: column sums off 1 by %g (fp32 CPU %g)" % (cid, dev_k, dev_32)
+    assert torch.equal(ops.softmax_spatial_fwd(xd, K), yd), "two forward calls differ"
+    gyd = torch.full((B, N, ld), 123.0, device="cuda")
+    gyd[..., :K] = dy.cuda()
+    dx = ops.softmax_spatial_bwd(yd, gyd, torch.full_like(xd, 9.0), K)
+    within("softmax_spatial_bwd", cid, dx[..., :K], dx64, dx32)
+    assert float(dx[..., K:].abs().sum()) == 0.0 if ld > K else True, "pad columns of dx are not zero"
+    assert torch.equal(ops.softmax_spatial_bwd(yd, gyd, torch.full_like(xd, -3.0), K), dx), "two backward calls differ"
+    # accumulate: columns < K are added to, the pad columns are written zero (include/catseg.h)
+    acc = ops.softmax_spatial_bwd(yd, gyd, base.cuda(), K, accumulate=True)
+    within("softmax_spatial_bwd", cid + "-acc", acc[..., :K], base[..., :K].double() + dx64, base[..., :K] + dx32)
+    assert float(acc[..., K:].abs().sum()) == 0.0 if ld > K else True, "accumulate: pad columns of dx are not zero"
+
+
+# ---------------------------------------------------------------------------------------------- 2. softmax over rows
+ROWS_GRID = 16384 * 4      # rows one sweep of the capped grid covers (16384 blocks x 4 waves): beyond it the stride loop runs
+SC = 256 ** -0.5
+ROWS = [
+    # rows, K, ld, scale, magnitude of x
+    (1, 1, 4, 1.0, 3.0), (3, 25, 25, SC, 3.0), (4, 25, 32, 50.0, 3.0), (65535, 63, 64, SC, 3.0), (65536, 64, 64, 1.0, 3.0),
+    (65537, 25, 32, SC, 3.0), (261120, 25, 32, SC, 3.0), (200003, 64, 64, 50.0, 3.0), (200003, 1, 4, 50.0, 3.0),
+    (261120, 63, 64, 1.0, 1e4), (65537, 25, 25, SC, 1e4),
+]
+
+
+def rows_id(c):
+    rows, K, ld, scale, mag = c
+    tags = ["rows%d" % rows, "K%d" % K, "ld%d" % ld, "scale%g" % scale]
+    if rows > ROWS_GRID:
+        tags.append("stride%d" % ((rows + ROWS_GRID - 1) // ROWS_GRID))
+    if mag > 100:
+        tags.append("span1e4")
+    return "-".join(tags)
+
+
+def rows_ref(x, dy, scale, dt):
+    xr = x.to(dt).requires_grad_()
+    y = torch.softmax(scale * xr, dim=-1)
+    (y * dy.to(dt)).sum().backward()
+    return y.detach(), xr.grad
+
+
+@pytest.mark.parametrize("case", ROWS, ids=rows_id)
+def test_softmax_over_rows(ops, case):
+    rows, K, ld, scale, mag = case
+    cid = rows_id(case)
+    g = gen(rows, K, ld, int(scale * 16), int(mag))
+    x = mag * torch.randn(rows, K, generator=g) if mag < 100 else (torch.rand(rows, K, generator=g) * 2 - 1) * mag
+    dy = torch.randn(rows, K, generator=g)
+    y64, dx64 = rows_ref(x, dy, scale, torch.float64)
+    y32, dx32 = rows_ref(x, dy, scale, torch.float32)
+    xd = torch.full((rows, ld), 123.0, device="cuda")
+    xd[:, :K] = x.cuda()
+    yd = ops.softmax_rows_fwd(xd, K, scale)
+    within("softmax_rows_fwd", cid, yd[:, :K], y64, y32)
+    gyd = torch.full((rows, ld), 123.0, device="cuda")
+    gyd[:, :K] = dy.cuda()
+    dx = ops.softmax_rows_bwd(yd, gyd, K, scale)
+    within("softmax_rows_bwd", cid, dx[:, :K], dx64, dx32)
+    if ld > K:
+        assert float(yd[:, K:].abs().sum()) == 0.0 and float(dx[:, K:].abs().sum()) == 0.0, "pad columns are not zero"
+    assert torch.equal(ops.softmax_rows_fwd(xd, K, scale), yd) and torch.equal(ops.softmax_rows_bwd(yd, gyd, K, scale), dx)
+
+
+# ---------------------------------------------------------------------------------------------- 3. cross entropy / 4. confusion matrix
+FULL = 2 * 544 * 960     # two frames at full resolution: 4080 blocks of 256 pixels, more partials than the finaliser has threads
+CE = [
+    # P, K, ignore_index ("K" = the class count), label mix, weight, logit magnitude
+    (1, 1, "K", "valid", 1.0, 3.0), (255, 2, 255, "ignored30", 0.4, 3.0), (256, 17, "K", "valid", 1.0, 3.0),
+    (257, 24, -1, "outside", 1.0, 3.0), (65537, 25, "K", "ignored30", 1.0, 3.0), (FULL, 25, "K", "ignored30", 0.4, 3.0),
+    (FULL, 17, 255, "outside", 1.0, 1e4), (65537, 64, "K", "ignored30", 1.0, 3.0), (257, 25, "K", "allignored", 1.0, 3.0),
+    (65537, 2, -1, "onevalid", 1.0, 3.0), (256, 1, 255, "ignored30", 0.4, 3.0), (255, 64, -1, "valid", 0.4, 1e4),
+    (257, 24, 255, "outside", 0.4, 1e4), (65537, 17, "K", "onevalid", 0.4, 3.0),
+]
+
+
+def ce_id(c):
+    P, K, ign, mix, weight, mag = c
+    tags = ["P%d" % P, "K%d" % K, "ign%s" % ign, mix, "w%g" % weight]
+    if P % 256:
+        tags.append("tail%d" % (P % 256))
+    if P > 65536:
+        tags.append("partials%d" % ((P + 255) // 256))
+    if mag > 100:
+        tags.append("mag1e4")
+    return "-".join(tags)
+
+
+def make_labels(P, K, ign, mix, g):
+    """labels for P pixels: valid classes, `ign` on about 30 %, a few values outside [0, K) that are NOT `ign`, ..."""
+    lab = torch.randint(0, K, (P,), generator=g)
+    if mix in ("ignored30", "outside"):
+        lab[torch.rand(P, generator=g) < 0.3] = ign
+    if mix == "outside":
+        stray = torch.tensor([v for v in (K, K + 3, 255, 1000, -1, -7, -100) if v != ign])
+        hit = torch.rand(P, generator=g) < 0.05
+        hit[min(3, P - 1)] = True
+        lab[hit] = stray[torch.randint(0, len(stray), (int(hit.sum()),), generator=g)]
+    if mix in ("allignored", "onevalid"):
+        keep = int(lab[P // 2])
+        lab[:] = ign
+        if mix == "onevalid":
+            lab[P // 2] = keep
+    return lab
+
+
+def ce_ref(x, lab, K, weight, dt):
+    """F.cross_entropy with every label outside [0, K) mapped to ignore_index first (torch itself raises on such a label)"""
+    t = lab.clone()
+    t[(lab < 0) | (lab >= K)] = -100
+    xr = x.to(dt).requires_grad_()
+    loss = F.cross_entropy(xr, t, ignore_index=-100) * weight
+    loss.backward()
+    return loss.detach().reshape(1), xr.grad
+
+
+@pytest.mark.parametrize("case", CE, ids=ce_id)
+def test_cross_entropy(ops, case):
+    P, K, ign, mix, weight, mag = case
+    cid = ce_id(case)
+    ign = K if ign == "K" else ign
+    g = gen(P, K, ign + 2, len(mix), int(weight * 10), int(mag))
+    x = mag * torch.randn(P, K, generator=g)
+    lab = make_labels(P, K, ign, mix, g)
+    valid = (lab >= 0) & (lab < K) & (lab != ign)
+    xd, dl = x.cuda(), torch.full((P, K), 7.0, device="cuda")
+    loss = ops.cross_entropy(xd, lab.cuda(), ign, weight, dl)
+    dl = dl.cpu()
+    assert float(dl[~valid].abs().sum()) == 0.0 if (~valid).any() else True, "gradient rows of ignored pixels are not exactly zero"
+    if mix == "allignored":
+        assert torch.isnan(loss).all() and float(dl.abs().sum()) == 0.0          # 0 / 0 as torch; no NaN in the gradient
+        return
+    l64, g64 = ce_ref(x, lab, K, weight, torch.float64)
+    l32, g32 = ce_ref(x, lab, K, weight, torch.float32)
+    within("cross_entropy loss", cid, loss, l64, l32)
+    within("cross_entropy grad", cid, dl, g64, g32)
+    # (p - onehot) * w sums to zero over the classes: K entries, each p good to 4 ulp of 1, times w = weight / count
+    w = weight / int(valid.sum())
+    assert dl[valid].double().sum(1).abs().max().item() <= 4 * EPS32 * (K + 4) * w
+
+
+CM = [(1, 1), (255, 2), (256, 17), (257, 24), (65537, 25), (FULL, 25), (FULL, 8), (65537, 64), (257, 64), (65537, 1)]
+
+
+def cm_id(c):
+    P, K = c
+    return "P%d-K%d" % (P, K) + ("-tail%d" % (P % 256) if P % 256 else "") + ("-blocks%d" % ((P + 255) // 256) if P > 65536 else "")
+
+
+def cm_ref(x, lab, K):
+    """utils.t_get_confusion_matrix of the reference project: pred = logits.argmax over the classes -- of several maximal logits the
+    FIRST (torch.argmax and numpy.argmax agree on that) --, cm[pred][label] += 1, labels outside [0, K) dropped"""
+    pred, t = np.argmax(x.numpy(), axis=1), lab.numpy()
+    keep = (t >= 0) & (t < K)
+    return np.bincount(K * pred[keep] + t[keep], minlength=K * K).reshape(K, K), int(keep.sum())
+
+
+@pytest.mark.parametrize("case", CM, ids=cm_id)
+def test_confusion_matrix(ops, case):
+    P, K = case
+    g = gen(P, K, 77)
+    x = (3 * torch.randn(P, K, generator=g)).mul(4).round().div(4)     # a coarse grid: ties happen by themselves ...
+    if K > 1:                                                           # ... and one row in four has its maximum duplicated exactly
+        rowsel = torch.nonzero(torch.rand(P, generator=g) < 0.25).reshape(-1)
+        col = torch.randint(0, K, (len(rowsel),), generator=g)
+        x[rowsel, col] = x[rowsel].max(1).values
+        assert P < 64 or int((x == x.max(1, keepdim=True).values).sum(1).gt(1).sum()) >= len(rowsel) // 2
+    lab = torch.randint(0, K + 1, (P,), generator=g)                    # K itself included
+    r = torch.rand(P, generator=g)
+    lab[r < 0.05] = 255
+    lab[(r >= 0.05) & (r < 0.1)] = -1
+    ref, nvalid = cm_ref(x, lab, K)
+    xd, ld = x.cuda(), lab.cuda()
+    cm = ops.confusion_matrix(xd, ld)
+    assert np.array_equal(cm.cpu().numpy(), ref) and int(cm.sum()) == nvalid
+    # accumulation: two halves into one matrix, and into a pre-filled one
+    h = max(1, P // 2 + 3) if P > 1 else 1
+    ref1 = cm_ref(x[:h], lab[:h], K)[0]
+    cm2 = ops.confusion_matrix(xd[:h].contiguous(), ld[:h].contiguous())
+    if h < P:
+        ref1 = ref1 + cm_ref(x[h:], lab[h:], K)[0]
+        ops.confusion_matrix(xd[h:].contiguous(), ld[h:].contiguous(), cm=cm2)
+    assert np.array_equal(cm2.cpu().numpy(), ref1) and np.array_equal(ref1, ref)
+    pre = torch.arange(K * K, dtype=torch.int32).reshape(K, K) * 3 + 1
+    cm3 = ops.confusion_matrix(xd, ld, cm=pre.cuda())
+    assert np.array_equal(cm3.cpu().numpy(), ref + pre.numpy())
+
+
+# ---------------------------------------------------------------------------------------------- 5. Adam
+ADAM_GRID = 8192 * 256 * 4       # elements one sweep of the capped grid covers
+LR, B1, B2, EPS = (float(np.float32(v)) for v in (1e-3, 0.9, 0.999, 1e-8))   # the C ABI takes float: these are the values the kernel sees
+
+
+def adam_ref(p, g, m, v, step, gs):
+    """torch.optim.Adam's update (no weight decay, no amsgrad) in the dtype of the tensors; bias corrections formed in double"""
+    g = g * gs
+    m = m * B1 + g * (1 - B1)
+    v = v * B2 + g * g * (1 - B2)
+    bc1, bc2 = 1 - B1 ** step, 1 - B2 ** step
+    p = p - (LR / bc1) * (m / (v.sqrt() / bc2 ** 0.5 + EPS))
+    return p, m, v
+
+
+def adam_grad(n, g):
+    gr = torch.randn(n, generator=g)
+    r = torch.rand(n, generator=g)
+    gr[r < 0.1] = 0.0
+    gr[(r >= 0.1) & (r < 0.2)] = 1e-25        # squares to a denormal / zero in float32
+    return gr
+
+
+def adam_id(c):
+    n, steps, gs = c
+    tags = ["n%d" % n, "steps%d" % steps, "gs%g" % gs]
+    if n > ADAM_GRID:
+        tags.append("strideloop")
+    if n % 4:
+        tags.append("tail%d" % (n % 4))
+    return "-".join(tags)
+
+
+ADAM = [(1, 10, 1.0), (3, 10, 1 / 128), (4, 10, 1.0), (5, 10, 1 / 128), (1003, 10, 1.0), (8388607, 2, 1 / 128), (8388608, 2, 1.0),
+        (8388609, 10, 1 / 128), (20000003, 2, 1.0)]
+
+
+def adam_dev_twin(ops, pd, gd, md, vd, step, gs):
+    """the same update through catseg_adam_step_dev, its four scalars from catseg_adam_hyper"""
+    from miccai2021_cataract_semantic_segmentation_amd._lib import lib
+    h = (ctypes.c_float * 4)()
+    lib.catseg_adam_hyper(LR, B1, B2, step, gs, h)
+    hyper = torch.tensor(list(h), dtype=torch.float32).cuda()
+    p2, m2, v2 = pd.clone(), md.clone(), vd.clone()
+    ops.adam_step_dev(p2, gd, m2, v2, hyper, B1, B2, EPS)
+    return p2, m2, v2
+
+
+@pytest.mark.parametrize("case", ADAM, ids=adam_id)
+def test_adam_from_zero_moments(ops, case):
+    n, steps, gs = case
+    cid = adam_id(case)
+    g = gen(n, steps)
+    p = torch.randn(n, generator=g)
+    s64 = (p.double(), torch.zeros(n, dtype=torch.float64), torch.zeros(n, dtype=torch.float64))
+    s32 = (p.clone(), torch.zeros(n), torch.zeros(n))
+    pd, md, vd = p.cuda(), torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda")
+    for step in range(1, steps + 1):
+        gr = adam_grad(n, g)
+        gd = gr.cuda()
+        s64 = adam_ref(s64[0], gr.double(), s64[1], s64[2], step, gs)
+        s32 = adam_ref(s32[0], gr, s32[1], s32[2], step, gs)
+        twin = adam_dev_twin(ops, pd, gd, md, vd, step, gs) if step <= 2 else None
+        ops.adam_step(pd, gd, md, vd, LR, step, B1, B2, EPS, gs)
+        if twin is not None:
+            assert all(torch.equal(a, b) for a, b in zip(twin, (pd, md, vd))), "adam_step_dev is not bit-identical to adam_step"
+        if step in (1, 2, 10):
+            for name, got, r64, r32 in zip("pmv", (pd, md, vd), s64, s32):
+                within("adam " + name, "%s-at%d" % (cid, step), got, r64, r32)
+        del gd, twin
+    del pd, md, vd
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("n,step,gs", [(1003, 1000, 1.0), (8388609, 100000, 1 / 128), (5, 100000, 1.0), (1003, 100000, 1 / 128)],
+                         ids=lambda v: "%g" % v)
+def test_adam_late_step(ops, n, step, gs):
+    """one update far into training (bias corrections near 1) from random moments, v >= 0"""
+    g = gen(n, step)
+    p, m, v, gr = torch.randn(n, generator=g), 0.1 * torch.randn(n, generator=g), 1e-2 * torch.rand(n, generator=g), adam_grad(n, g)
+    v[::7] = 0.0
+    r64 = adam_ref(p.double(), gr.double(), m.double(), v.double(), step, gs)
+    r32 = adam_ref(p, gr, m, v, step, gs)
+    pd, gd, md, vd = p.cuda(), gr.cuda(), m.cuda(), v.cuda()
+    twin = adam_dev_twin(ops, pd, gd, md, vd, step, gs)
+    ops.adam_step(pd, gd, md, vd, LR, step, B1, B2, EPS, gs)
+    assert all(torch.equal(a, b) for a, b in zip(twin, (pd, md, vd))), "adam_step_dev is not bit-identical to adam_step"
+    for name, got, a, b in zip("pmv", (pd, md, vd), r64, r32):
+        within("adam " + name, "n%d-step%d-gs%g" % (n, step, gs), got, a, b)
+
+
+@pytest.mark.parametrize("which", [0, 1, 2, 3], ids=["p", "g", "m", "v"])
+def test_adam_rejects_a_misaligned_buffer(ops, which):
+    from miccai2021_cataract_semantic_segmentation_amd._lib import CatsegError
+    n = 1003
+    g = gen(n, which)
+    bufs = [torch.randn(n + 1, generator=g).cuda() for _ in range(4)]
+    before = [b.clone() for b in bufs]
+    args = [b[1:] if i == which else b[:n] for i, b in enumerate(bufs)]       # a slice starting at element 1: 4 bytes off
+    assert args[which].data_ptr() % 16 == 4
+    with pytest.raises(CatsegError):
+        ops.adam_step(args[0], args[1], args[2], args[3], LR, 1, B1, B2, EPS, 1.0)
+    hyper = torch.tensor([LR, 0.1, 0.03, 1.0]).cuda()
+    with pytest.raises(CatsegError):
+        ops.adam_step_dev(args[0], args[1], args[2], args[3], hyper, B1, B2, EPS)
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(bufs, before)), "a rejected call wrote to its buffers"
+
+
+# ---------------------------------------------------------------------------------------------- 6. max-pool 3 x 3 / 2
+POOL_GRID = 16384 * 256       # channel quads one sweep of the capped grid covers
+POOL = [
+    # B, H, W, C, x is a channel slice of a buffer 8 wider, input kind
+    (2, 1, 1, 4, False, "relu"), (2, 1, 9, 8, True, "relu"), (1, 2, 2, 64, False, "const"), (3, 2, 7, 4, True, "neginf"),
+    (2, 13, 18, 8, False, "relu"), (2, 31, 32, 64, True, "relu"), (1, 272, 480, 8, False, "randn"), (2, 2, 7, 8, False, "const"),
+    (1, 31, 32, 4, True, "neginf"), (9, 272, 480, 64, False, "relu"),
+]
+
+
+def pool_id(c):
+    B, H, W, C, sl, kind = c
+    tags = ["B%d" % B, "%dx%d" % (H, W), "C%d" % C, "slice" if sl else "dense", kind]
+    if B * ((H + 1) // 2) * ((W + 1) // 2) * C // 4 > POOL_GRID:
+        tags.append("strideloop")
+    return "-".join(tags)
+
+
+def pool_bwd_ref(x, dy, dt):
+    """x, dy: NHWC; F.max_pool2d + autograd on the channels-last view (no copy)"""
+    xr = x.to(dt).permute(0, 3, 1, 2).requires_grad_()
+    y = F.max_pool2d(xr, 3, 2, 1)
+    y.backward(dy.to(dt).permute(0, 3, 1, 2))
+    return xr.grad.permute(0, 2, 3, 1)
+
+
+@pytest.mark.parametrize("case", POOL, ids=pool_id)
+def test_maxpool(ops, case):
+    B, H, W, C, sl, kind = case
+    cid = pool_id(case)
+    g = gen(B, H, W, C, len(kind))
+    x = torch.randn(B, H, W, C, generator=g)
+    if kind == "relu":
+        x = x.relu()                                     # about half the entries tie at 0
+    elif kind == "const":
+        x = torch.full_like(x, 1.5)
+    elif kind == "neginf":
+        x[torch.rand(x.shape, generator=g) < 0.6] = float("-inf")      # whole windows of -inf among them
+    Ho, Wo = (H + 1) // 2, (W + 1) // 2
+    dy = torch.randn(B, Ho, Wo, C, generator=g)
+    yref = F.max_pool2d(x.permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1)
+    if sl:
+        buf = torch.full((B, H, W, C + 8), 1e30, device="cuda")
+        buf[..., :C] = x.cuda()
+        xd = buf[..., :C]
+        assert ops.ld_of(xd) == C + 8
+    else:
+        xd = x.cuda()
+    yd, idx = ops.maxpool_fwd(xd)
+    assert torch.equal(yd.cpu(), yref), "%s: forward differs from F.max_pool2d" % cid
+    del xd
+    dxd = ops.maxpool_bwd(dy.cuda(), idx, (B, H, W, C))
+    del yd, idx
+    d64 = pool_bwd_ref(x, dy, torch.float64)
+    d32 = pool_bwd_ref(x, dy, torch.float32)
+    within("maxpool_bwd", cid, dxd, d64, d32)
+    del dxd
+    ops.release_workspaces()
+    torch.cuda.empty_cache()
+
+
+# ---------------------------------------------------------------------------------------------- 7. helpers without a test of their own
+@pytest.mark.parametrize("rows,C", [(1, 4), (37, 8), (1000, 64), (70001, 256)], ids=lambda v: "%d" % v)
+def test_relu_bwd(ops, rows, C):
+    g = gen(rows, C)
+    z = torch.randn(rows, C, generator=g)
+    r = torch.rand(rows, C, generator=g)
+    z[r < 0.2] = 0.0
+    z[(r >= 0.2) & (r < 0.4)] = -0.0
+    dz = torch.randn(rows, C, generator=g)
+    zb = torch.full((rows, C + 8), 5.0, device="cuda")        # three different row pitches: C + 8, C + 4, C
+    db = torch.full((rows, C + 4), 5.0, device="cuda")
+    zb[:, :C], db[:, :C] = z.cuda(), dz.cuda()
+    gk = ops.relu_bwd(db[:, :C], zb[:, :C])
+    assert (ops.ld_of(zb[:, :C]), ops.ld_of(db[:, :C])) == (C + 8, C + 4) or rows == 1
+    ref = torch.where(z > 0, dz, torch.zeros_like(dz))
+    assert torch.equal(gk.cpu(), ref)
+
+
+@pytest.mark.parametrize("n", [1, 3, 4, 7, 4099, 5000001])
+def test_scale_by_device_scalar(ops, n):
+    g = gen(n)
+    x = torch.randn(n, generator=g)
+    s = torch.tensor([0.3712], dtype=torch.float32)
+    xd = x.cuda()
+    ops.scale_by_device_scalar(xd, s.cuda())
+    within("scale_by_device_scalar", "n%d" % n, xd, x.double() * s.double(), x * s)
+
+
+def fold_ref(w, b, gamma, beta, rm, rv, eps, dt):
+    w, gamma, beta, rm, rv = (t.to(dt) for t in (w, gamma, beta, rm, rv))
+    sc = gamma / torch.sqrt(rv + eps)
+    bias = beta + ((b.to(dt) if b is not None else 0) - rm) * sc
+    return w * sc[:, None], bias
+
+
+@pytest.mark.parametrize("bias", [True, False], ids=["bias", "nobias"])
+@pytest.mark.parametrize("per_out", [1, 9 * 48, 720])
+@pytest.mark.parametrize("O", [1, 25, 512])
+def test_fold_bn(ops, O, per_out, bias):
+    g = gen(O, per_out, bias)
+    w = torch.randn(O, per_out, generator=g)
+    b = torch.randn(O, generator=g) if bias else None
+    gamma, beta, rm = torch.randn(O, generator=g), torch.randn(O, generator=g), torch.randn(O, generator=g)
+    rv = torch.rand(O, generator=g)
+    rv[::3] = 0.0                                     # a channel that never varied
+    eps = float(np.float32(1e-5))
+    wf, bf = ops.fold_bn(w.cuda(), None if b is None else b.cuda(), gamma.cuda(), beta.cuda(), rm.cuda(), rv.cuda(), eps, O, per_out)
+    w64, b64 = fold_ref(w, b, gamma, beta, rm, rv, eps, torch.float64)
+    w32, b32 = fold_ref(w, b, gamma, beta, rm, rv, eps, torch.float32)
+    cid = "O%d-per%d-%s" % (O, per_out, "bias" if bias else "nobias")
+    within("fold_bn weight", cid, wf.reshape(O, per_out), w64, w32)
+    within("fold_bn bias", cid, bf, b64, b32)
+
+
+@pytest.mark.parametrize("cin,cpad", [(3, 4), (25, 32), (48, 48)])
+def test_weight_pad_round_trip(ops, cin, cpad):
+    O, taps = 7, 9
+    w = torch.randn(O, taps, cin, generator=gen(cin, cpad))
+    pk = ops.weight_pad_cin(w.cuda(), O, taps, cin, cpad)
+    assert torch.equal(pk[..., :cin].cpu(), w)
+    assert cpad == cin or float(pk[..., cin:].abs().sum()) == 0.0
+    back = ops.weight_unpad_cin(pk, torch.full((O, taps, cin), 9.0, device="cuda"), O, taps, cin, cpad)
+    assert torch.equal(back.cpu(), w)
+
+
+@pytest.mark.parametrize("O", [1, 64])
+def test_stem_pack_round_trip(ops, O):
+    w = torch.randn(O, 7, 7, 3, generator=gen(O, 5))           # OHWI, as a channels-last [O, 3, 7, 7] weight lies in memory
+    pk = ops.stem_pack_weight(w.cuda(), O)
+    assert pk.shape == (O, 7, 8, 4)
+    assert torch.equal(pk[:, :, :7, :3].cpu(), w)
+    assert float(pk[:, :, 7, :].abs().sum()) == 0.0 and float(pk[..., 3].abs().sum()) == 0.0
+    dw = ops.stem_unpack_grad(pk, torch.full((O, 7, 7, 3), 9.0, device="cuda"), O)
+    assert torch.equal(dw.cpu(), w)
+
+
+@pytest.mark.parametrize("B,H,W,C,sl", [(1, 1, 1, 4, False), (2, 5, 7, 8, False), (2, 5, 7, 8, True), (3, 68, 120, 256, False),
+                                        (3, 68, 120, 256, True)], ids=lambda v: "%d" % v)
+def test_global_avgpool_bwd_overwrites(ops, B, H, W, C, sl):
+    dy = torch.randn(B, 1, 1, C, generator=gen(B, H, W, C))
+    wide = C + 8 if sl else C
+    buf = torch.full((B, H, W, wide), float("nan"), device="cuda")           # poisoned: accumulate=False must not read it
+    dx = buf[..., :C] if sl else buf
+    ops.global_avgpool_bwd(dy.cuda(), dx, False)
+    hw = H * W
+    within("global_avgpool_bwd", "B%d-%dx%d-C%d-%s" % (B, H, W, C, "slice" if sl else "dense"), dx,
+           (dy.double() / hw).expand(B, H, W, C), (dy / hw).expand(B, H, W, C))
+    if sl:
+        assert torch.isnan(buf[..., C:]).all(), "wrote outside its channel slice"
+
+
+# ---------------------------------------------------------------------------------------------- 8. more classes than 25: the LDS request
+def lds_request(entry, K):
+    """bytes of LDS per block (dynamic + static) of the hungriest kernel behind an entry point, from csrc/lovasz.hip and csrc/ohem.hip:
+    256 pixel rows of K | 1 floats, twice for the Lovasz backward, + K x K counters for the confusion matrix; static: the per-wave class
+    counts (4 x 64 words), the 8 wave partials of cross entropy, the 2048-bin histogram of OHEM"""
+    S = 256 * (K | 1) * 4
+    return {"lovasz_fwd": S + 1024, "lovasz_bwd": 2 * S + 1024, "cross_entropy": S + 32, "confusion_matrix": S + 4 * K * K,
+            "ohem": S + 8192}[entry]
+
+
+def lds_limits():
+    from miccai2021_cataract_semantic_segmentation_amd._lib import lib, check
+    a, b = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib.catseg_lds_limits(ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
+
+
+def serves(entry, K):
+    """the prediction: a request within the opt-in maximum is served, a larger one is refused before anything is launched"""
+    per_block, optin = lds_limits()
+    need = lds_request(entry, K)
+    print("LDS %-17s K %2d: %6d bytes; per block %d, opt-in %d -> %s" % (entry, K, need, per_block, optin,
+                                                                         "served" if need <= optin else "refused"))
+    return need <= optin
+
+
+def refused(call, outputs):
+    from miccai2021_cataract_semantic_segmentation_amd._lib import CatsegError
+    before = [o.clone() for o in outputs]
+    with pytest.raises(CatsegError, match="LDS"):
+        call()
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(outputs, before)), "a refused call wrote to its outputs"
+
+
+BIGK = [31, 32, 33, 48, 64]
+P8 = 2500
+
+
+def bigk_inputs(K, tag):
+    g = gen(K, tag)
+    x = 3 * torch.randn(P8, K, generator=g)
+    lab = torch.randint(0, K, (P8,), generator=g)
+    lab[torch.rand(P8, generator=g) < 0.1] = K
+    return x, lab
+
+
+def test_lds_limits_are_reported(ops):
+    per_block, optin = lds_limits()
+    assert 65536 <= per_block <= optin
+
+
+@pytest.mark.parametrize("K", BIGK)
+def test_lovasz_beyond_25_classes(ops, K):
+    from oracle import losses as OL
+    x, lab = bigk_inputs(K, 1)
+
+    def ref(dt):
+        xr = x.to(dt).requires_grad_()
+        loss = OL.lovasz_softmax(xr.t().reshape(1, K, P8, 1), lab.reshape(1, P8, 1))
+        loss.backward()
+        return loss.detach().reshape(1), xr.grad
+    xd, ld = x.cuda(), lab.cuda()
+    loss_out, dl = torch.full((1,), 7.0, device="cuda"), torch.full((P8, K), 7.0, device="cuda")
+    if not serves("lovasz_fwd", K):
+        return refused(lambda: ops.lovasz_softmax(xd, ld, 1.0, None, loss_out=loss_out), [loss_out])
+    (l64, g64), (l32, g32) = ref(torch.float64), ref(torch.float32)
+    within("lovasz loss K>25", "K%d" % K, ops.lovasz_softmax(xd, ld, 1.0, None, loss_out=loss_out), l64, l32)
+    if not serves("lovasz_bwd", K):
+        return refused(lambda: ops.lovasz_softmax(xd, ld, 1.0, dl, loss_out=loss_out), [loss_out, dl])
+    within("lovasz loss K>25", "K%d-withgrad" % K, ops.lovasz_softmax(xd, ld, 1.0, dl, loss_out=loss_out), l64, l32)
+    within("lovasz grad K>25", "K%d" % K, dl, g64, g32)
+    # the two-call form around autograd takes the same route
+    l2, ws = ops.lovasz_softmax_fwd(xd, ld, 1.0, True)
+    d2 = ops.lovasz_softmax_bwd(xd, ws, None, 1.0)
+    assert torch.equal(l2, loss_out) and torch.equal(d2, dl)
+
+
+@pytest.mark.parametrize("K", BIGK)
+def test_cross_entropy_beyond_25_classes(ops, K):
+    x, lab = bigk_inputs(K, 2)
+    xd, ld = x.cuda(), lab.cuda()
+    loss_out, dl = torch.full((1,), 7.0, device="cuda"), torch.full((P8, K), 7.0, device="cuda")
+    if not serves("cross_entropy", K):
+        return refused(lambda: ops.cross_entropy(xd, ld, K, 1.0, dl, loss_out=loss_out), [loss_out, dl])
+    ops.cross_entropy(xd, ld, K, 1.0, dl, loss_out=loss_out)
+    (l64, g64), (l32, g32) = ce_ref(x, lab, K, 1.0, torch.float64), ce_ref(x, lab, K, 1.0, torch.float32)
+    within("cross_entropy loss", "K%d-P%d" % (K, P8), loss_out, l64, l32)
+    within("cross_entropy grad", "K%d-P%d" % (K, P8), dl, g64, g32)
+
+
+@pytest.mark.parametrize("K", BIGK)
+def test_confusion_matrix_beyond_25_classes(ops, K):
+    x, lab = bigk_inputs(K, 3)
+    xd, ld = x.cuda(), lab.cuda()
+    cm = torch.full((K, K), 5, dtype=torch.int32, device="cuda")
+    if not serves("confusion_matrix", K):
+        return refused(lambda: ops.confusion_matrix(xd, ld, cm=cm), [cm])
+    ops.confusion_matrix(xd, ld, cm=cm)
+    assert np.array_equal(cm.cpu().numpy(), cm_ref(x, lab, K)[0] + 5)
+
+
+@pytest.mark.parametrize("K", BIGK)
+def test_ohem_beyond_25_classes(ops, K):
+    from oracle import losses as OL
+    x, lab = bigk_inputs(K, 4)
+    lab[lab == K] = -100                     # the oracle's ignore label without an experiment
+
+    def ref(dt):
+        xr = x.to(dt).requires_grad_()
+        loss = OL.ohem_cross_entropy(xr.t().reshape(1, K, P8, 1), lab.reshape(1, P8, 1), None, 0.7, 500)
+        loss.backward()
+        return loss.detach().reshape(1), xr.grad
+    xd, ld = x.cuda(), lab.cuda()
+    loss_out, dl = torch.full((1,), 7.0, device="cuda"), torch.full((P8, K), 7.0, device="cuda")
+    if not serves("ohem", K):
+        return refused(lambda: ops.ohem_cross_entropy(xd, ld, -100, 0.7, 500, 1.0, dl, loss_out=loss_out), [loss_out, dl])
+    ops.ohem_cross_entropy(xd, ld, -100, 0.7, 500, 1.0, dl, loss_out=loss_out)
+    (l64, g64), (l32, g32) = ref(torch.float64), ref(torch.float32)
+    within("ohem loss K>25", "K%d" % K, loss_out, l64, l32)
+    within("ohem grad K>25", "K%d" % K, dl, g64, g32)
