@@ -6,6 +6,8 @@ walks the tape in reverse, writing parameter gradients straight into one flat fp
 torch.autograd sees exactly one node per network (``NetFunction``) and one per loss, which keeps
 the reference's ``loss.backward(); optimiser.step()`` calling convention working.
 """
+import collections
+
 import torch
 from torch import nn
 
@@ -280,7 +282,8 @@ class Ctx:
         return buf, False
 
     def pgrad(self, p):
-        return p.grad
+        """where the gradient of parameter p is written (None for an absent bias)"""
+        return None if p is None else p.grad
 
     def done(self, *params):
         """gradient of these parameters has been enqueued.  Inside a parallel region the signal is held back until the region
@@ -385,34 +388,217 @@ FUSE_BN_STATS = True  # training forward: BatchNorm batch statistics from the co
 FUSE_EVAL_BN = True   # eval-mode forward: fold BatchNorm into the conv and fuse bias/residual/ReLU into its epilogue
 
 
-def _fused_head(cx, x, x_in, y, stats, scale, conv, bn, head, need_dx, pad_to):
-    """BatchNorm + ReLU + the K-class 1 x 1 classifier `head` behind the head convolution `conv` whose output y (and batch statistics) exist:
-    the normalised activation and its gradient are never written (ops.head_fwd / ops.head_backward, csrc/headfuse.h); the convolution's
-    backward streams the blocked planes of dy as on conv_bn_act's head route."""
-    w, hw = conv.weight, head.weight
-    Cout, K = w.shape[0], hw.shape[0]
-    kh, kw = conv.kernel_size
-    s, p, d = conv.stride[0], conv.padding[0], conv.dilation[0]
-    cx.claim(hw, head.bias)
-    hb = head.bias.data if head.bias is not None else None
-    logits = ops.head_fwd(y, stats[:Cout], scale, bn.bias.data, hw.data, hb, K, max(pad_to, (K + 3) // 4 * 4))
+# ---- the path of one conv_bn_act layer: decided ONCE, in its forward, and written down as a Path ------------------------------------------
+# input form -- how the convolution reads x:
+#   stem7 / stem3   the image as it is through a direct stem kernel (csrc/stem7.hip: ResNet 7x7/2; csrc/stem3.hip: HRNet 3x3/2), training forward
+#   stem4           the implicit GEMM's packed 4-channel stem (image as NHWC-4, weights as ops.stem_pack_weight)
+#   pad3            a 3-channel image into a generic convolution: image and weights padded to 4 channels
+#   plain           an NHWC activation
+STEM7, STEM3, STEM4, PAD3, PLAIN = "stem7", "stem3", "stem4", "pad3", "plain"
+# forward form: eval-mode BatchNorm folded into the convolution / training (batch statistics) / eval-mode BatchNorm as a kernel of its own
+FOLDED, TRAIN, EVAL = "folded", "train", "eval"
+# backward form (recorded training passes only, else None) -- in which form the gradient of the convolution's output exists:
+#   planes   fp16 x 2 planes that the trunk's plane kernels stream (_bwd_planes)
+#   h2       blocked f16x2 planes that both GEMMs of a head layer read (_bwd_h2)
+#   head     as h2, behind the fused BatchNorm + ReLU + classifier (_fused_head / _bwd_fused_head)
+#   generic  an fp32 tensor (_bwd_generic)
+BWD_PLANES, BWD_H2, BWD_HEAD, BWD_GENERIC = "planes", "h2", "head", "generic"
+Path = collections.namedtuple("Path", "input forward backward")
 
-    def bwd():
-        dl = cx.take(logits)
-        if dl is None:
-            return
-        dyp, dysc = ops.head_backward(dl, y, stats, bn.weight.data, bn.bias.data, hw.data, cx.pgrad(hw),
-                                      cx.pgrad(head.bias) if head.bias is not None else None, cx.pgrad(bn.weight), cx.pgrad(bn.bias),
-                                      cx.pgrad(conv.bias) if conv.bias is not None else None)
-        del dl
-        cx.done(hw, head.bias)
-        ops.conv_bwd_weight_h2(x_in, dyp, dysc, Cout, cx.pgrad(w), kh, kw, s, p, d)
-        if need_dx:
-            dx, accx = cx.dest(x)
-            ops.conv_bwd_data_h2(dyp, dysc, w.data, tuple(x.shape), Cout, kh, kw, p, d, dx, accx)
-        cx.done(bn.weight, bn.bias, w, conv.bias)
-    cx.push(bwd)
+# what a recorded layer keeps for its backward (z: the tensor whose cotangent starts it -- the fused head's logits on that form)
+_Saved = collections.namedtuple("_Saved", "cx path c bn x x_in wk y stats yrec z relu residual need_dx private_in")
+
+# the first pass of a BatchNorm's backward as its private_in consumer's backward-data epilogue left it: sums = what ops.bn_backward_pre /
+# bn_backward_pre_planes take, planes = it came from the plane kernel (ops.conv_bwd_data_pl) and carries max|g|
+_Pre = collections.namedtuple("_Pre", "sums planes")
+
+
+def _input_form(cx, x, conv, c, need_dx, out):
+    w3 = (not conv.stem) and c.weight.shape[1] == 3       # 3-channel image into a generic conv (HRNet 3x3/2 stem)
+    direct = cx.train and c.bias is None and not need_dx and out is None
+    if (conv.stem and direct and c.weight.data.is_contiguous(memory_format=torch.channels_last)
+            and ops.stem7_ok(x, c.weight.data, c.kh, c.kw, c.stride, c.pad, c.dil, c.groups)):
+        # the ResNet stem's first convolution, training forward: the direct fp64-accumulating kernel on the image as it is (csrc/stem7.hip);
+        # the backward-weight pass packs its operands for the implicit GEMM itself
+        return STEM7
+    if conv.stem:
+        return STEM4
+    if w3 and direct and ops.stem3_ok(x, c.weight.data, c.kh, c.kw, c.stride, c.pad, c.dil, c.groups):
+        # the HRNet stem's first convolution: HBM-bound direct kernels on the image as it is (NCHW or NHWC-4), no repack, no channel padding
+        return STEM3
+    return PAD3 if w3 else PLAIN
+
+
+def _conv_input(inp, x, c):
+    """(x_in, wk): input and weights as the forward kernel of input form `inp` reads them"""
+    if inp == STEM4:
+        return (x if is_nhwc4(x) else ops.nchw3_to_nhwc4(x)), ops.stem_pack_weight(c.weight.data, c.Cout)
+    if inp == PAD3:
+        return (x if is_nhwc4(x) else ops.nchw3_to_nhwc4(x)), ops.weight_pad_cin(c.weight.data, c.Cout, c.kh * c.kw, 3, 4)
+    return x, c.weight.data
+
+
+def _conv_weight_grad(cx, inp, c, x_in, wk, dy):
+    """weight (and bias) gradient of a convolution of input form `inp` from its fp32 output gradient"""
+    dw, dbias = cx.pgrad(c.weight), cx.pgrad(c.bias)
+    if inp in (STEM7, STEM4):
+        x4 = x_in if is_nhwc4(x_in) else ops.nchw3_to_nhwc4(x_in)      # (stem7: the forward read the image as it was)
+        dpk = torch.empty((c.Cout, 7, 8, 4), dtype=torch.float32, device=dy.device)     # the packed layout of ops.stem_pack_weight
+        ops.conv_bwd_weight(x4, dy, dpk, dbias, c.kh, c.kw, c.stride, c.pad, c.dil, stem4=True)
+        ops.stem_unpack_grad(dpk, dw, c.Cout)
+    elif inp == STEM3:
+        ops.stem3_bwd_weight(x_in, dy, dw)
+    elif inp == PAD3:
+        dpk = torch.empty_like(wk)
+        ops.conv_bwd_weight(x_in, dy, dpk, dbias, c.kh, c.kw, c.stride, c.pad, c.dil)
+        ops.weight_unpad_cin(dpk, dw, c.Cout, c.kh * c.kw, 3, 4)
+    else:
+        ops.conv_bwd_weight(x_in, dy, dw, dbias, c.kh, c.kw, c.stride, c.pad, c.dil, groups=c.groups)
+
+
+def _backward_form(inp, c, x_in, y, yrec, partials, relu, residual, out, need_dx, head):
+    """the backward form of a recorded training layer, from what its forward knows.  Everything asked here holds until the layer's backward:
+    the module switches behind ops.h2_dy_route are set before a pass, not inside one (and the forward of the fused head has already acted
+    on the answer), shapes and modules do not change."""
+    if yrec is not None:
+        # The convolution ran the plane kernel (ops.fwd_route: D3P), which takes no bias and reads the planes of x -- its producer's, or the
+        # ones ops.conv_fwd attached to x for this layer.  They are still there in the backward: `_planes` is an attribute of the tensor
+        # OBJECT, and ops.drop_amax clears it only on the destination of a launch that overwrites that object.  A recorded pass writes an
+        # activation before its first consumer reads it (every form's backward-weight reads x as the forward saw it), a tensor with planes
+        # is never an `out=` view of a concatenation buffer (bn_apply writes planes only where out is None), and the destinations of the
+        # backward pass are gradient buffers (Ctx.dest / Ctx._own).  (The fused head below needs no planes for z, i.e. zrec is None; with
+        # its other conditions that means yrec is None: planes_ok held for this width a moment ago, inside ops.conv_fwd.)
+        return BWD_PLANES
+    if residual is None and inp == PLAIN and ops.h2_dy_route(x_in, y, c.weight.data, c.kh, c.kw, c.stride, c.pad, c.dil, c.groups, need_dx):
+        # head layers on the f16x2 kernels: dy exists only as the blocked planes both of its consumers read
+        if (head is not None and TAPS is None and relu and out is None and partials is not None and head.kernel_size == (1, 1)
+                and head.stride == (1, 1) and head.padding == (0, 0) and head.groups == 1 and ops.head_fuse_ok(y, head.weight.shape[0])):
+            return BWD_HEAD
+        return BWD_H2
+    return BWD_GENERIC
+
+
+def _fused_head(L, scale, head, pad_to):
+    """BatchNorm + ReLU + the K-class 1 x 1 classifier `head` behind the head convolution whose output L.y (and batch statistics) exist:
+    the normalised activation and its gradient are never written (ops.head_fwd / ops.head_backward, csrc/headfuse.h); the convolution's
+    backward streams the blocked planes of dy as on the h2 form."""
+    hw, K = head.weight, head.weight.shape[0]
+    L.cx.claim(hw, head.bias)
+    hb = head.bias.data if head.bias is not None else None
+    logits = ops.head_fwd(L.y, L.stats[:L.c.Cout], scale, L.bn.bias.data, hw.data, hb, K, max(pad_to, (K + 3) // 4 * 4))
+    L = L._replace(z=logits)
+    L.cx.push(lambda: _bwd_fused_head(L, head))
     return logits
+
+
+def _bwd_fused_head(L, head):
+    cx, bn = L.cx, L.bn
+    dl = cx.take(L.z)
+    if dl is None:
+        return
+    dyp, dysc = ops.head_backward(dl, L.y, L.stats, bn.weight.data, bn.bias.data, head.weight.data, cx.pgrad(head.weight), cx.pgrad(head.bias),
+                                  cx.pgrad(bn.weight), cx.pgrad(bn.bias), cx.pgrad(L.c.bias))
+    del dl
+    cx.done(head.weight, head.bias)
+    _h2_tail(L, dyp, dysc)
+
+
+def _h2_tail(L, dyp, dysc):
+    """backward-weight and backward-data of a head convolution from the blocked planes of its output gradient"""
+    cx, c, x = L.cx, L.c, L.x
+    ops.conv_bwd_weight_h2(L.x_in, dyp, dysc, c.Cout, cx.pgrad(c.weight), c.kh, c.kw, c.stride, c.pad, c.dil)
+    if L.need_dx:
+        dx, accx = cx.dest(x)
+        ops.conv_bwd_data_h2(dyp, dysc, c.weight.data, tuple(x.shape), c.Cout, c.kh, c.kw, c.pad, c.dil, dx, accx)
+    cx.done(L.bn.weight, L.bn.bias, c.weight, c.bias)
+
+
+def _conv_bn_act_backward(L):
+    """tape entry of a conv_bn_act layer: its backward form, but for what only the backward knows -- whether z's private_in consumer ran
+    the first pass of this BatchNorm's backward in its backward-data epilogue (`pre`), and in which kernel.  The planes form merges a
+    pre of the plane kernel only, the h2 form none; the generic form takes either."""
+    pre = L.cx.bn_pre.pop(id(L.z), None)
+    L.cx.bn_src.pop(id(L.z), None)          # (its private_in consumer, if any, has run: y is not kept alive beyond this layer's backward)
+    form = L.path.backward
+    if form == BWD_PLANES and (pre is None or pre.planes):
+        _bwd_planes(L, pre)
+    elif form == BWD_H2 and pre is None:
+        _bwd_h2(L)
+    else:
+        _bwd_generic(L, pre)
+
+
+def _cotangent(L):
+    """(dz, dres, accumulate): the gradient of the layer's output -- None when nothing reached it -- and where the residual branch's goes"""
+    dz = L.cx.take(L.z)
+    if dz is None or L.residual is None:
+        return dz, None, False
+    return (dz,) + L.cx.dest(L.residual)
+
+
+def _input_grad(L, dgrad, planes):
+    """dx through dgrad(dx, accumulate, bn_src) -> (dx, pre), one of ops.conv_bwd_data / conv_bwd_data_pl(with_pre=True).  private_in: x is
+    relu(bn(.)) of the preceding conv_bn_act and has no other consumer; where this call is the first contribution to its gradient the
+    kernel may run the first pass of that BatchNorm's backward in its epilogue, and that layer's backward finds `pre` under cx.bn_pre."""
+    cx, x = L.cx, L.x
+    dx, accx = cx.dest(x)
+    src = cx.bn_src.get(id(x)) if (L.private_in and not accx) else None
+    pre = dgrad(dx, accx, src)[1]
+    if pre is not None:
+        cx.bn_pre[id(x)] = _Pre(pre, planes)
+
+
+def _bwd_planes(L, pre):
+    """planes form: the gradient of the convolution's output exists as planes only; backward-weight and backward-data stream them"""
+    cx, bn, w = L.cx, L.bn, L.c.weight
+    dz, dres, acc = _cotangent(L)
+    if dz is None:
+        return
+    if pre is not None:
+        dyp = ops.bn_backward_pre_planes(dz, L.y, L.stats, bn.weight.data, pre.sums, L.yrec, cx.pgrad(bn.weight), cx.pgrad(bn.bias))
+    else:
+        z_mask = L.z if (L.residual is not None or not L.relu) else None
+        dyp = ops.bn_backward_planes(dz, z_mask, L.y, L.stats, bn.weight.data, L.relu, cx.pgrad(bn.weight), cx.pgrad(bn.bias), dres, acc,
+                                     bn.bias.data, L.yrec)
+    del dz
+    ops.dwgrad3_pl(ops.planes_of(L.x_in), dyp, cx.pgrad(w))
+    if L.need_dx:
+        _input_grad(L, lambda dx, accx, src: ops.conv_bwd_data_pl(dyp, w.data, dx, accumulate=accx, bn_src=src, with_pre=True), True)
+    cx.done(bn.weight, bn.bias, w, L.c.bias)
+
+
+def _bwd_h2(L):
+    """h2 form: dy exists only as the blocked planes both of its consumers read (ops.bn_backward_h2)"""
+    cx, bn = L.cx, L.bn
+    dz = cx.take(L.z)
+    if dz is None:
+        return
+    dyp, dysc = ops.bn_backward_h2(dz, L.y, L.stats, bn.weight.data, L.relu, cx.pgrad(bn.weight), cx.pgrad(bn.bias), bn.bias.data,
+                                   cx.pgrad(L.c.bias))
+    del dz
+    _h2_tail(L, dyp, dysc)
+
+
+def _bwd_generic(L, pre):
+    """generic form: dy as an fp32 tensor through ops.conv_bwd_weight / conv_bwd_data"""
+    cx, bn, c, x = L.cx, L.bn, L.c, L.x
+    dz, dres, acc = _cotangent(L)
+    if dz is None:
+        return
+    if pre is not None:
+        # dz is already masked and its per-tile sums exist (the consumer's backward-data epilogue): merge + apply only
+        dy = ops.bn_backward_pre(dz, L.y, L.stats, bn.weight.data, pre.sums, cx.pgrad(bn.weight), cx.pgrad(bn.bias))
+    else:
+        # without a residual branch the ReLU mask is recomputed from y (z is not read: 1 of 3 tensor reads saved)
+        z_mask = L.z if (L.residual is not None or not L.relu) else None
+        dy = ops.bn_backward(dz, z_mask, L.y, L.stats, bn.weight.data, L.relu, cx.pgrad(bn.weight), cx.pgrad(bn.bias), dres, acc,
+                             beta=bn.bias.data)
+    del dz
+    _conv_weight_grad(cx, L.path.input, c, L.x_in, L.wk, dy)
+    if L.path.input == PLAIN and L.need_dx:         # (every other input form reads the image)
+        _input_grad(L, lambda dx, accx, src: ops.conv_bwd_data(dy, c.weight.data, tuple(x.shape), c.kh, c.kw, c.stride, c.pad, c.dil, out=dx,
+                                                               accumulate=accx, groups=c.groups, bn_src=src, with_pre=True), False)
+    cx.done(bn.weight, bn.bias, c.weight, c.bias)
 
 
 def conv_bn_act(cx, x, conv, bn, relu=True, residual=None, out=None, need_dx=True, private_in=False, sole_conv_out=False, head=None, z_tap=None):
@@ -426,156 +612,62 @@ def conv_bn_act(cx, x, conv, bn, relu=True, residual=None, out=None, need_dx=Tru
     backward in its epilogue (ops.conv_bwd_data(bn_src=...)).
     sole_conv_out: the caller states that the OUTPUT of this layer feeds nothing but one conv_bn_act(private_in=True) (the same first half
     of a BasicBlock, seen from the producer): on the planes route (ops.planes_ok) it then exists as fp16 x 2 planes only."""
-    w = conv.weight
-    Cout = w.shape[0]
-    kh, kw = conv.kernel_size
-    s, p, d = conv.stride[0], conv.padding[0], conv.dilation[0]
-    pad3 = (not conv.stem) and w.shape[1] == 3       # 3-channel image into a generic conv (HRNet 3x3/2 stem)
-    stem3 = stem7 = False
-    if (conv.stem and cx.train and conv.bias is None and not need_dx and out is None and w.data.is_contiguous(memory_format=torch.channels_last)
-            and ops.stem7_ok(x, w.data, kh, kw, s, p, d, conv.groups)):
-        # the ResNet stem's first convolution, training forward: the direct fp64-accumulating kernel on the image as it is (csrc/stem7.hip);
-        # the backward-weight pass packs its operands for the implicit GEMM itself
-        stem7 = True
-        x_in, wk = x, w.data
-    elif conv.stem:
-        x_in = x if is_nhwc4(x) else ops.nchw3_to_nhwc4(x)
-        wk = ops.stem_pack_weight(w.data, Cout)
-    elif pad3 and cx.train and conv.bias is None and not need_dx and out is None and ops.stem3_ok(x, w.data, kh, kw, s, p, d, conv.groups):
-        # the HRNet stem's first convolution: HBM-bound direct kernels on the image as it is (NCHW or NHWC-4), no repack, no channel padding
-        stem3 = True
-        x_in, wk = x, w.data
-    elif pad3:
-        x_in = x if is_nhwc4(x) else ops.nchw3_to_nhwc4(x)
-        wk = ops.weight_pad_cin(w.data, Cout, kh * kw, 3, 4)
-    else:
-        x_in, wk = x, w.data
-    bias = conv.bias.data if conv.bias is not None else None
-    cx.claim(w, conv.bias, bn.weight, bn.bias)
-    zrec = yrec = None
-    if not cx.train and not cx.record and FUSE_EVAL_BN:
+    c = ops.conv_args(conv)
+    Cout = c.Cout
+    inp = _input_form(cx, x, conv, c, need_dx, out)
+    x_in, wk = _conv_input(inp, x, c)
+    bias = c.bias.data if c.bias is not None else None
+    cx.claim(c.weight, c.bias, bn.weight, bn.bias)
+    fwd = FOLDED if (not cx.train and not cx.record and FUSE_EVAL_BN) else TRAIN if cx.train else EVAL
+    if fwd == FOLDED:
         # inference fast path: eval-mode BatchNorm folded into the weights, bias + residual + ReLU applied in
         # the convolution epilogue — one kernel per layer, no separate normalisation pass over HBM
         per_out = wk.numel() // Cout
         wf, bf = ops.fold_bn(wk, bias, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, bn.eps, Cout, per_out)
-        zf = ops.conv_fwd_fused(x_in, wf, bf, residual, relu, Cout, kh, kw, s, p, d, out=out, stem4=conv.stem, groups=conv.groups)
+        zf = ops.conv_fwd_fused(x_in, wf, bf, residual, relu, Cout, c.kh, c.kw, c.stride, c.pad, c.dil, out=out, stem4=inp == STEM4, groups=c.groups)
         if z_tap is not None:
             tap(z_tap, zf)
         return zf if head is None else conv_bias(cx, zf, head)
-    if cx.train:
+    partials = yrec = zrec = None
+    if fwd == TRAIN:
         # batch statistics: per-tile partial sums come out of the convolution's epilogue (no separate pass over y)
-        if stem3:
-            y = ops.stem3_fwd(x_in, wk, None, bn_stats=FUSE_BN_STATS)
-        elif stem7:
-            y = ops.stem7_fwd(x_in, wk, None, bn_stats=FUSE_BN_STATS)
+        if inp == STEM3:
+            res = ops.stem3_fwd(x_in, wk, None, bn_stats=FUSE_BN_STATS)
+        elif inp == STEM7:
+            res = ops.stem7_fwd(x_in, wk, None, bn_stats=FUSE_BN_STATS)
         else:
-            y = ops.conv_fwd(x_in, wk, bias, Cout, kh, kw, s, p, d, stem4=conv.stem, groups=conv.groups, bn_stats=FUSE_BN_STATS, train=cx.record,
-                             exact=conv.exact_operands)
-        y, partials = y if FUSE_BN_STATS else (y, None)
-        # planes route: the convolution streamed planes and left max|y|; then the BatchNorm's output gets planes too (exponent from a bound)
-        yrec = getattr(y, "_yrec", None)
+            res, yrec = ops.conv_fwd(x_in, wk, bias, Cout, c.kh, c.kw, c.stride, c.pad, c.dil, stem4=inp == STEM4, groups=c.groups,
+                                     bn_stats=FUSE_BN_STATS, train=cx.record, exact=conv.exact_operands, with_yrec=True)
+        y, partials = res if FUSE_BN_STATS else (res, None)
+        # planes route: the convolution streamed planes and left max|y| (yrec); then the BatchNorm's output gets planes too (exponent from a bound)
         if (yrec is not None and partials is not None and out is None and ops.planes_ok(Cout, ops.rows_of(y))
                 and (residual is None or ops.amax_of(residual) is not None)):
             zrec = ops.new_amax(y.device)
-        if zrec is not None:
+        if partials is not None:
             stats, scale = ops.bn_finalize(partials, ops.rows_of(y), Cout, bn.weight.data, bn.eps, bn.momentum, bn.running_mean, bn.running_var,
-                                           bound=(bn.bias.data, yrec, zrec))
-        elif partials is not None:
-            stats, scale = ops.bn_finalize(partials, ops.rows_of(y), Cout, bn.weight.data, bn.eps, bn.momentum, bn.running_mean, bn.running_var)
+                                           bound=(bn.bias.data, yrec, zrec) if zrec is not None else None)
         else:
             stats, scale = ops.bn_train_stats(y, bn.weight.data, bn.eps, bn.momentum, bn.running_mean, bn.running_var)
         bn._pending_batches += 1
         mean = stats[:Cout]
     else:
-        y = ops.conv_fwd(x_in, wk, bias, Cout, kh, kw, s, p, d, stem4=conv.stem, groups=conv.groups, train=cx.record)
+        y = ops.conv_fwd(x_in, wk, bias, Cout, c.kh, c.kw, c.stride, c.pad, c.dil, stem4=inp == STEM4, groups=c.groups, train=cx.record)
         stats = None
         mean = bn.running_mean
         scale = ops.bn_eval_scale(bn.weight.data, bn.running_var, bn.eps)
-    if (head is not None and cx.train and cx.record and TAPS is None and zrec is None and residual is None and relu and out is None
-            and not conv.stem and not pad3 and partials is not None and head.kernel_size == (1, 1) and head.stride == (1, 1)
-            and head.padding == (0, 0) and head.groups == 1 and ops.head_fuse_ok(y, head.weight.shape[0])
-            and ops.h2_dy_route(x_in, y, w.data, kh, kw, s, p, d, conv.groups, need_dx)):
-        return _fused_head(cx, x, x_in, y, stats, scale, conv, bn, head, need_dx, 32)
+    path = Path(inp, fwd, _backward_form(inp, c, x_in, y, yrec, partials, relu, residual, out, need_dx, head) if cx.record and fwd == TRAIN else None)
+    if path.backward == BWD_HEAD:
+        return _fused_head(_Saved(cx, path, c, bn, x, x_in, wk, y, stats, yrec, None, relu, residual, need_dx, private_in), scale, head, 32)
     z = ops.bn_apply(y, mean, scale, bn.bias.data, residual, relu, out=out, planes_rec=zrec,
                      planes_only=zrec is not None and sole_conv_out and relu and residual is None,
                      want_mask=cx.record and cx.train)       # (a residual block's output: its ReLU mask as bits for the backward pass)
     if cx.record:
-        if not cx.train:
+        if fwd != TRAIN:
             raise NotImplementedError("backward through eval-mode BatchNorm is not on the training path")
-
         if relu and residual is None and out is None:
             cx.bn_src[id(z)] = (y, stats, bn.weight.data, bn.bias.data)     # for a private_in consumer of z
-
-        def bwd():
-            dz = cx.take(z)
-            pre = cx.bn_pre.pop(id(z), None)
-            cx.bn_src.pop(id(z), None)          # (its private_in consumer, if any, has run: y is not kept alive beyond this layer's backward)
-            if dz is None:
-                return
-            dres, acc = (None, False)
-            if residual is not None:
-                dres, acc = cx.dest(residual)
-            if yrec is not None and (pre is None or len(pre) == 3) and ops.planes_of(x_in) is not None and conv.bias is None:
-                # planes route: the gradient of the convolution's output exists as planes only; backward-weight and backward-data stream them
-                if pre is not None:
-                    dyp = ops.bn_backward_pre_planes(dz, y, stats, bn.weight.data, pre, yrec, cx.pgrad(bn.weight), cx.pgrad(bn.bias))
-                else:
-                    z_mask = z if (residual is not None or not relu) else None
-                    dyp = ops.bn_backward_planes(dz, z_mask, y, stats, bn.weight.data, relu, cx.pgrad(bn.weight), cx.pgrad(bn.bias), dres, acc,
-                                                 bn.bias.data, yrec)
-                del dz
-                ops.dwgrad3_pl(ops.planes_of(x_in), dyp, cx.pgrad(w))
-                if need_dx:
-                    dx, accx = cx.dest(x)
-                    src = cx.bn_src.get(id(x)) if (private_in and not accx) else None
-                    r = ops.conv_bwd_data_pl(dyp, w.data, dx, accumulate=accx, bn_src=src)
-                    if isinstance(r, tuple):
-                        cx.bn_pre[id(x)] = r[1]
-                cx.done(bn.weight, bn.bias, w, conv.bias)
-                return
-            if (pre is None and residual is None and not conv.stem and not pad3
-                    and ops.h2_dy_route(x_in, y, w.data, kh, kw, s, p, d, conv.groups, need_dx)):
-                # head layers on the f16x2 kernels: dy exists only as the blocked planes both of its consumers read (ops.bn_backward_h2)
-                dyp, dysc = ops.bn_backward_h2(dz, y, stats, bn.weight.data, relu, cx.pgrad(bn.weight), cx.pgrad(bn.bias), bn.bias.data,
-                                               cx.pgrad(conv.bias) if conv.bias is not None else None)
-                del dz
-                ops.conv_bwd_weight_h2(x_in, dyp, dysc, Cout, cx.pgrad(w), kh, kw, s, p, d)
-                if need_dx:
-                    dx, accx = cx.dest(x)
-                    ops.conv_bwd_data_h2(dyp, dysc, w.data, tuple(x.shape), Cout, kh, kw, p, d, dx, accx)
-                cx.done(bn.weight, bn.bias, w, conv.bias)
-                return
-            if pre is not None:
-                # dz is already masked and its per-tile sums exist (the consumer's backward-data epilogue): merge + apply only
-                dy = ops.bn_backward_pre(dz, y, stats, bn.weight.data, pre, cx.pgrad(bn.weight), cx.pgrad(bn.bias))
-            else:
-                # without a residual branch the ReLU mask is recomputed from y (z is not read: 1 of 3 tensor reads saved)
-                z_mask = z if (residual is not None or not relu) else None
-                dy = ops.bn_backward(dz, z_mask, y, stats, bn.weight.data, relu, cx.pgrad(bn.weight), cx.pgrad(bn.bias), dres, acc,
-                                     beta=bn.bias.data)
-            del dz
-            dbias = cx.pgrad(conv.bias) if conv.bias is not None else None
-            if conv.stem:
-                x4 = x_in if is_nhwc4(x_in) else ops.nchw3_to_nhwc4(x_in)      # (stem7: the forward read the image as it was)
-                dpk = torch.empty((Cout, 7, 8, 4), dtype=torch.float32, device=dy.device)     # the packed layout of ops.stem_pack_weight
-                ops.conv_bwd_weight(x4, dy, dpk, dbias, kh, kw, s, p, d, stem4=True)
-                ops.stem_unpack_grad(dpk, cx.pgrad(w), Cout)
-            elif stem3:
-                ops.stem3_bwd_weight(x_in, dy, cx.pgrad(w))
-            elif pad3:
-                dpk = torch.empty_like(wk)
-                ops.conv_bwd_weight(x_in, dy, dpk, dbias, kh, kw, s, p, d)
-                ops.weight_unpad_cin(dpk, cx.pgrad(w), Cout, kh * kw, 3, 4)
-            else:
-                ops.conv_bwd_weight(x_in, dy, cx.pgrad(w), dbias, kh, kw, s, p, d, groups=conv.groups)
-                if need_dx:
-                    dx, accx = cx.dest(x)
-                    src = cx.bn_src.get(id(x)) if (private_in and not accx) else None
-                    r = ops.conv_bwd_data(dy, w.data, tuple(x.shape), kh, kw, s, p, d, out=dx, accumulate=accx, groups=conv.groups, bn_src=src)
-                    if isinstance(r, tuple):
-                        cx.bn_pre[id(x)] = r[1]
-            cx.done(bn.weight, bn.bias, w, conv.bias)
-        cx.push(bwd)
+        L = _Saved(cx, path, c, bn, x, x_in, wk, y, stats, yrec, z, relu, residual, need_dx, private_in)
+        cx.push(lambda: _conv_bn_act_backward(L))
     if z_tap is not None:
         tap(z_tap, z)
     return z if head is None else conv_bias(cx, z, head)
@@ -584,23 +676,19 @@ def conv_bn_act(cx, x, conv, bn, relu=True, residual=None, out=None, need_dx=Tru
 def conv_bias(cx, x, conv, pad_to=32):
     """plain conv (+bias), used for the K-class classifier heads.  The output keeps a zero-padded
     row stride (pad_to floats) so that it can feed 16-byte-granular kernels."""
-    w = conv.weight
-    Cout = w.shape[0]
-    kh, kw = conv.kernel_size
-    s, p, d = conv.stride[0], conv.padding[0], conv.dilation[0]
+    w, Cout, kh, kw, s, p, d, _, b = ops.conv_args(conv)
     ld = max(pad_to, (Cout + 3) // 4 * 4)
-    bias = conv.bias.data if conv.bias is not None else None
-    y = ops.conv_fwd(x, w.data, bias, Cout, kh, kw, s, p, d, zero_to=ld, train=cx.record)
-    cx.claim(w, conv.bias)
+    y = ops.conv_fwd(x, w.data, b.data if b is not None else None, Cout, kh, kw, s, p, d, zero_to=ld, train=cx.record)
+    cx.claim(w, b)
     if cx.record:
         def bwd():
             dy = cx.take(y)
             if dy is None:
                 return
-            ops.conv_bwd_weight(x, dy, cx.pgrad(w), cx.pgrad(conv.bias) if conv.bias is not None else None, kh, kw, s, p, d)
+            ops.conv_bwd_weight(x, dy, cx.pgrad(w), cx.pgrad(b), kh, kw, s, p, d)
             dx, acc = cx.dest(x)
             ops.conv_bwd_data(dy, w.data, tuple(x.shape), kh, kw, s, p, d, out=dx, accumulate=acc)
-            cx.done(w, conv.bias)
+            cx.done(w, b)
         cx.push(bwd)
     return y
 
@@ -608,19 +696,11 @@ def conv_bias(cx, x, conv, pad_to=32):
 def conv_act(cx, x, conv, relu=True):
     """conv + bias (+ ReLU) without normalisation -- the VGG-style layers of models/FCN.py:42-55 of the reference: bias and ReLU run in
     the convolution's epilogue.  x NHWC (or the raw NCHW image for a 3-channel first layer)."""
-    w = conv.weight
-    Cout = w.shape[0]
-    kh, kw = conv.kernel_size
-    s, p, d = conv.stride[0], conv.padding[0], conv.dilation[0]
-    pad3 = w.shape[1] == 3
-    if pad3:
-        x_in = x if is_nhwc4(x) else ops.nchw3_to_nhwc4(x)
-        wk = ops.weight_pad_cin(w.data, Cout, kh * kw, 3, 4)
-    else:
-        x_in, wk = x, w.data
-    bias = conv.bias.data if conv.bias is not None else None
-    cx.claim(w, conv.bias)
-    z = ops.conv_fwd_fused(x_in, wk, bias, None, relu, Cout, kh, kw, s, p, d)
+    c = ops.conv_args(conv)
+    inp = PAD3 if c.weight.shape[1] == 3 else PLAIN
+    x_in, wk = _conv_input(inp, x, c)
+    cx.claim(c.weight, c.bias)
+    z = ops.conv_fwd_fused(x_in, wk, c.bias.data if c.bias is not None else None, None, relu, c.Cout, c.kh, c.kw, c.stride, c.pad, c.dil)
     if cx.record:
         def bwd():
             dz = cx.take(z)
@@ -628,16 +708,11 @@ def conv_act(cx, x, conv, relu=True):
                 return
             dy = ops.relu_bwd(dz, z) if relu else dz
             del dz
-            dbias = cx.pgrad(conv.bias) if conv.bias is not None else None
-            if pad3:
-                dpk = torch.empty_like(wk)
-                ops.conv_bwd_weight(x_in, dy, dpk, dbias, kh, kw, s, p, d)
-                ops.weight_unpad_cin(dpk, cx.pgrad(w), Cout, kh * kw, 3, 4)
-            else:
-                ops.conv_bwd_weight(x_in, dy, cx.pgrad(w), dbias, kh, kw, s, p, d)
+            _conv_weight_grad(cx, inp, c, x_in, wk, dy)
+            if inp == PLAIN:
                 dx, acc = cx.dest(x)
-                ops.conv_bwd_data(dy, w.data, tuple(x.shape), kh, kw, s, p, d, out=dx, accumulate=acc)
-            cx.done(w, conv.bias)
+                ops.conv_bwd_data(dy, c.weight.data, tuple(x.shape), c.kh, c.kw, c.stride, c.pad, c.dil, out=dx, accumulate=acc)
+            cx.done(c.weight, c.bias)
         cx.push(bwd)
     return z
 
@@ -666,21 +741,18 @@ class ConvTranspose2d(nn.ConvTranspose2d):
 def conv_transpose(cx, x, deconv):
     """nn.ConvTranspose2d on a class-logit tensor (rows zero padded to 32 floats: conv_bias's output).  The transposed convolution IS the
     backward-data pass of the convolution with the same weight tensor; its own backward is that convolution's forward / backward-weight."""
-    w = deconv.weight
-    Cin, Cout = w.shape[0], w.shape[1]
-    k, s, p = deconv.kernel_size[0], deconv.stride[0], deconv.padding[0]
-    assert deconv.kernel_size[0] == deconv.kernel_size[1] and deconv.output_padding[0] == 0 and deconv.dilation[0] == 1 and deconv.groups == 1
-    bias = deconv.bias.data if deconv.bias is not None else None
-    cx.claim(w, deconv.bias)
-    y, wp = ops.conv_transpose_fwd(x, w.data, bias, Cout, k, s, p)
+    w, Cout, k, kw, s, p, d, groups, b = ops.conv_args(deconv)
+    assert k == kw and deconv.output_padding[0] == 0 and d == 1 and groups == 1
+    cx.claim(w, b)
+    y, wp = ops.conv_transpose_fwd(x, w.data, b.data if b is not None else None, Cout, k, s, p)
     if cx.record:
         def bwd():
             dy = cx.take(y)
             if dy is None:
                 return
             dx, acc = cx.dest(x)
-            ops.conv_transpose_bwd(dy, x, wp, cx.pgrad(w), cx.pgrad(deconv.bias) if deconv.bias is not None else None, k, s, p, dx, acc)
-            cx.done(w, deconv.bias)
+            ops.conv_transpose_bwd(dy, x, wp, cx.pgrad(w), cx.pgrad(b), k, s, p, dx, acc)
+            cx.done(w, b)
         cx.push(bwd)
     return y
 

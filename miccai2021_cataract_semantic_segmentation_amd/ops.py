@@ -943,6 +943,17 @@ def wgrad_route(L):
     return F32
 
 
+ConvArgs = collections.namedtuple("ConvArgs", "weight Cout kh kw stride pad dil groups bias")
+
+
+def conv_args(conv):
+    """THE unpacking of a convolution module (nn.Conv2d / nn.ConvTranspose2d; stride, padding and dilation are square in every model here).
+    weight and bias are the parameters themselves; a shape-only stand-in for a module (the planner's predictors) has no weight"""
+    kh, kw = conv.kernel_size
+    return ConvArgs(getattr(conv, "weight", None), conv.out_channels, kh, kw, conv.stride[0], conv.padding[0], conv.dilation[0], conv.groups,
+                    conv.bias)
+
+
 def _h2_only_guard(x, route, what):
     """a tensor that exists only as blocked f16x2 planes may only take the route that reads them"""
     if getattr(x, "_h2_only", False) and route != H2_BLOCKED:
@@ -950,7 +961,7 @@ def _h2_only_guard(x, route, what):
 
 
 def conv_fwd(x, w_ptr_tensor, bias, Cout, kh, kw, stride=1, pad=0, dil=1, out=None, zero_to=0, stem4=False, groups=1, bn_stats=False, train=False,
-             exact=False):
+             exact=False, with_yrec=False):
     """train=True (the engine's recorded forward): a backward pass will follow -- the split planes of x are written in both layouts
     and kept for it (release_b3_cache() frees them).
     exact=True (the first layers of a trunk, whose rounding error the rest of the network amplifies most: tools/error_growth.py): the
@@ -958,7 +969,9 @@ def conv_fwd(x, w_ptr_tensor, bias, Cout, kh, kw, stride=1, pad=0, dil=1, out=No
     kernels could take.  (Measured at 2 x 3 x 544 x 960, relative RMS error of layer1's output against fp64: fp32 CPU 1.22e-6, this 0.89e-6,
     two fp16 planes 1.12e-6, three bf16 planes / six products 1.25e-6 -- 84 accumulator roundings per output instead of 42.)
     bn_stats=True: returns (out, partials) where partials = (buffer, n_tiles, tile_rows) are the per-(M-tile, channel)
-    BatchNorm partial sums written by the convolution's epilogue (for bn_finalize), or None if this layer's kernel has none"""
+    BatchNorm partial sums written by the convolution's epilogue (for bn_finalize), or None if this layer's kernel has none
+    with_yrec=True: returns (result, record) -- result as without it, record the max|y| record the planes kernel left (None on every
+    other route)"""
     B, H, W, Cin = x.shape
     Ho, Wo = conv_out_size(H, kh, stride, pad, dil), conv_out_size(W, kw, stride, pad, dil)
     if out is None:
@@ -980,21 +993,20 @@ def conv_fwd(x, w_ptr_tensor, bias, Cout, kh, kw, stride=1, pad=0, dil=1, out=No
         yrec = new_amax(x.device)
         with _Timed("fwd_d3p", flops):
             res = dconv3_pl(xp, dconv3_weight_image(w_ptr_tensor, h2=True), None, out=out, bn_stats=bn_stats, out_rec=yrec)
-        (res[0] if bn_stats else res)._yrec = yrec
-        return res
+        return (res, yrec) if with_yrec else res
     if route in (D3H, D3):
         _refuse_placeholder(x, "the in-kernel-split direct 3x3 kernel")
         rec = amax_of(x) if route == D3H else None
         wimg = dconv3_weight_image(w_ptr_tensor, h2=rec is not None)
         with _Timed("fwd_d3h" if rec is not None else "fwd_d3", flops):
             res = dconv3(x, wimg, bias, out=out, bn_stats=bn_stats, x_amax=rec)
-        return res
+        return (res, None) if with_yrec else res
     _refuse_placeholder(x, "a convolution forward outside the planes route")
     if route == P1R:
         with _Timed("fwd_p1", flops):
             res = pconv1(x, p1_weight_image(w_ptr_tensor), bias, Cout, out, bn_stats=bn_stats)
         drop_amax(out)
-        return res
+        return (res, None) if with_yrec else res
     if route == S2P:
         d = make_desc(x.shape, ld_of(x), Cout, ld_of(out), kh, kw, stride, pad, dil)
         if bn_stats:
@@ -1038,9 +1050,8 @@ def conv_fwd(x, w_ptr_tensor, bias, Cout, kh, kw, stride=1, pad=0, dil=1, out=No
                                                     part.numel(), ctypes.byref(tr), ctypes.byref(nt), stream()))
             else:
                 check(lib.catseg_conv2d_fwd(ctypes.byref(d), ptr(x), ptr(w_ptr_tensor), ptr(bias), ptr(out), zero_to, stream()))
-    if bn_stats:
-        return out, ((part, nt.value, tr.value) if tr.value > 0 else None)
-    return out
+    res = (out, (part, nt.value, tr.value) if tr.value > 0 else None) if bn_stats else out
+    return (res, None) if with_yrec else res
 
 
 def bn_finalize(partials, rows, C, gamma, eps, momentum, running_mean, running_var, bound=None):
@@ -1066,10 +1077,11 @@ def bn_finalize(partials, rows, C, gamma, eps, momentum, running_mean, running_v
 BN_BWD_FUSE = True    # first pass of the backward of relu(bn1(.)) in the epilogue of the backward-data kernel that produces its dz
 
 
-def conv_bwd_data(dy, w, xshape, kh, kw, stride=1, pad=0, dil=1, out=None, accumulate=False, groups=1, bn_src=None):
+def conv_bwd_data(dy, w, xshape, kh, kw, stride=1, pad=0, dil=1, out=None, accumulate=False, groups=1, bn_src=None, with_pre=False):
     """bn_src = (q, stats, gamma, beta): the convolution's input was relu(bn(q)) and this call is the ONLY contribution to its
     gradient.  When the direct kernel takes the layer, the result is then already masked (g = dx where relu(bn(q)) > 0) and the
-    call returns (g, (partials, n_tiles)) for bn_backward_pre; otherwise it returns dx alone, as without bn_src."""
+    call returns (g, (partials, n_tiles)) for bn_backward_pre; otherwise it returns dx alone, as without bn_src.
+    with_pre=True: always returns the pair, (dx, None) where the epilogue did not run that pass."""
     B, H, W, Cin = xshape
     Cout = dy.shape[-1]
     _refuse_placeholder(dy, "conv_bwd_data (fp32 output gradient)")
@@ -1128,7 +1140,7 @@ def conv_bwd_data(dy, w, xshape, kh, kw, stride=1, pad=0, dil=1, out=None, accum
         d = make_desc(xshape, ld_of(out), Cout, ld_of(dy), kh, kw, stride, pad, dil, False, groups)
         with _Timed("dgrad", flops):
             check(lib.catseg_conv2d_bwd_data(ctypes.byref(d), ptr(dy), ptr(w), ptr(out), 1 if accumulate else 0, stream()))
-    return out
+    return (out, None) if with_pre else out
 
 
 def _wgrad_h2_planes(x, dy, dgrad_blk):
@@ -1359,9 +1371,9 @@ def bn_backward_pre_planes(g, q, stats, gamma, pre, y_rec, dgamma, dbeta):
     return Planes(buf, rec, q.shape)
 
 
-def conv_bwd_data_pl(dyp, w, out, accumulate=False, bn_src=None):
+def conv_bwd_data_pl(dyp, w, out, accumulate=False, bn_src=None, with_pre=False):
     """backward-data of a trunk 3x3 convolution from the planes of dy; bn_src as in conv_bwd_data: then returns
-    (g, (partials, rows, g_record)) for bn_backward_pre(_planes)"""
+    (g, (partials, rows, g_record)) for bn_backward_pre(_planes); with_pre as in conv_bwd_data"""
     B, H, W, C = dyp.shape
     wimg = dconv3_weight_image(w, backward_data=True, h2=True)
     flops = 2.0 * B * H * W * C * C * 9
@@ -1377,7 +1389,7 @@ def conv_bwd_data_pl(dyp, w, out, accumulate=False, bn_src=None):
         return out, (part, nr, grec)
     with _Timed("dgrad_d3p", flops):
         dconv3_pl(dyp, wimg, None, out=out, accumulate=accumulate)
-    return out
+    return (out, None) if with_pre else out
 
 
 def _bn_apply(y, mean, scale, beta, residual, relu, out):
@@ -1435,12 +1447,11 @@ def concat_planes_route(ys, consumers):
     if 4 * rows * Cin >= B3_PLANE_LIMIT:
         return False
     for conv in consumers:
-        kh, kw = conv.kernel_size
-        st, pd, dl, Cout = conv.stride[0], conv.padding[0], conv.dilation[0], conv.out_channels
-        if (conv.in_channels != Cin or getattr(conv, "exact_operands", False) or getattr(conv, "stem", False) or conv.groups != 1
+        _, Cout, kh, kw, st, pd, dl, groups, bias = conv_args(conv)
+        if (conv.in_channels != Cin or getattr(conv, "exact_operands", False) or getattr(conv, "stem", False) or groups != 1
                 or conv_out_size(H, kh, st, pd, dl) != H or conv_out_size(W, kw, st, pd, dl) != W):
             return False
-        L = Layer((B, H, W, Cin), Cout, kh, kw, st, pd, dl, bias=conv.bias is not None)      # (the concatenation carries no amax record and no planes)
+        L = Layer((B, H, W, Cin), Cout, kh, kw, st, pd, dl, bias=bias is not None)      # (the concatenation carries no amax record and no planes)
         if fwd_route(L) != H2_BLOCKED or wgrad_route(L) != H2_BLOCKED:
             return False
     return True
