@@ -422,6 +422,11 @@ int catseg_bn_backward_pre(const float* g, int ldg, const float* q, int ldq, con
 /* ---- layout / pointwise helpers ---------------------------------------------------------- */
 /* img.float() NCHW (B,3,H,W) -> NHWC with 4 channels (4th = 0) : managers/OCRNet_Manager.py:86 */
 int catseg_nchw3_to_nhwc4(const float* x, float* y, int B, int H, int W, catseg_stream_t stream);
+/* the same with torchvision.transforms.Normalize folded in (models/Ensemble.py:63-65 normalises the frame for its UPerNet members only):
+ * y[b][h][w][c] = (x[b][c][h][w] - mean[c]) / stdv[c] for c < 3 -- a subtraction and a TRUE division, two roundings, bit-identical to
+ * tensor.sub_(mean).div_(std) -- and 0 for c = 3.  mean, stdv: HOST float[3] (stdv[c] != 0).  y 16-byte aligned. */
+int catseg_nchw3_to_nhwc4_norm(const float* x, float* y, int B, int H, int W, const float* mean, const float* stdv,
+                               catseg_stream_t stream);
 /* OIHW-logical/OHWI-physical 7x7x3 stem weight -> packed [O][7][8][4] and back (gradient) */
 int catseg_stem_pack_weight(const float* w_ohwi, float* packed, int O, catseg_stream_t stream);
 int catseg_stem_unpack_grad(const float* packed_grad, float* dw_ohwi, int O, catseg_stream_t stream);
@@ -576,6 +581,20 @@ int catseg_aug_color_op(uint8_t* img, int B, int H, int W, const int32_t* op, co
  *   (the 'mean' merge on the last accumulation). */
 int catseg_resize_nearest(const float* src, int lds, float* dst, int ldd, int B, int Hi, int Wi, int Ho, int Wo, int C, int flip,
                           int accumulate, float divide_by, catseg_stream_t stream);
+
+/* ---- ensemble merge (models/Ensemble.py:57-74: nn.Softmax2d per member, torch.stack, torch.mean; BaseManager.py:671-674: argmax) ---- */
+/* One launch for M members' NHWC logits [P][ld[m]] (ld[m] >= K; rows up to 68 floats are staged through LDS with 16-byte loads, wider ones --
+ * views into a concat buffer -- are read per lane).  logits, ld: HOST arrays of M device pointers / leading dimensions; the kernel receives
+ * them by value (no device-side table, no copy: the launch can be captured).  1 <= M <= 8, 1 <= K <= 64.
+ *   p_m = softmax(logits_m[pixel][0:K]) with the row maximum subtracted, fp32;
+ *   mode 0 (mean): (p_0 + p_1 + ... + p_{M-1}) / M, summed in member order, a true division; mode 1 (max): element-wise maximum;
+ *   probs (may be NULL): merged values [P][ld_probs], K <= ld_probs <= 68, columns [K, ld_probs) WRITTEN ZERO;
+ *   labels (may be NULL): int64 [P], the FIRST maximal merged class (torch.argmax, the rule of catseg_confusion_matrix), taken from the very
+ *   fp32 values stored in probs: labels == argmax(probs) bit for bit.
+ * HBM traffic (M + 1) P K 4 bytes + 8 P.  LDS: 1024 * (widest staged row | 1) bytes, opt-in beyond 64 KB as the loss kernels do.
+ * CATSEG_EINVAL before anything is launched: M or K out of range, a NULL member, ld[m] < K, bad ld_probs, both outputs NULL. */
+int catseg_ensemble_merge(const float* const* logits, const int* ld, int M, long long P, int K, int mode, float* probs, int ld_probs,
+                          int64_t* labels, catseg_stream_t stream);
 
 /* ---- metrics / optimiser ------------------------------------------------------------------ */
 /* t_get_confusion_matrix (utils/torch_utils.py:221-241): cm[pred*K + gt] += 1 (int32, K x K),

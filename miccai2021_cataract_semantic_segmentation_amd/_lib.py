@@ -151,6 +151,7 @@ _SIGS = {
     "catseg_bn_backward": (I, [P, I, P, I, P, I, P, P, P, L, I, I, P, I, P, P, P, I, I, P, SZ, P]),
     "catseg_bn_backward_pre": (I, [P, I, P, I, P, P, P, I, L, I, P, I, P, P, P, SZ, P]),
     "catseg_nchw3_to_nhwc4": (I, [P, P, I, I, I, P]),
+    "catseg_nchw3_to_nhwc4_norm": (I, [P, P, I, I, I, P, P, P]),
     "catseg_stem_pack_weight": (I, [P, P, I, P]),
     "catseg_stem_unpack_grad": (I, [P, P, I, P]),
     "catseg_axpy2d": (I, [P, I, P, I, L, I, F, I, P]),
@@ -187,6 +188,7 @@ _SIGS = {
     "catseg_focal_bwd": (I, [P, P, L, I, F, P, P, P, P]),
     "catseg_ingest_u8": (I, [P, P, I, I, I, P, P, I, I, P, P, P, P, P, P]),
     "catseg_resize_nearest": (I, [P, I, P, I, I, I, I, I, I, I, I, I, F, P]),
+    "catseg_ensemble_merge": (I, [P, P, I, L, I, I, P, I, P, P]),
     "catseg_confusion_matrix": (I, [P, P, L, I, P, P]),
     "catseg_adam_step": (I, [P, P, P, P, L, F, F, F, F, I, F, P]),
     "catseg_pconv1_supported": (I, [I, I]),

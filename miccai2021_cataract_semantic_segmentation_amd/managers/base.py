@@ -263,7 +263,7 @@ class BaseManager:
             self.model.get_intermediate = False
         if hasattr(self.model, "get_features"):
             self.model.get_features = False
-        self.load_checkpoint("best")
+        self.load_inference_weights()
         loader = DataLoader(self.valid_set, batch_size=1, shuffle=False)
         net = self.model
         if self.config["tta"]:                       # BaseManager.py:652-660: hflip x 5 scales, mean-merged
@@ -276,6 +276,10 @@ class BaseManager:
             self.model = net
         m = t_get_mean_iou(cm, self.experiment, True, rare=True)
         return tuple(float(v) for v in m)
+
+    def load_inference_weights(self):
+        """BaseManager.py:649: inference scores this run's 'best' checkpoint (EnsembleManager: its members' own, loaded at construction)"""
+        self.load_checkpoint("best")
 
     # ------------------------------------------------------------------ checkpoints (BaseManager.py:471-529)
     def save_checkpoint(self, is_best):

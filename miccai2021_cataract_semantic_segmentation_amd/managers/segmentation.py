@@ -77,6 +77,26 @@ class EncDecManager(BaseManager):
         return out[1] if isinstance(out, tuple) else out      # (get_features = False at inference: prediction only)
 
 
+class EnsembleManager(BaseManager):
+    """managers/Ensemble_Manager.py:6-16: inference with models.Ensemble built from config['graph'] = {"model": "Ensemble", "merge": ...,
+    "members": {...}}; every member loads log_path / <member's ckpt> / chkpts / chkpt_best.pt.  There is nothing to train and no
+    checkpoint of the ensemble itself (BaseManager.py:649 skips load_checkpoint for it).  With WORLD_SIZE > 1 every rank loads the
+    same checkpoints (no parameter broadcast) and the frames are sharded round-robin by _eval_pass."""
+
+    def load_model(self):
+        import pathlib
+        if self.config["mode"] != "inference":
+            raise ValueError("EnsembleManager runs mode: 'inference' only (got '{}'): an ensemble is not trained".format(self.config["mode"]))
+        cls = getattr(self.model_registry, self.config["graph"]["model"])
+        self.model = cls(config=self.config["graph"], experiment=self.experiment).to(self.device)
+        self.model.load_pretrained(pathlib.Path(self.config["log_path"]), self.device)
+        self.model.to(self.device).eval()        # (reaches every member)
+        self.grad_scale = 1.0
+
+    def load_inference_weights(self):
+        pass
+
+
 class SyntheticCataractDataset(Dataset):
     """Seeded synthetic frames with blob-structured label maps (piecewise-constant patches, a few classes
     absent, optional ignore label) — the shape of data SURVEY.md 8d asks the measurements to use."""

@@ -1616,6 +1616,18 @@ def nchw3_to_nhwc4(x):
     return y
 
 
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+def nchw3_to_nhwc4_norm(x, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """torchvision Normalize(mean, std) of an NCHW frame, written in the stem's NHWC-4 layout: ((x - mean) / std, 4th channel 0), one pass"""
+    B, C, H, W = x.shape
+    assert C == 3 and x.is_contiguous() and x.dtype == torch.float32 and len(mean) == 3 and len(std) == 3
+    y = torch.empty((B, H, W, 4), dtype=torch.float32, device=x.device)
+    check(lib.catseg_nchw3_to_nhwc4_norm(ptr(x), ptr(y), B, H, W, (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std), stream()))
+    return y
+
+
 def stem_pack_weight(w, O):
     pk = torch.empty((O, 7, 8, 4), dtype=torch.float32, device=w.device)
     check(lib.catseg_stem_pack_weight(ptr(w), ptr(pk), O, stream()))
@@ -1954,6 +1966,30 @@ def resize_nearest(src, Ho, Wo, flip=0, out=None, accumulate=False, divide_by=0.
     check(lib.catseg_resize_nearest(ptr(src), ld_of(src), ptr(out), ld_of(out), B, Hi, Wi, Ho, Wo, C, flip, 1 if accumulate else 0,
                                     divide_by, stream()))
     return out
+
+
+MERGE_MODES = {"mean": 0, "max": 1}
+
+
+def ensemble_merge(members, mode="mean", want_probs=True, want_labels=False):
+    """members: M NHWC logit tensors [B, H, W, K] (pixel strides may differ) -> softmax per member, mean / max over the members, in ONE
+    launch.  Returns (probs [B, H, W, K] NHWC or None, labels int64 [B, H, W] or None); labels = argmax of probs, first maximum."""
+    t0 = members[0]
+    B, H, W, K = t0.shape
+    n = len(members)
+    for t in members:
+        assert tuple(t.shape) == (B, H, W, K) and t.dtype == torch.float32 and t.stride(-1) == 1 and t.device == t0.device
+        assert (H == 1 or W == 1 or t.stride(1) == W * t.stride(2)) and (B == 1 or t.stride(0) == H * W * ld_of(t)), \
+            "ensemble_merge: pixels must be evenly spaced (one pixel stride over the whole tensor)"
+    Pn = B * H * W
+    probs = new_act(B, H, W, K, t0.device) if want_probs else None
+    labels = torch.empty((B, H, W), dtype=torch.int64, device=t0.device) if want_labels else None
+    ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in members])
+    lds = (ctypes.c_int * n)(*[ld_of(t) for t in members])
+    with _Timed("hbm:ensemble_merge", 4.0 * (n + (1 if want_probs else 0)) * Pn * K + (8.0 * Pn if want_labels else 0.0)):
+        check(lib.catseg_ensemble_merge(ptrs, lds, n, Pn, K, MERGE_MODES[mode], ptr(probs), ld_of(probs) if want_probs else 0, ptr(labels),
+                                        stream()))
+    return probs, labels
 
 
 def confusion_matrix(logits, labels, cm=None):
