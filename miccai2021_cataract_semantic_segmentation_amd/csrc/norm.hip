@@ -35,7 +35,15 @@ RowSplit plan_rows(long long rows, int C) {
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *(const f32x4*)p; }
 
+// The row lanes of a block are merged by one thread, one after the other.  Up to this many lanes the chain stays in fp32: every layer of
+// 32 channels or more (rpp <= 32), whose sums keep the bits they always had.  A longer chain (C <= 28: 36 to 256 lanes) merges in fp64.
+constexpr int kLaneChainF32 = 32;
+
 // per (row block, channel): shift K, s1 = sum(x-K), s2 = sum((x-K)^2)
+// K is the block's FIRST row.  A first row far from the block's other rows costs digits: s2 grows by (K - mean_b)^2 / var_b over the block's
+// M2 and the fp32 roundings of its sum come back amplified by that factor when s1^2 / n is taken off.  Measured on a single block of 64 rows
+// whose first row lies 20 sigma off: invstd 19 x the error of a two-pass fp32 evaluation (1.5e-6 of 0.65; a first row inside the data: 0.4 x),
+// the mean 3.6 x (tests/test_batchnorm_gpu.py::test_first_row_outlier).
 __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ y, int ld, long long rows, int C,
                                                          RowSplit s, float* __restrict__ part) {
   const int t = threadIdx.x;
@@ -67,9 +75,25 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict
   sh2[t] = s2;
   __syncthreads();
   if (act && rl == 0) {
-    for (int k = 1; k < s.rpp; ++k) {
-      s1 += sh1[t + k * s.tpr];
-      s2 += sh2[t + k * s.tpr];
+    if (s.rpp > kLaneChainF32) {
+      // a narrow layer (C <= 28) has up to 256 row lanes: added one after the other in fp32, that chain was the largest error of the whole
+      // reduction (5 ulp of the variance at 65 rows x 8 channels, where every lane holds one row).  Merged in fp64, they leave as fp32
+      double a1[4] = {s1[0], s1[1], s1[2], s1[3]}, a2[4] = {s2[0], s2[1], s2[2], s2[3]};
+      for (int k = 1; k < s.rpp; ++k) {
+        const f32x4 v1 = sh1[t + k * s.tpr], v2 = sh2[t + k * s.tpr];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          a1[i] += (double)v1[i];
+          a2[i] += (double)v2[i];
+        }
+      }
+      s1 = f32x4{(float)a1[0], (float)a1[1], (float)a1[2], (float)a1[3]};
+      s2 = f32x4{(float)a2[0], (float)a2[1], (float)a2[2], (float)a2[3]};
+    } else {
+      for (int k = 1; k < s.rpp; ++k) {
+        s1 += sh1[t + k * s.tpr];
+        s2 += sh2[t + k * s.tpr];
+      }
     }
     float* o = part + ((long long)blockIdx.x * 3) * C;
 #pragma unroll
@@ -179,7 +203,8 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
     // bound of the normalised output of this channel, BEFORE the pass that computes it: |fma(y - mean, scale, beta)| <= |scale| (max|y| +
     // |mean|) + |beta|, with max|y| from the convolution's epilogue (csrc/dconv3_pl.hip).  The maximum over the channels (positive floats
     // order like their bit patterns) is what catseg_bn_apply_planes derives the planes' exponent from (csrc/planes.h).
-    const float bound = (fabsf(gam * invstd) * (__uint_as_float(ym) + fabsf((float)mean)) + fabsf(bet)) * 1.001f;
+    // Evaluated in fp64 from the fp32 mean and invstd just stored, rounded once: in fp32 its five roundings put it up to ~5 ulp above the formula.
+    const float bound = (float)((fabs((double)gam * (double)invstd) * ((double)__uint_as_float(ym) + fabs((double)(float)mean)) + fabs((double)bet)) * 1.001);
     atomicMax(z_rec + CS_REC_BOUND, __float_as_uint(bound));
   }
   if (running_mean) {
@@ -372,9 +397,23 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __rest
   sh2[t] = sgx;
   __syncthreads();
   if (act && rl == 0) {
-    for (int k = 1; k < s.rpp; ++k) {
-      sg += sh1[t + k * s.tpr];
-      sgx += sh2[t + k * s.tpr];
+    if (s.rpp > kLaneChainF32) {     // (a long chain of lanes merges in fp64: bn_partial_kernel)
+      double a1[4] = {sg[0], sg[1], sg[2], sg[3]}, a2[4] = {sgx[0], sgx[1], sgx[2], sgx[3]};
+      for (int k = 1; k < s.rpp; ++k) {
+        const f32x4 v1 = sh1[t + k * s.tpr], v2 = sh2[t + k * s.tpr];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          a1[i] += (double)v1[i];
+          a2[i] += (double)v2[i];
+        }
+      }
+      sg = f32x4{(float)a1[0], (float)a1[1], (float)a1[2], (float)a1[3]};
+      sgx = f32x4{(float)a2[0], (float)a2[1], (float)a2[2], (float)a2[3]};
+    } else {
+      for (int k = 1; k < s.rpp; ++k) {
+        sg += sh1[t + k * s.tpr];
+        sgx += sh2[t + k * s.tpr];
+      }
     }
     float* o = part + ((long long)blockIdx.x * 2) * C;
     *(f32x4*)(o + c) = sg;

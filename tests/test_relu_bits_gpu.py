@@ -7,7 +7,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("shape", [(2, 12, 20, 256), (1, 5, 7, 512), (3, 33, 17, 256), (1, 1, 1, 1024), (2, 9, 11, 48), (1, 17, 30, 8), (2, 7, 5, 200)])
+# (the last two: the HRNet head width -- three channel blocks, 64 + 64 + 52 quads -- and a shape behind the 8192-block cap of the apply kernels'
+# grids, 65280 x 34 quads; tests/test_batchnorm_gpu.py checks the z-reading side of both against float64)
+@pytest.mark.parametrize("shape", [(2, 12, 20, 256), (1, 5, 7, 512), (3, 33, 17, 256), (1, 1, 1, 1024), (2, 9, 11, 48), (1, 17, 30, 8), (2, 7, 5, 200),
+                                   (1, 9, 13, 720), (2, 136, 240, 136)])
 @pytest.mark.parametrize("acc", [False, True])
 def test_mask_bits_and_backward_bit_identical(shape, acc):
     from miccai2021_cataract_semantic_segmentation_amd import ops
@@ -70,7 +73,7 @@ def test_hrnet_step_takes_the_bits_and_reproduces_the_gradients():
     assert torch.equal(res[True], res[False])
 
 
-@pytest.mark.parametrize("shape", [(2, 12, 20, 96), (1, 9, 13, 192), (2, 5, 7, 384), (1, 130, 3, 48)])
+@pytest.mark.parametrize("shape", [(2, 12, 20, 96), (1, 9, 13, 192), (2, 5, 7, 384), (1, 130, 3, 48), (1, 9, 13, 720)])
 @pytest.mark.parametrize("acc", [False, True])
 def test_planes_route_mask_bits_and_backward_bit_identical(shape, acc):
     """the trunk's residual BatchNorm on the planes route (catseg_bn_apply_planes_mask / catseg_bn_backward_planes_mask): the mask bytes are the
