@@ -88,6 +88,29 @@ __device__ __forceinline__ bool cs_quad_walk(int cpt, long long& r, int& c, long
 #endif
 static inline bool cs_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 static inline size_t cs_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// 1-D grid of 256-thread blocks over n items, at most `cap` blocks (the kernels stride over the rest)
+static inline unsigned cs_grid_256(long long n, long long cap) { return (unsigned)((n + 255) / 256 < cap ? (n + 255) / 256 : cap); }
+
+// The gather geometry every implicit-GEMM argument struct carries under the same names.  Forward (and backward-weight): the GEMM rows decode
+// over the output grid Ho x Wo and gather from the H x W input.  Mirrored (stride-1 backward-data): they decode over the input grid and gather
+// from dy.
+template <class Args>
+void cs_fill_geometry(Args& a, const catseg_conv_desc* d, bool mirrored = false) {
+  if (mirrored) { a.H = d->Ho; a.W = d->Wo; a.Ho = d->H; a.Wo = d->W; a.stride = 1; }
+  else { a.H = d->H; a.W = d->W; a.Ho = d->Ho; a.Wo = d->Wo; a.stride = d->stride; }
+  a.kw = d->kw; a.pad = d->pad; a.dil = d->dil;
+}
+
+// Claim the BatchNorm partials of a convolution epilogue whose tiles are tile_m rows tall (cs_tile_bn_partials below): true = bn_part holds
+// the ceil(M / tile_m) x 3 x Cout floats, the kernel is to write them and *tile_rows / *n_tiles describe them; false (both 0) = no fused
+// statistics, the caller runs the separate statistics pass.
+static inline bool cs_claim_bn_partials(int M, int tile_m, int Cout, const float* bn_part, size_t bn_part_floats, int* tile_rows, int* n_tiles) {
+  const int nt = (M + tile_m - 1) / tile_m;
+  *tile_rows = 0; *n_tiles = 0;
+  if (bn_part == nullptr || (size_t)nt * 3 * Cout > bn_part_floats) return false;
+  *tile_rows = tile_m; *n_tiles = nt;
+  return true;
+}
 
 // A block gets 64 KB of LDS (static + dynamic) without asking; a kernel that wants more has to opt in with hipFuncSetAttribute, up to the
 // device's opt-in maximum (hipDeviceAttributeSharedMemPerBlockOptin).  Call this for EVERY kernel of an entry point before its first launch:

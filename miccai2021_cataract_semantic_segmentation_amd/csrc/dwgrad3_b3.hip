@@ -13,7 +13,7 @@
 // 2 tile rows) is permuted so that those are 8 CONSECUTIVE pixels of one row (lane group g takes pixels 4g .. 4g+3 of row 0 as
 // k = 0..3 and of row 1 as k = 4..7; both operands use the same permutation), and the pixel row stride is an odd multiple of 32 bytes:
 // 8 consecutive rows then fall into 8 different 32-byte bank groups.
-#include "common.h"
+#include "slabs.h"
 
 // This file compiles twice (as dconv3_b3.hip does): as it is -- three bf16 planes, six products -- and through dwgrad3_f16x2.hip (-DDW_H2):
 // TWO fp16 planes, THREE products; both operands are scaled by 2^e from their producers' amax records while they are split in registers
@@ -22,7 +22,6 @@
 #define DW_NPL 2
 #define DW_MFMA __builtin_amdgcn_mfma_f32_16x16x32_f16
 #define dwgrad3_b3_kernel dwgrad3_h2_kernel
-#define dwgrad3_reduce_kernel dwgrad3_h2_reduce_kernel
 #else
 #define DW_NPL 3
 #define DW_MFMA __builtin_amdgcn_mfma_f32_16x16x32_bf16
@@ -278,30 +277,6 @@ __global__ __launch_bounds__(G::NTHR, 2) void dwgrad3_b3_kernel(const WgArgs a) 
     }
 }
 
-// dw = sum over the slabs, in a fixed order: 64 float4 columns (1 KB contiguous per slab row) x 4 slab lanes per block, each lane adds
-// every 4th slab with four independent load chains, fixed-order combine over the lanes
-__global__ __launch_bounds__(256) void dwgrad3_reduce_kernel(const float* __restrict__ slabs, float* __restrict__ dw, long long n4, int splits,
-                                                             long long slab_stride4) {
-  __shared__ f32x4 sh[4][64];
-  const int c = threadIdx.x & 63, sl = threadIdx.x >> 6;
-  const long long col = (long long)blockIdx.x * 64 + c;
-  f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
-  if (col < n4) {
-    const f32x4* p = (const f32x4*)slabs + col;
-    int k = sl;
-    for (; k + 12 < splits; k += 16) {
-      s0 += p[(long long)k * slab_stride4];
-      s1 += p[(long long)(k + 4) * slab_stride4];
-      s2 += p[(long long)(k + 8) * slab_stride4];
-      s3 += p[(long long)(k + 12) * slab_stride4];
-    }
-    for (; k < splits; k += 4) s0 += p[(long long)k * slab_stride4];
-  }
-  sh[sl][c] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (sl == 0 && col < n4) ((f32x4*)dw)[col] = (sh[0][c] + sh[1][c]) + (sh[2][c] + sh[3][c]);
-}
-
 using Wg48 = WgCfg<48, 48, 3, 1, 4>;   // one block: all 48 x 432 accumulators (wave = 48 co x 7 of the 27 (tap, ci) tiles)
 using Wg64 = WgCfg<64, 64, 1, 1, 4>;   // 64 x 64 (stage-1 bottlenecks): block = 64 co x (one filter row x 64 ci)
 using Wg96 = WgCfg<96, 48, 1, 2, 2>;   // block = 96 co x (one filter row x 48 ci); variants over (co tile, ci chunk, filter row)
@@ -395,7 +370,7 @@ int wg_run(int B, int H, int W, int C, const float* x, int ldx, const float* dy,
   else if (p.kind == 3) hipLaunchKernelGGL((dwgrad3_b3_kernel<Wg64>), dim3(p.splits, p.variants), dim3(Wg64::NTHR), 0, st, a);
   else hipLaunchKernelGGL((dwgrad3_b3_kernel<Wg96>), dim3(p.splits, p.variants), dim3(Wg96::NTHR), 0, st, a);
   const long long n4 = wel / 4;
-  hipLaunchKernelGGL(dwgrad3_reduce_kernel, dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, st, (const float*)workspace, dw, n4, p.splits, n4);
+  cs_launch_reduce_slabs4((const float*)workspace, dw, n4, p.splits, st);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
 }

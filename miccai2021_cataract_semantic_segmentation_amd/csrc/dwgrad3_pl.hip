@@ -10,6 +10,7 @@
 // Tiling, fragment addressing, product order (hl, lh, hh), slabs + fixed-order reduction: exactly dwgrad3_f16x2's -- the results are
 // bit-identical to it for equal exponents (tests/test_dwgrad3_pl_gpu.py).
 #include "planes.h"
+#include "slabs.h"
 
 extern int catseg_g_wg_blocks;      // csrc/dwgrad3_b3.hip (catseg_debug_set_dwgrad3_blocks): the 48-channel form (two blocks per CU)
 // blocks of the 96+ channel form: THREE fit a CU (46 KB of LDS, four waves).  With 768 blocks a launch uses the third slot and hides its LDS-DMA
@@ -259,29 +260,6 @@ __global__ __launch_bounds__(G::NTHR, 2) void dwgrad3_pl_kernel(const WpArgs a) 
     }
 }
 
-// dw = sum over the slabs, in a fixed order (dwgrad3_b3.hip: dwgrad3_reduce_kernel)
-__global__ __launch_bounds__(256) void dwgrad3_pl_reduce_kernel(const float* __restrict__ slabs, float* __restrict__ dw, long long n4, int splits,
-                                                                long long slab_stride4) {
-  __shared__ f32x4 sh[4][64];
-  const int c = threadIdx.x & 63, sl = threadIdx.x >> 6;
-  const long long col = (long long)blockIdx.x * 64 + c;
-  f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
-  if (col < n4) {
-    const f32x4* p = (const f32x4*)slabs + col;
-    int k = sl;
-    for (; k + 12 < splits; k += 16) {
-      s0 += p[(long long)k * slab_stride4];
-      s1 += p[(long long)(k + 4) * slab_stride4];
-      s2 += p[(long long)(k + 8) * slab_stride4];
-      s3 += p[(long long)(k + 12) * slab_stride4];
-    }
-    for (; k < splits; k += 4) s0 += p[(long long)k * slab_stride4];
-  }
-  sh[sl][c] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (sl == 0 && col < n4) ((f32x4*)dw)[col] = (sh[0][c] + sh[1][c]) + (sh[2][c] + sh[3][c]);
-}
-
 using Wp48 = WpCfg<48, 48, 3, 1, 4, 4, 2>;   // one block: all 48 x 432 accumulators, tiles 4 x 16, two image buffers of 33 KB
 // block = 96 co x (one filter row x 48 ci), tiles 2 x 16, two image buffers of 23 KB: THREE blocks fit a CU (catseg_debug_dwgrad3_pl_occupancy),
 // which is what hides the LDS-DMA round trip behind a 45-MFMA tile.  A third image buffer costs the third block: 60 -> 92 us (PMC: the same
@@ -349,7 +327,7 @@ extern "C" int catseg_dwgrad3_pl(int B, int H, int W, int C, const void* x_plane
   if (p.kind == 1) hipLaunchKernelGGL((dwgrad3_pl_kernel<Wp48>), dim3(grid), dim3(Wp48::NTHR), 0, st, a);
   else hipLaunchKernelGGL((dwgrad3_pl_kernel<Wp96>), dim3(grid), dim3(Wp96::NTHR), 0, st, a);
   const long long n4 = wel / 4;
-  hipLaunchKernelGGL(dwgrad3_pl_reduce_kernel, dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, st, (const float*)workspace, dw, n4, p.splits, n4);
+  cs_launch_reduce_slabs4((const float*)workspace, dw, n4, p.splits, st);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
 }

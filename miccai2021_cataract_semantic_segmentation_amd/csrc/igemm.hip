@@ -19,7 +19,7 @@
 //   K-major operand: [16][cols] floats, read with conflict-free ds_read_b32 (lane = column).
 // MFMA k-mapping: lane half h = lane >> 5 feeds k = 8*jj + 4*h + ii of the K-step to MFMA (jj, ii);
 // A and B use the same mapping, the sum over k is order-insensitive up to fp32 rounding.
-#include "common.h"
+#include "slabs.h"
 
 // LDS ring depth of the 128x128 and larger tiles.  A/B on one MI355X (tools/bench_conv.py, same process order):
 // 3 slots / one barrier per K-step = 124 TFLOP/s forward, 2 slots / two barriers but 4 blocks per CU = 128.
@@ -764,19 +764,7 @@ __global__ __launch_bounds__(256, igemm_min_waves(MI, NI, NARROW)) void igemm_f3
   igemm_f32_body<L_NN, MI, NI, true, NARROW>(p);
 }
 
-// out[i] = sum_s slab[s][i]  (deterministic split reduction of backward-weight partials)
-__global__ void reduce_slabs_kernel(const float* __restrict__ slabs, float* __restrict__ out, long long n4,
-                                    int splits, long long stride4) {
-  const f32x4* s = (const f32x4*)slabs;
-  f32x4* o = (f32x4*)out;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-    f32x4 a = s[i];
-    for (int k = 1; k < splits; ++k) a += s[i + k * stride4];
-    o[i] = a;
-  }
-}
-
-// the same for MANY slabs of a small tensor (direct backward-weight: up to 512 slabs of 83-330 KB): a block owns 64
+// cs_reduce_slabs_kernel (slabs.h) for MANY slabs of a small tensor (direct backward-weight: up to 512 slabs of 83-330 KB): a block owns 64
 // float4 columns, its 16 waves each add a contiguous range of slabs (8 independent loads in flight), the 16 partials
 // are combined through LDS in wave order -> fixed summation order, deterministic
 __global__ __launch_bounds__(1024) void reduce_slabs_wide_kernel(const float* __restrict__ slabs, float* __restrict__ out, long long n4,
@@ -1080,6 +1068,43 @@ Geo fwd_geo(const catseg_conv_desc* d, const float* x) {
   return g;
 }
 
+// descriptor -> arguments of the forward GEMM y[B Ho Wo][Cout] = gather(x) w^T (dense; zero_to and the epilogue fields stay with the caller)
+IgemmArgs fwd_args(const catseg_conv_desc* d, const float* x, const float* w, const float* bias, float* y) {
+  IgemmArgs a = {};
+  a.g = fwd_geo(d, x);
+  a.other = w; a.C = y; a.bias = bias;
+  a.M = a.g.rows; a.N = d->Cout; a.ldc = d->ldy;
+  if (d->stem4) { a.taps = d->kh; a.Cred = 32; a.ldo = d->kh * 32; a.tap_stride = 32; }
+  else { a.taps = d->kh * d->kw; a.Cred = d->Cin; a.ldo = a.taps * d->Cin; a.tap_stride = d->Cin; }
+  a.Cred_b = a.Cred;
+  if (!d->stem4) fill_taps(a, d->kh, d->kw, d->dil, +1, d->stride, -d->pad);
+  return a;
+}
+
+// grouped: one GEMM per group, launched as a batch of d->groups -- the batch strides walk the channel groups of x, w and y
+void group_args(IgemmArgs& a, const catseg_conv_desc* d) {
+  const int cig = d->Cin / d->groups, cog = d->Cout / d->groups;
+  a.N = cog; a.Cred = a.Cred_b = cig; a.ldo = a.taps * cig; a.tap_stride = cig;
+  a.g_bs = cig; a.o_bs = (long long)cog * a.taps * cig; a.c_bs = cog;
+}
+
+// dbias[c] = sum over the rows of dy[rows][ld], c < C, in two launches (partial sums over row blocks, then over the partials).  ld32_parts > 0
+// allows the 16-byte-load kernel for rows of 32 floats (ld == 32, C <= 32, dy 16-byte aligned) with that many blocks: `part` then has to hold
+// ld32_parts x 32 floats; otherwise colsum_parts(rows) x C floats.
+int colsum_parts(long long rows) { return (int)((rows + 1023) / 1024 < 256 ? (rows + 1023) / 1024 : 256); }
+int launch_colsum(const float* dy, int ld, long long rows, int C, float* part, int ld32_parts, float* dbias, hipStream_t st) {
+  if (ld == 32 && C <= 32 && cs_aligned16(dy) && ld32_parts > 0) {
+    hipLaunchKernelGGL(colsum_ld32_kernel, dim3(ld32_parts), dim3(256), 0, st, dy, rows, part);
+    hipLaunchKernelGGL(colsum_final_kernel, dim3(1), dim3(256), 0, st, (const float*)part, ld32_parts, 32, dbias, C);
+  } else {
+    const int gy = colsum_parts(rows);
+    hipLaunchKernelGGL(colsum_partial_kernel, dim3((C + 63) / 64, gy), dim3(256), 0, st, dy, ld, rows, C, part);
+    hipLaunchKernelGGL(colsum_final_kernel, dim3((C + 255) / 256), dim3(256), 0, st, (const float*)part, gy, C, dbias);
+  }
+  CS_LAUNCH_CHECK();
+  return CATSEG_OK;
+}
+
 }  // namespace
 
 extern "C" int catseg_debug_set_tile(int mi, int ni) {
@@ -1105,19 +1130,11 @@ extern "C" int catseg_conv2d_fwd(const catseg_conv_desc* d, const float* x, cons
   if (int e = check_desc(d)) return e;
   CS_REQUIRE(cs_aligned16(x) && cs_aligned16(w) && cs_aligned16(y), "conv fwd: pointers must be 16-byte aligned");
   CS_REQUIRE(zero_to <= d->ldy, "conv fwd: zero_to > ldy");
-  IgemmArgs a = {};
-  a.g = fwd_geo(d, x);
-  a.other = w; a.C = y; a.bias = bias;
-  a.M = a.g.rows; a.N = d->Cout; a.ldc = d->ldy;
-  if (d->stem4) { a.taps = d->kh; a.Cred = 32; a.ldo = d->kh * 32; a.tap_stride = 32; }
-  else { a.taps = d->kh * d->kw; a.Cred = d->Cin; a.ldo = a.taps * d->Cin; a.tap_stride = d->Cin; }
-  a.Cred_b = a.Cred; a.zero_to = zero_to; a.accumulate = 0;
-  if (!d->stem4) fill_taps(a, d->kh, d->kw, d->dil, +1, d->stride, -d->pad);
-  if (d->groups > 1) {  // one GEMM per group: batch strides walk the channel groups of x, w and y
+  IgemmArgs a = fwd_args(d, x, w, bias, y);
+  a.zero_to = zero_to;
+  if (d->groups > 1) {
     CS_REQUIRE(zero_to == 0, "conv fwd: zero_to is not supported with groups");
-    const int cig = d->Cin / d->groups, cog = d->Cout / d->groups;
-    a.N = cog; a.Cred = a.Cred_b = cig; a.ldo = a.taps * cig; a.tap_stride = cig;
-    a.g_bs = cig; a.o_bs = (long long)cog * a.taps * cig; a.c_bs = cog;
+    group_args(a, d);
     if (bias) { catseg_set_error("conv fwd: bias is not supported with groups"); return CATSEG_EINVAL; }
     return launch_igemm<L_NT>(a, d->groups, 1, (hipStream_t)stream);
   }
@@ -1136,23 +1153,12 @@ extern "C" int catseg_conv2d_fwd_bnstats(const catseg_conv_desc* d, const float*
   CS_REQUIRE(zero_to <= d->ldy && tile_rows && n_tiles, "conv fwd bnstats: bad args");
   *tile_rows = 0; *n_tiles = 0;
   if (d->groups > 1) return catseg_conv2d_fwd(d, x, w, bias, y, zero_to, stream);
-  IgemmArgs a = {};
-  a.g = fwd_geo(d, x);
-  a.other = w; a.C = y; a.bias = bias;
-  a.M = a.g.rows; a.N = d->Cout; a.ldc = d->ldy;
-  if (d->stem4) { a.taps = d->kh; a.Cred = 32; a.ldo = d->kh * 32; a.tap_stride = 32; }
-  else { a.taps = d->kh * d->kw; a.Cred = d->Cin; a.ldo = a.taps * d->Cin; a.tap_stride = d->Cin; }
-  a.Cred_b = a.Cred; a.zero_to = zero_to; a.accumulate = 0;
-  if (!d->stem4) fill_taps(a, d->kh, d->kw, d->dil, +1, d->stride, -d->pad);
+  IgemmArgs a = fwd_args(d, x, w, bias, y);
+  a.zero_to = zero_to;
   const int ncols = zero_to > a.N ? zero_to : a.N;
   const TilePlan pl = plan_tiles(L_NT, a.M, ncols, 1, a.g.rows, true, (long long)a.taps * a.Cred);
-  if (pl.narrow == 0 || pl.narrow == 1) {
-    const int tm = 64 * pl.mi, nt = (a.M + tm - 1) / tm;
-    if (bn_part != nullptr && (size_t)nt * 3 * d->Cout <= bn_part_floats) {
-      a.bn_part = bn_part;
-      *tile_rows = tm; *n_tiles = nt;
-    }
-  }
+  if ((pl.narrow == 0 || pl.narrow == 1) && cs_claim_bn_partials(a.M, 64 * pl.mi, d->Cout, bn_part, bn_part_floats, tile_rows, n_tiles))
+    a.bn_part = bn_part;
   return launch_igemm<L_NT>(a, 1, 1, (hipStream_t)stream, &pl);
 }
 
@@ -1162,21 +1168,12 @@ extern "C" int catseg_conv2d_fwd_fused(const catseg_conv_desc* d, const float* x
                                        const float* residual, int ldr, int relu, float* y, catseg_stream_t stream) {
   if (int e = check_desc(d)) return e;
   CS_REQUIRE(cs_aligned16(x) && cs_aligned16(w) && cs_aligned16(y), "conv fwd fused: pointers must be 16-byte aligned");
-  IgemmArgs a = {};
-  a.g = fwd_geo(d, x);
-  a.other = w; a.C = y; a.bias = bias;
-  a.M = a.g.rows; a.N = d->Cout; a.ldc = d->ldy;
-  if (d->stem4) { a.taps = d->kh; a.Cred = 32; a.ldo = d->kh * 32; a.tap_stride = 32; }
-  else { a.taps = d->kh * d->kw; a.Cred = d->Cin; a.ldo = a.taps * d->Cin; a.tap_stride = d->Cin; }
-  a.Cred_b = a.Cred;
+  IgemmArgs a = fwd_args(d, x, w, bias, y);
   a.residual = residual; a.ldr = ldr; a.relu = relu;
-  if (!d->stem4) fill_taps(a, d->kh, d->kw, d->dil, +1, d->stride, -d->pad);
   if (d->groups > 1) {
     CS_REQUIRE(residual == nullptr, "conv fwd fused: residual is not supported with groups");
-    const int cig = d->Cin / d->groups, cog = d->Cout / d->groups;
-    a.N = cog; a.Cred = a.Cred_b = cig; a.ldo = a.taps * cig; a.tap_stride = cig;
-    a.g_bs = cig; a.o_bs = (long long)cog * a.taps * cig; a.c_bs = cog;
-    a.bias_bs = cog;
+    group_args(a, d);
+    a.bias_bs = d->Cout / d->groups;
     return launch_igemm<L_NT>(a, d->groups, 1, (hipStream_t)stream);
   }
   return launch_igemm<L_NT>(a, 1, 1, (hipStream_t)stream);
@@ -1357,26 +1354,19 @@ extern "C" int catseg_conv2d_bwd_weight(const catseg_conv_desc* d, const float* 
     if (int e = launch_igemm<L_TN>(a, 1, grid_y, st, &pl)) return e;
   if (splits > 1) {
     const long long n4 = (long long)(wel / 4);
-    const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
     if (splits >= 64 && n4 <= 64 * 1024)  // many slabs of a small tensor: more parallelism across the slabs
       hipLaunchKernelGGL(reduce_slabs_wide_kernel, dim3((unsigned)((n4 + 63) / 64)), dim3(1024), 0, st, (const float*)workspace, dw, n4, splits, n4);
     else
-      hipLaunchKernelGGL(reduce_slabs_kernel, dim3(blocks), dim3(256), 0, st, (const float*)workspace, dw, n4, splits, n4);
+      cs_launch_reduce_slabs((const float*)workspace, dw, n4, splits, 2048, st);
     CS_LAUNCH_CHECK();
   }
   if (dbias) {
     float* part = (float*)((char*)workspace + (splits > 1 ? (size_t)splits * wel * 4 : 0));
     const long long rows = (long long)d->B * d->Ho * d->Wo;
-    const int gy = (int)((rows + 1023) / 1024 < 256 ? (rows + 1023) / 1024 : 256);
-    if (d->ldy == 32 && d->Cout <= 32 && cs_aligned16(dy)) {       // (the workspace holds 256 x Cout floats for the partials: 256 x 32 only then)
-      const int gn = d->Cout == 32 ? gy : (int)((long long)gy * d->Cout / 32 > 0 ? (long long)gy * d->Cout / 32 : 1);
-      hipLaunchKernelGGL(colsum_ld32_kernel, dim3(gn), dim3(256), 0, st, dy, rows, part);
-      hipLaunchKernelGGL(colsum_final_kernel, dim3(1), dim3(256), 0, st, (const float*)part, gn, 32, dbias, d->Cout);
-    } else {
-      hipLaunchKernelGGL(colsum_partial_kernel, dim3((d->Cout + 63) / 64, gy), dim3(256), 0, st, dy, d->ldy, rows, d->Cout, part);
-      hipLaunchKernelGGL(colsum_final_kernel, dim3((d->Cout + 255) / 256), dim3(256), 0, st, (const float*)part, gy, d->Cout, dbias);
-    }
-    CS_LAUNCH_CHECK();
+    // (the workspace holds 256 x Cout floats for the partials: the blocks of the 32-wide kernel shrink with Cout below 32)
+    const int gy = colsum_parts(rows);
+    const int gn = d->Cout == 32 ? gy : (int)((long long)gy * d->Cout / 32 > 0 ? (long long)gy * d->Cout / 32 : 1);
+    return launch_colsum(dy, d->ldy, rows, d->Cout, part, gn, dbias, st);
   }
   return CATSEG_OK;
 }
@@ -1386,18 +1376,8 @@ extern "C" int catseg_bias_grad(const float* dy, int ld, long long rows, int C, 
                                 catseg_stream_t stream) {
   CS_REQUIRE(dy && dbias && rows > 0 && C > 0 && ld >= C, "bias_grad: bad args");
   CS_REQUIRE(workspace && workspace_bytes >= (size_t)256 * C * 4, "bias_grad: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  const int gy = (int)((rows + 1023) / 1024 < 256 ? (rows + 1023) / 1024 : 256);
-  if (ld == 32 && C <= 32 && cs_aligned16(dy) && workspace_bytes >= (size_t)256 * 32 * 4) {
-    hipLaunchKernelGGL(colsum_ld32_kernel, dim3(gy), dim3(256), 0, st, dy, rows, (float*)workspace);
-    hipLaunchKernelGGL(colsum_final_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, gy, 32, dbias, C);
-    CS_LAUNCH_CHECK();
-    return CATSEG_OK;
-  }
-  hipLaunchKernelGGL(colsum_partial_kernel, dim3((C + 63) / 64, gy), dim3(256), 0, st, dy, ld, rows, C, (float*)workspace);
-  hipLaunchKernelGGL(colsum_final_kernel, dim3((C + 255) / 256), dim3(256), 0, st, (const float*)workspace, gy, C, dbias);
-  CS_LAUNCH_CHECK();
-  return CATSEG_OK;
+  // the 32-wide kernel writes rows of 32 partials whatever C is: only when the workspace holds 256 of them
+  return launch_colsum(dy, ld, rows, C, (float*)workspace, workspace_bytes >= (size_t)256 * 32 * 4 ? colsum_parts(rows) : 0, dbias, (hipStream_t)stream);
 }
 
 extern "C" int catseg_gemm_batched(int layout, int batch, int M, int N, int K, const float* A, int lda,

@@ -15,7 +15,7 @@
 // one MFMA deep; LDS image per operand plane: [rows][32 B], the two 16-byte chunks of a row swapped where (row >> 3) & 1
 // (conflict-free ds_read_b128 over its four 16-lane groups); global -> LDS by global_load_lds_dwordx4, double buffered
 // behind a counted vmcnt.  The im2col matrix is never built (per-row tap mask + affine tap offsets, zero page for padding).
-#include "common.h"
+#include "slabs.h"
 
 namespace {
 
@@ -1159,17 +1159,6 @@ __global__ __launch_bounds__(256, 1) void igemm_b3t_kernel(const B3TArgs p) {
     }
 }
 
-// out[i] = sum_s slab[s][i]  (fixed order: deterministic)
-__global__ void b3_reduce_slabs_kernel(const float* __restrict__ slabs, float* __restrict__ out, long long n4, int splits, long long stride4) {
-  const f32x4* s = (const f32x4*)slabs;
-  f32x4* o = (f32x4*)out;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-    f32x4 a = s[i];
-    for (int k = 1; k < splits; ++k) a += s[i + k * stride4];
-    o[i] = a;
-  }
-}
-
 const float* zero_page_b3() {
   static const float* z[64] = {};
   int dev = 0;
@@ -1199,7 +1188,6 @@ int pick_b3_tile(int N) {
   if (N <= 96) return 5;
   if (N <= 128) return 2;
   if (N <= 192) return 4;
-  if (N == 192) return 4;
   return 9;   // 256 x 256, one wave per SIMD, register-pipelined
 }
 
@@ -1235,6 +1223,35 @@ int run_b3(const B3Args& a, hipStream_t st) {
   return CATSEG_OK;
 }
 
+// descriptor -> GEMM arguments of the forward convolution y[B Ho Wo][Cout] = gather(x) w^T, from planar planes ([rows][Cin]) or blocked ones
+// ([Cin/16][rows][16]).  Index limits are NOT checked here: the planar entry points check 32-bit element offsets themselves, the blocked
+// ones rely on run_b3's bound on the plane bytes (one buffer resource per operand).
+B3Args b3_fwd_args(const catseg_conv_desc* d, const void* x_planes, const void* w_planes, const float* bias, float* y, bool blocked) {
+  B3Args a = {};
+  if (blocked) { a.blocked = 1; a.a_rows = d->B * d->H * d->W; a.w_rows = d->Cout; }
+  a.a = (const u16*)x_planes; a.lda = d->Cin; a.a_plane = (long long)d->B * d->H * d->W * d->Cin;
+  a.w = (const u16*)w_planes; a.ldw = d->kh * d->kw * d->Cin; a.w_plane = (long long)d->Cout * a.ldw;
+  a.C = y; a.ldc = d->ldy; a.bias = bias;
+  a.M = d->B * d->Ho * d->Wo; a.N = d->Cout; a.Cin = d->Cin; a.taps = d->kh * d->kw;
+  cs_fill_geometry(a, d);
+  a.sign = 1;
+  return a;
+}
+
+// the same for the stride-1 backward-data dx[B H W][Cin] (+)= gather(dy) wt^T; cop = the channel pitch of the dy planes (Cout rounded up to
+// 8 in the planar layout, to 16 in the blocked one)
+B3Args b3_bwd_data_args(const catseg_conv_desc* d, const void* dy_planes, const void* wt_planes, float* dx, int accumulate, int cop, bool blocked) {
+  B3Args a = {};
+  if (blocked) { a.blocked = 1; a.a_rows = d->B * d->Ho * d->Wo; a.w_rows = d->Cin; }
+  a.a = (const u16*)dy_planes; a.lda = cop; a.a_plane = (long long)d->B * d->Ho * d->Wo * cop;
+  a.w = (const u16*)wt_planes; a.ldw = d->kh * d->kw * cop; a.w_plane = (long long)d->Cin * a.ldw;
+  a.C = dx; a.ldc = d->ldx; a.bias = nullptr;
+  a.M = d->B * d->H * d->W; a.N = d->Cin; a.Cin = cop; a.taps = d->kh * d->kw;
+  cs_fill_geometry(a, d, true);
+  a.sign = -1; a.accumulate = accumulate;
+  return a;
+}
+
 }  // namespace
 
 extern "C" int catseg_debug_set_b3_tile(int t) {
@@ -1249,9 +1266,7 @@ extern "C" int catseg_split3(const float* x, int ld, long long rows, int C, void
   CS_REQUIRE(rows > 0 && C > 0 && ld >= C && cs_aligned16(planes), "split3: bad args");
   const int ldp = (C + 7) & ~7;
   const long long n = rows * (ldp >> 3);
-  long long blocks = (n + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(split3_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, ld, rows, C, ldp, (u16*)planes, rows * ldp);
+  hipLaunchKernelGGL(split3_kernel, dim3(cs_grid_256(n, 16384)), dim3(256), 0, (hipStream_t)stream, x, ld, rows, C, ldp, (u16*)planes, rows * ldp);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
 }
@@ -1261,9 +1276,7 @@ extern "C" int catseg_split3_weight_t(const float* w, int O, int taps, int Cin, 
   CS_REQUIRE(O > 0 && taps > 0 && Cin > 0 && cs_aligned16(planes), "split3_weight_t: bad args");
   const int ldp = (O + 7) & ~7;
   const long long n = (long long)Cin * taps * ldp;
-  long long blocks = (n + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(split3_wt_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, O, taps, Cin, ldp, (u16*)planes, n);
+  hipLaunchKernelGGL(split3_wt_kernel, dim3(cs_grid_256(n, 16384)), dim3(256), 0, (hipStream_t)stream, w, O, taps, Cin, ldp, (u16*)planes, n);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
 }
@@ -1275,13 +1288,8 @@ extern "C" int catseg_conv2d_fwd_bf16x3(const catseg_conv_desc* d, const void* x
   CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->Cin % 8 == 0 && d->kh * d->kw <= 32, "conv fwd bf16x3: needs Cin % 8 == 0, <= 32 taps, dense");
   CS_REQUIRE(cs_aligned16(x_planes) && cs_aligned16(w_planes) && cs_aligned16(y) && zero_to <= d->ldy, "conv fwd bf16x3: alignment");
   CS_REQUIRE((long long)d->B * d->H * d->W * d->Cin < (1ll << 31) && (long long)d->Cout * d->kh * d->kw * d->Cin < (1ll << 31), "conv fwd bf16x3: 32-bit offsets");
-  B3Args a = {};
-  a.a = (const u16*)x_planes; a.lda = d->Cin; a.a_plane = (long long)d->B * d->H * d->W * d->Cin;
-  a.w = (const u16*)w_planes; a.ldw = d->kh * d->kw * d->Cin; a.w_plane = (long long)d->Cout * a.ldw;
-  a.C = y; a.ldc = d->ldy; a.bias = bias;
-  a.M = d->B * d->Ho * d->Wo; a.N = d->Cout; a.Cin = d->Cin; a.taps = d->kh * d->kw;
-  a.H = d->H; a.W = d->W; a.Ho = d->Ho; a.Wo = d->Wo; a.kw = d->kw; a.stride = d->stride; a.pad = d->pad; a.dil = d->dil;
-  a.sign = 1; a.zero_to = zero_to;
+  B3Args a = b3_fwd_args(d, x_planes, w_planes, bias, y, false);
+  a.zero_to = zero_to;
   return run_b3(a, (hipStream_t)stream);
 }
 
@@ -1292,19 +1300,11 @@ extern "C" int catseg_conv2d_fwd_bf16x3_bnstats(const catseg_conv_desc* d, const
   CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->Cin % 8 == 0 && d->kh * d->kw <= 32, "conv fwd bf16x3: needs Cin % 8 == 0, <= 32 taps, dense");
   CS_REQUIRE(cs_aligned16(x_planes) && cs_aligned16(w_planes) && cs_aligned16(y) && zero_to <= d->ldy && tile_rows && n_tiles, "conv fwd bf16x3: bad args");
   CS_REQUIRE((long long)d->B * d->H * d->W * d->Cin < (1ll << 31) && (long long)d->Cout * d->kh * d->kw * d->Cin < (1ll << 31), "conv fwd bf16x3: 32-bit offsets");
-  B3Args a = {};
-  a.a = (const u16*)x_planes; a.lda = d->Cin; a.a_plane = (long long)d->B * d->H * d->W * d->Cin;
-  a.w = (const u16*)w_planes; a.ldw = d->kh * d->kw * d->Cin; a.w_plane = (long long)d->Cout * a.ldw;
-  a.C = y; a.ldc = d->ldy; a.bias = bias;
-  a.M = d->B * d->Ho * d->Wo; a.N = d->Cout; a.Cin = d->Cin; a.taps = d->kh * d->kw;
-  a.H = d->H; a.W = d->W; a.Ho = d->Ho; a.Wo = d->Wo; a.kw = d->kw; a.stride = d->stride; a.pad = d->pad; a.dil = d->dil;
-  a.sign = 1; a.zero_to = zero_to;
-  const int nt = (a.M + 255) / 256;     // every bf16x3 tile form is 256 rows tall (128 x 256 excepted: never picked by the heuristic)
-  *tile_rows = 0; *n_tiles = 0;
-  if (bn_part != nullptr && (size_t)nt * 3 * d->Cout <= bn_part_floats && pick_b3_tile(zero_to > a.N ? zero_to : a.N) != 3) {
-    a.bn_part = bn_part;
-    *tile_rows = 256; *n_tiles = nt;
-  }
+  B3Args a = b3_fwd_args(d, x_planes, w_planes, bias, y, false);
+  a.zero_to = zero_to;
+  // every bf16x3 tile form is 256 rows tall (128 x 256 excepted: never picked by the heuristic, and then nothing is claimed)
+  if (pick_b3_tile(zero_to > a.N ? zero_to : a.N) == 3) bn_part = nullptr;
+  if (cs_claim_bn_partials(a.M, 256, d->Cout, bn_part, bn_part_floats, tile_rows, n_tiles)) a.bn_part = bn_part;
   return run_b3(a, (hipStream_t)stream);
 }
 
@@ -1317,14 +1317,7 @@ extern "C" int catseg_conv2d_bwd_data_bf16x3(const catseg_conv_desc* d, const vo
   const int cop = (d->Cout + 7) & ~7;
   CS_REQUIRE((long long)d->B * d->Ho * d->Wo * cop < (1ll << 31) && (long long)d->Cin * d->kh * d->kw * cop < (1ll << 31),
              "conv bwd_data bf16x3: 32-bit offsets");
-  B3Args a = {};
-  a.a = (const u16*)dy_planes; a.lda = cop; a.a_plane = (long long)d->B * d->Ho * d->Wo * cop;
-  a.w = (const u16*)wt_planes; a.ldw = d->kh * d->kw * cop; a.w_plane = (long long)d->Cin * a.ldw;
-  a.C = dx; a.ldc = d->ldx; a.bias = nullptr;
-  a.M = d->B * d->H * d->W; a.N = d->Cin; a.Cin = cop; a.taps = d->kh * d->kw;
-  a.H = d->Ho; a.W = d->Wo; a.Ho = d->H; a.Wo = d->W; a.kw = d->kw; a.stride = 1; a.pad = d->pad; a.dil = d->dil;
-  a.sign = -1; a.accumulate = accumulate;
-  return run_b3(a, (hipStream_t)stream);
+  return run_b3(b3_bwd_data_args(d, dy_planes, wt_planes, dx, accumulate, cop, false), (hipStream_t)stream);
 }
 
 // ---- blocked operand planes (the 256 x 256 register-pipelined kernel reads whole cache lines per LDS-DMA instruction) ----------
@@ -1350,9 +1343,7 @@ extern "C" int catseg_split3_weight_blocked(const float* w, int O, int taps, int
   CS_REQUIRE(O > 0 && taps > 0 && Cin > 0 && Cin % 16 == 0 && cs_aligned16(planes), "split3_weight_blocked: needs Cin % 16 == 0");
   const int K = taps * Cin;
   const long long n = (long long)O * K;
-  long long blocks = (n + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(split3_weight_blocked_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, O, K, O, O, taps, Cin, (u16*)planes, n);
+  hipLaunchKernelGGL(split3_weight_blocked_kernel<false>, dim3(cs_grid_256(n, 16384)), dim3(256), 0, (hipStream_t)stream, w, O, K, O, O, taps, Cin, (u16*)planes, n);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
 }
@@ -1364,9 +1355,7 @@ extern "C" int catseg_split3_weight_t_blocked(const float* w, int O, int taps, i
   const int Opad = (O + 15) & ~15;
   const int K = taps * Opad;
   const long long n = (long long)Cin * K;
-  long long blocks = (n + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(split3_weight_blocked_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, Cin, K, O, Opad, taps, Cin, (u16*)planes, n);
+  hipLaunchKernelGGL(split3_weight_blocked_kernel<true>, dim3(cs_grid_256(n, 16384)), dim3(256), 0, (hipStream_t)stream, w, Cin, K, O, Opad, taps, Cin, (u16*)planes, n);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
 }
@@ -1378,23 +1367,11 @@ extern "C" int catseg_conv2d_fwd_bf16x3_blocked(const catseg_conv_desc* d, const
                                                 catseg_stream_t stream) {
   CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->Cin % 16 == 0 && d->kh * d->kw <= 32, "conv fwd bf16x3 blocked: needs Cin % 16 == 0, <= 32 taps, dense");
   CS_REQUIRE(cs_aligned16(x_planes) && cs_aligned16(w_planes) && cs_aligned16(y) && zero_to <= d->ldy, "conv fwd bf16x3 blocked: alignment");
-  B3Args a = {};
-  a.blocked = 1;
-  a.a_rows = d->B * d->H * d->W; a.w_rows = d->Cout;
-  a.a = (const u16*)x_planes; a.lda = d->Cin; a.a_plane = (long long)a.a_rows * d->Cin;
-  a.w = (const u16*)w_planes; a.ldw = d->kh * d->kw * d->Cin; a.w_plane = (long long)d->Cout * a.ldw;
-  a.C = y; a.ldc = d->ldy; a.bias = bias;
-  a.M = d->B * d->Ho * d->Wo; a.N = d->Cout; a.Cin = d->Cin; a.taps = d->kh * d->kw;
-  a.H = d->H; a.W = d->W; a.Ho = d->Ho; a.Wo = d->Wo; a.kw = d->kw; a.stride = d->stride; a.pad = d->pad; a.dil = d->dil;
-  a.sign = 1; a.zero_to = zero_to;
+  B3Args a = b3_fwd_args(d, x_planes, w_planes, bias, y, true);
+  a.zero_to = zero_to;
   if (bn_part != nullptr) {
     CS_REQUIRE(tile_rows && n_tiles, "conv fwd bf16x3 blocked: tile_rows / n_tiles");
-    const int nt = (a.M + 255) / 256;
-    *tile_rows = 0; *n_tiles = 0;
-    if ((size_t)nt * 3 * d->Cout <= bn_part_floats) {
-      a.bn_part = bn_part;
-      *tile_rows = 256; *n_tiles = nt;
-    }
+    if (cs_claim_bn_partials(a.M, 256, d->Cout, bn_part, bn_part_floats, tile_rows, n_tiles)) a.bn_part = bn_part;
   }
   return run_b3(a, (hipStream_t)stream);
 }
@@ -1405,15 +1382,7 @@ extern "C" int catseg_conv2d_fwd_fused_bf16x3_blocked(const catseg_conv_desc* d,
                                                       const float* residual, int ldr, int relu, float* y, catseg_stream_t stream) {
   CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->Cin % 16 == 0 && d->kh * d->kw <= 32, "conv fwd fused bf16x3: needs Cin % 16 == 0, <= 32 taps, dense");
   CS_REQUIRE(cs_aligned16(x_planes) && cs_aligned16(w_planes) && cs_aligned16(y) && (residual == nullptr || ldr >= d->Cout), "conv fwd fused bf16x3: bad args");
-  B3Args a = {};
-  a.blocked = 1;
-  a.a_rows = d->B * d->H * d->W; a.w_rows = d->Cout;
-  a.a = (const u16*)x_planes; a.lda = d->Cin; a.a_plane = (long long)a.a_rows * d->Cin;
-  a.w = (const u16*)w_planes; a.ldw = d->kh * d->kw * d->Cin; a.w_plane = (long long)d->Cout * a.ldw;
-  a.C = y; a.ldc = d->ldy; a.bias = bias;
-  a.M = d->B * d->Ho * d->Wo; a.N = d->Cout; a.Cin = d->Cin; a.taps = d->kh * d->kw;
-  a.H = d->H; a.W = d->W; a.Ho = d->Ho; a.Wo = d->Wo; a.kw = d->kw; a.stride = d->stride; a.pad = d->pad; a.dil = d->dil;
-  a.sign = 1;
+  B3Args a = b3_fwd_args(d, x_planes, w_planes, bias, y, true);
   a.residual = residual; a.ldr = ldr; a.relu = relu;
   return run_b3(a, (hipStream_t)stream);
 }
@@ -1424,41 +1393,12 @@ extern "C" int catseg_conv2d_bwd_data_bf16x3_blocked(const catseg_conv_desc* d, 
                                                      int accumulate, catseg_stream_t stream) {
   CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->stride == 1 && d->kh * d->kw <= 32, "conv bwd_data bf16x3 blocked: stride 1, <= 32 taps, dense");
   CS_REQUIRE(cs_aligned16(dy_planes) && cs_aligned16(wt_planes) && cs_aligned16(dx), "conv bwd_data bf16x3 blocked: alignment");
-  const int cop = (d->Cout + 15) & ~15;
-  B3Args a = {};
-  a.blocked = 1;
-  a.a_rows = d->B * d->Ho * d->Wo; a.w_rows = d->Cin;
-  a.a = (const u16*)dy_planes; a.lda = cop; a.a_plane = (long long)a.a_rows * cop;
-  a.w = (const u16*)wt_planes; a.ldw = d->kh * d->kw * cop; a.w_plane = (long long)d->Cin * a.ldw;
-  a.C = dx; a.ldc = d->ldx; a.bias = nullptr;
-  a.M = d->B * d->H * d->W; a.N = d->Cin; a.Cin = cop; a.taps = d->kh * d->kw;
-  a.H = d->Ho; a.W = d->Wo; a.Ho = d->H; a.Wo = d->W; a.kw = d->kw; a.stride = 1; a.pad = d->pad; a.dil = d->dil;
-  a.sign = -1; a.accumulate = accumulate;
-  return run_b3(a, (hipStream_t)stream);
+  return run_b3(b3_bwd_data_args(d, dy_planes, wt_planes, dx, accumulate, (d->Cout + 15) & ~15, true), (hipStream_t)stream);
 }
-
-namespace {
-int b3t_splits(int tiles, long long P) {
-  int best = 1;
-  double best_fill = 0.0;
-  for (int sp = 1; sp <= 64; ++sp) {
-    if (P / sp < 2048 && sp > 1) break;                 // at least 128 K-steps per block
-    const double rounds = (double)tiles * sp / 256.0;
-    const double fill = rounds / (double)(long long)(rounds + 0.999999);
-    if (fill > best_fill + 0.01) { best_fill = fill; best = sp; }
-  }
-  return best;
-}
-}  // namespace
 
 // workspace: split-reduction slabs (only when more than one split is planned)
 extern "C" size_t catseg_conv2d_bwd_weight_bf16x3_workspace(const catseg_conv_desc* d) {
-  if (!d) return 0;
-  const long long P = (long long)d->B * d->Ho * d->Wo;
-  const int N = d->kh * d->kw * d->Cin;
-  const int tiles = ((d->Cout + 255) / 256) * ((N + 255) / 256);
-  const int sp = b3t_splits(tiles, P);
-  return sp > 1 ? cs_align_up((size_t)sp * d->Cout * N * 4, 256) : 0;
+  return d ? cs_wgrad_plan(d).workspace_bytes : 0;
 }
 
 // dw[o][ky][kx][c] = sum_p dy[p][o] x[pix(p,ky,kx)][c] from pre-split planes: dy_planes = catseg_split3 of dy (C = Cout),
@@ -1468,33 +1408,21 @@ extern "C" int catseg_conv2d_bwd_weight_bf16x3(const catseg_conv_desc* d, const 
   CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->Cin % 8 == 0, "conv bwd_weight bf16x3: dense, Cin % 8 == 0");
   CS_REQUIRE(cs_aligned16(x_planes) && cs_aligned16(dy_planes) && cs_aligned16(dw), "conv bwd_weight bf16x3: alignment");
   CS_REQUIRE((long long)d->B * d->H * d->W * d->Cin < (1ll << 31), "conv bwd_weight bf16x3: 32-bit offsets");
-  const size_t need = catseg_conv2d_bwd_weight_bf16x3_workspace(d);
-  if (workspace_bytes < need || (need && !workspace)) {
-    catseg_set_error("conv bwd_weight bf16x3: workspace %zu < %zu", workspace_bytes, need);
+  const CsWgradPlan pl = cs_wgrad_plan(d);
+  if (workspace_bytes < pl.workspace_bytes || (pl.workspace_bytes && !workspace)) {
+    catseg_set_error("conv bwd_weight bf16x3: workspace %zu < %zu", workspace_bytes, pl.workspace_bytes);
     return CATSEG_EWORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
   B3TArgs a = {};
-  a.P = d->B * d->Ho * d->Wo;
-  a.M = d->Cout; a.Cin = d->Cin; a.taps = d->kh * d->kw; a.N = a.taps * d->Cin;
-  a.ldo = (d->Cout + 7) & ~7; a.dy = (const u16*)dy_planes; a.dy_plane = (long long)a.P * a.ldo;
-  a.ldx = d->Cin; a.x = (const u16*)x_planes; a.x_plane = (long long)d->B * d->H * d->W * d->Cin;
-  a.H = d->H; a.W = d->W; a.Ho = d->Ho; a.Wo = d->Wo; a.kw = d->kw; a.stride = d->stride; a.pad = d->pad; a.dil = d->dil;
-  const int img = d->Ho * d->Wo;
-  a.step_b = 16 / img; a.step_qy = (16 % img) / d->Wo; a.step_rx = (16 % img) % d->Wo;
-  a.tilesM = (a.M + 255) / 256; a.tilesN = (a.N + 255) / 256;
-  const int sp0 = b3t_splits(a.tilesM * a.tilesN, a.P);
-  a.rows_per_split = (int)((((long long)a.P + sp0 - 1) / sp0 + 15) / 16 * 16);
-  const int sp = (a.P + a.rows_per_split - 1) / a.rows_per_split;
-  a.ldc = a.N; a.c_split_stride = (long long)a.M * a.N;
-  a.C = sp > 1 ? (float*)workspace : dw;
+  const int sp = cs_wgrad_fill(a, d, pl, dw, workspace);
+  a.dy = (const u16*)dy_planes; a.dy_plane = (long long)a.P * a.ldo;
+  a.x = (const u16*)x_planes; a.x_plane = (long long)d->B * d->H * d->W * d->Cin;
   a.zero = zero_page_b3();
   hipLaunchKernelGGL(igemm_b3t_kernel, dim3(a.tilesM * a.tilesN * sp), dim3(256), 0, st, a);
   CS_LAUNCH_CHECK();
   if (sp > 1) {
-    const long long n4 = (long long)a.M * a.N / 4;
-    const int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-    hipLaunchKernelGGL(b3_reduce_slabs_kernel, dim3(blocks), dim3(256), 0, st, (const float*)workspace, dw, n4, sp, n4);
+    cs_launch_reduce_slabs((const float*)workspace, dw, (long long)a.M * a.N / 4, sp, 4096, st);
     CS_LAUNCH_CHECK();
   }
   return CATSEG_OK;

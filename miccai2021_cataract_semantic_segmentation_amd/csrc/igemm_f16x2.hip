@@ -16,7 +16,7 @@
 // register-pipelined forward / backward-data kernel of igemm_bf16x3.hip (blocked planes, LDS-DMA through buffer resources, one wave
 // per SIMD) with 48 MFMAs per K-step in the order  lh | hh | hl  and four 32 KB LDS slots -- and igemm_h2t_kernel, its backward-weight
 // counterpart (planar planes, transposed LDS reads).
-#include "common.h"
+#include "slabs.h"
 
 // waves per block of the forward / backward-data kernel: 8 = igemm_h2w8_kernel (two waves per SIMD, the default since round 6),
 // 4 = igemm_h2w_kernel (one 512-register wave per SIMD); bit-identical results
@@ -1115,29 +1115,6 @@ __global__ __launch_bounds__(256, 1) void igemm_h2t_kernel(const H2TArgs p) {
     }
 }
 
-// out[i] = sum_s slab[s][i]  (fixed order: deterministic)
-__global__ void h2_reduce_slabs_kernel(const float* __restrict__ slabs, float* __restrict__ out, long long n4, int splits, long long stride4) {
-  const f32x4* s = (const f32x4*)slabs;
-  f32x4* o = (f32x4*)out;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-    f32x4 a = s[i];
-    for (int k = 1; k < splits; ++k) a += s[i + k * stride4];
-    o[i] = a;
-  }
-}
-
-int h2t_splits(int tiles, long long P) {
-  int best = 1;
-  double best_fill = 0.0;
-  for (int sp = 1; sp <= 64; ++sp) {
-    if (P / sp < 2048 && sp > 1) break;                 // at least 128 K-steps per block
-    const double rounds = (double)tiles * sp / 256.0;
-    const double fill = rounds / (double)(long long)(rounds + 0.999999);
-    if (fill > best_fill + 0.01) { best_fill = fill; best = sp; }
-  }
-  return best;
-}
-
 int run_h2(H2Args a, hipStream_t st) {
   CS_REQUIRE(a.a_plane * 4 < (1ll << 32) - 64 && a.w_plane * 4 < (1ll << 32) - 64, "f16x2 blocked planes: an operand's two planes must stay below 4 GB");
   CS_REQUIRE(a.ea && a.ew, "f16x2: prescale exponents missing");
@@ -1159,9 +1136,7 @@ int run_h2(H2Args a, hipStream_t st) {
 int amax_launch(const float* x, int ld, long long rows, int C, unsigned* amax_bits, hipStream_t st) {
   if (hipMemsetAsync(amax_bits, 0, 4, st) != hipSuccess) { catseg_set_error("amax: memset failed"); return CATSEG_EHIP; }
   const long long n = rows * ((C + 3) / 4);
-  long long blocks = (n + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(amax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, ld, rows, C, amax_bits);
+  hipLaunchKernelGGL(amax_kernel, dim3(cs_grid_256(n, 2048)), dim3(256), 0, st, x, ld, rows, C, amax_bits);
   return CATSEG_OK;
 }
 
@@ -1260,9 +1235,7 @@ extern "C" int catseg_split2h_weight_blocked(const float* w, int O, int taps, in
   const int K = taps * Cin;
   if (int rc = amax_launch(w, K, O, K, ab, st)) return rc;
   const long long n = (long long)O * K;
-  long long blocks = (n + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(split2h_weight_blocked_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, w, O, K, O, O, taps, Cin, (const unsigned*)ab,
+  hipLaunchKernelGGL(split2h_weight_blocked_kernel<false>, dim3(cs_grid_256(n, 16384)), dim3(256), 0, st, w, O, K, O, O, taps, Cin, (const unsigned*)ab,
                      (u16*)planes, n, (int*)(ab + 1));
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
@@ -1278,9 +1251,7 @@ extern "C" int catseg_split2h_weight_t_blocked(const float* w, int O, int taps, 
   const int Opad = (O + 15) & ~15;
   const int K = taps * Opad;
   const long long n = (long long)Cin * K;
-  long long blocks = (n + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(split2h_weight_blocked_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, w, Cin, K, O, Opad, taps, Cin, (const unsigned*)ab,
+  hipLaunchKernelGGL(split2h_weight_blocked_kernel<true>, dim3(cs_grid_256(n, 16384)), dim3(256), 0, st, w, Cin, K, O, Opad, taps, Cin, (const unsigned*)ab,
                      (u16*)planes, n, (int*)(ab + 1));
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
@@ -1296,8 +1267,23 @@ H2Args h2_fwd_args(const catseg_conv_desc* d, const void* x_planes, const void* 
   a.ea = (const int*)x_scale + 1; a.ew = (const int*)w_scale + 1;
   a.C = y; a.ldc = d->ldy; a.bias = bias;
   a.M = d->B * d->Ho * d->Wo; a.N = d->Cout; a.Cin = d->Cin; a.taps = d->kh * d->kw;
-  a.H = d->H; a.W = d->W; a.Ho = d->Ho; a.Wo = d->Wo; a.kw = d->kw; a.stride = d->stride; a.pad = d->pad; a.dil = d->dil;
+  cs_fill_geometry(a, d);
   a.sign = 1;
+  return a;
+}
+// the stride-1 backward-data twin: dx[B H W][Cin] (+)= gather(dy) wt^T, the channel pitch of the dy planes is Cout rounded up to 16
+H2Args h2_bwd_data_args(const catseg_conv_desc* d, const void* dy_planes, const void* dy_scale, const void* wt_planes, const void* wt_scale,
+                        float* dx, int accumulate) {
+  const int cop = (d->Cout + 15) & ~15;
+  H2Args a = {};
+  a.a_rows = d->B * d->Ho * d->Wo; a.w_rows = d->Cin;
+  a.a = (const u16*)dy_planes; a.a_plane = (long long)a.a_rows * cop;
+  a.w = (const u16*)wt_planes; a.w_plane = (long long)d->Cin * d->kh * d->kw * cop;
+  a.ea = (const int*)dy_scale + 1; a.ew = (const int*)wt_scale + 1;
+  a.C = dx; a.ldc = d->ldx; a.bias = nullptr;
+  a.M = d->B * d->H * d->W; a.N = d->Cin; a.Cin = cop; a.taps = d->kh * d->kw;
+  cs_fill_geometry(a, d, true);
+  a.sign = -1; a.accumulate = accumulate;
   return a;
 }
 }  // namespace
@@ -1313,12 +1299,7 @@ extern "C" int catseg_conv2d_fwd_f16x2_blocked(const catseg_conv_desc* d, const 
   a.zero_to = zero_to;
   if (bn_part != nullptr) {
     CS_REQUIRE(tile_rows && n_tiles, "conv fwd f16x2: tile_rows / n_tiles");
-    const int nt = (a.M + 255) / 256;
-    *tile_rows = 0; *n_tiles = 0;
-    if ((size_t)nt * 3 * d->Cout <= bn_part_floats) {
-      a.bn_part = bn_part;
-      *tile_rows = 256; *n_tiles = nt;
-    }
+    if (cs_claim_bn_partials(a.M, 256, d->Cout, bn_part, bn_part_floats, tile_rows, n_tiles)) a.bn_part = bn_part;
   }
   return run_h2(a, (hipStream_t)stream);
 }
@@ -1341,27 +1322,12 @@ extern "C" int catseg_conv2d_bwd_data_f16x2_blocked(const catseg_conv_desc* d, c
                                                     const void* wt_scale, float* dx, int accumulate, catseg_stream_t stream) {
   CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->stride == 1 && d->kh * d->kw <= 32, "conv bwd_data f16x2: stride 1, <= 32 taps, dense");
   CS_REQUIRE(cs_aligned16(dy_planes) && cs_aligned16(wt_planes) && cs_aligned16(dx) && dy_scale && wt_scale, "conv bwd_data f16x2: alignment");
-  const int cop = (d->Cout + 15) & ~15;
-  H2Args a = {};
-  a.a_rows = d->B * d->Ho * d->Wo; a.w_rows = d->Cin;
-  a.a = (const u16*)dy_planes; a.a_plane = (long long)a.a_rows * cop;
-  a.w = (const u16*)wt_planes; a.w_plane = (long long)d->Cin * d->kh * d->kw * cop;
-  a.ea = (const int*)dy_scale + 1; a.ew = (const int*)wt_scale + 1;
-  a.C = dx; a.ldc = d->ldx; a.bias = nullptr;
-  a.M = d->B * d->H * d->W; a.N = d->Cin; a.Cin = cop; a.taps = d->kh * d->kw;
-  a.H = d->Ho; a.W = d->Wo; a.Ho = d->H; a.Wo = d->W; a.kw = d->kw; a.stride = 1; a.pad = d->pad; a.dil = d->dil;
-  a.sign = -1; a.accumulate = accumulate;
-  return run_h2(a, (hipStream_t)stream);
+  return run_h2(h2_bwd_data_args(d, dy_planes, dy_scale, wt_planes, wt_scale, dx, accumulate), (hipStream_t)stream);
 }
 
 // workspace: split-reduction slabs (only when more than one split is planned)
 extern "C" size_t catseg_conv2d_bwd_weight_f16x2_workspace(const catseg_conv_desc* d) {
-  if (!d) return 0;
-  const long long P = (long long)d->B * d->Ho * d->Wo;
-  const int N = d->kh * d->kw * d->Cin;
-  const int tiles = ((d->Cout + 255) / 256) * ((N + 255) / 256);
-  const int sp = h2t_splits(tiles, P);
-  return sp > 1 ? cs_align_up((size_t)sp * d->Cout * N * 4, 256) : 0;
+  return d ? cs_wgrad_plan(d).workspace_bytes : 0;
 }
 
 // dw[o][ky][kx][c] = sum_p dy[p][o] x[pix(p,ky,kx)][c] from two-plane fp16 operands in the PLANAR layout of catseg_split2h:
@@ -1374,33 +1340,21 @@ int run_h2t(const catseg_conv_desc* d, const void* x_planes, const void* x_scale
   const int cpad_x = blocked ? (d->Cin + 15) & ~15 : d->Cin, cpad_o = blocked ? (d->Cout + 15) & ~15 : (d->Cout + 7) & ~7;
   CS_REQUIRE((long long)d->B * d->H * d->W * cpad_x * 4 < (1ll << 32) - 64 && (long long)d->B * d->Ho * d->Wo * cpad_o * 4 < (1ll << 32) - 64,
              "conv bwd_weight f16x2: an operand's two planes must stay below 4 GB");
-  const size_t need = catseg_conv2d_bwd_weight_f16x2_workspace(d);
-  if (workspace_bytes < need || (need && !workspace)) {
-    catseg_set_error("conv bwd_weight f16x2: workspace %zu < %zu", workspace_bytes, need);
+  const CsWgradPlan pl = cs_wgrad_plan(d);
+  if (workspace_bytes < pl.workspace_bytes || (pl.workspace_bytes && !workspace)) {
+    catseg_set_error("conv bwd_weight f16x2: workspace %zu < %zu", workspace_bytes, pl.workspace_bytes);
     return CATSEG_EWORKSPACE;
   }
   H2TArgs a = {};
-  a.P = d->B * d->Ho * d->Wo;
-  a.M = d->Cout; a.Cin = d->Cin; a.taps = d->kh * d->kw; a.N = a.taps * d->Cin;
-  a.ldo = (d->Cout + 7) & ~7; a.dy = (const u16*)dy_planes; a.dy_plane = (long long)a.P * cpad_o;
-  a.ldx = d->Cin; a.x = (const u16*)x_planes; a.x_rows = (long long)d->B * d->H * d->W; a.x_plane = a.x_rows * cpad_x;
+  const int sp = cs_wgrad_fill(a, d, pl, dw, workspace);
+  a.dy = (const u16*)dy_planes; a.dy_plane = (long long)a.P * cpad_o;
+  a.x = (const u16*)x_planes; a.x_rows = (long long)d->B * d->H * d->W; a.x_plane = a.x_rows * cpad_x;
   a.blocked = blocked;
   a.edy = (const int*)dy_scale + 1; a.ex = (const int*)x_scale + 1;
-  a.H = d->H; a.W = d->W; a.Ho = d->Ho; a.Wo = d->Wo; a.kw = d->kw; a.stride = d->stride; a.pad = d->pad; a.dil = d->dil;
-  const int img = d->Ho * d->Wo;
-  a.step_b = 16 / img; a.step_qy = (16 % img) / d->Wo; a.step_rx = (16 % img) % d->Wo;
-  a.tilesM = (a.M + 255) / 256; a.tilesN = (a.N + 255) / 256;
-  const int sp0 = h2t_splits(a.tilesM * a.tilesN, a.P);
-  a.rows_per_split = (int)((((long long)a.P + sp0 - 1) / sp0 + 15) / 16 * 16);
-  const int sp = (a.P + a.rows_per_split - 1) / a.rows_per_split;
-  a.ldc = a.N; a.c_split_stride = (long long)a.M * a.N;
-  a.C = sp > 1 ? (float*)workspace : dw;
   hipLaunchKernelGGL(igemm_h2t_kernel, dim3(a.tilesM * a.tilesN * sp), dim3(256), 0, st, a);
   CS_LAUNCH_CHECK();
   if (sp > 1) {
-    const long long n4 = (long long)a.M * a.N / 4;
-    const int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-    hipLaunchKernelGGL(h2_reduce_slabs_kernel, dim3(blocks), dim3(256), 0, st, (const float*)workspace, dw, n4, sp, n4);
+    cs_launch_reduce_slabs((const float*)workspace, dw, (long long)a.M * a.N / 4, sp, 4096, st);
     CS_LAUNCH_CHECK();
   }
   return CATSEG_OK;

@@ -8,7 +8,7 @@
 // (halo included) and derives all filter taps from shifted windows of that LDS image:
 //   dw[o][ky][kx][c] += sum_px dy[px][o] * xs[ky][px + kx][c]
 // v_mfma_f32_16x16x4_f32, M = Cout (3 tiles of 16 per wave), N = (ky, kx, c / 16) tiles spread over the waves, k = pixel.
-// Partial sums per pixel range go to slabs that reduce_slabs_kernel (igemm.hip) adds in a fixed order: deterministic.
+// Partial sums per pixel range go to slabs that igemm.hip adds (cs_reduce_slabs_kernel / reduce_slabs_wide_kernel) in a fixed order: deterministic.
 #include "common.h"
 
 namespace {

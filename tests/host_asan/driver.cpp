@@ -18,6 +18,17 @@ static int checks = 0, failed = 0;
     if (!(cond)) { ++failed; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } \
   } while (0)
 
+// an entry point must refuse its arguments on the host: `code`, and a message that contains `sub`
+#define EXPECT_ERR(call, code, sub)                                                                            \
+  do {                                                                                                         \
+    const int rc__ = (call);                                                                                   \
+    ++checks;                                                                                                  \
+    if (rc__ != (code) || std::strstr(catseg_last_error(), (sub)) == nullptr) {                                \
+      ++failed;                                                                                                \
+      std::printf("FAILED %s:%d: %s -> %d \"%s\" (expected %d \"%s\")\n", __FILE__, __LINE__, #call, rc__, catseg_last_error(), (code), (sub)); \
+    }                                                                                                          \
+  } while (0)
+
 static catseg_conv_desc desc(int B, int H, int W, int Cin, int Cout, int k, int s, int p, int d = 1) {
   catseg_conv_desc c;
   std::memset(&c, 0, sizeof c);
@@ -95,6 +106,41 @@ int main() {
     EXPECT(catseg_debug_plan_conv(&d, 0, nullptr) != CATSEG_OK);
   }
 
+  // ---- pinned plans: workspace sizes and tile plans of the layers the split-precision paths serve, as literals (recorded from the library
+  // before the host launch code of the implicit-GEMM files was consolidated; a mismatch prints the row to paste after a DELIBERATE change)
+  {
+    struct Pin { Shape s; size_t ws_b3, ws_h2, ws_f32; int plan[3][5]; };
+    const Pin pins[] = {
+        {{8, 136, 240, 720, 512, 3, 1, 1, 1}, 716636160u, 716636160u, 66879488u, {{2, 2, 0, 1, 0}, {2, 2, 0, 1, 0}, {4, 2, 0, 5, 0}}},
+        {{8, 136, 240, 512, 512, 3, 1, 1, 1}, 603979776u, 603979776u, 66584576u, {{2, 2, 0, 1, 0}, {2, 2, 0, 1, 0}, {4, 2, 0, 7, 0}}},
+        {{8, 136, 240, 1024, 512, 1, 1, 0, 1}, 67108864u, 67108864u, 67633152u, {{2, 2, 0, 1, 0}, {2, 2, 0, 1, 0}, {4, 2, 0, 32, 0}}},
+        {{8, 68, 120, 2048, 512, 1, 1, 0, 1}, 67108864u, 67108864u, 67633152u, {{2, 2, 0, 1, 0}, {2, 2, 0, 1, 0}, {4, 2, 0, 16, 0}}},
+        {{8, 68, 120, 512, 2048, 1, 1, 0, 1}, 67108864u, 67108864u, 69206016u, {{2, 2, 0, 1, 0}, {2, 2, 0, 1, 0}, {4, 2, 0, 16, 0}}},
+        {{8, 136, 240, 48, 48, 3, 1, 1, 1}, 5308416u, 5308416u, 42350592u, {{2, 1, 1, 1, 0}, {2, 1, 1, 1, 0}, {1, 1, 0, 96, 1}}},
+        {{8, 136, 240, 48, 96, 3, 2, 1, 1}, 4976640u, 4976640u, 15857664u, {{2, 2, 1, 1, 0}, {2, 1, 1, 1, 0}, {1, 1, 0, 95, 0}}},
+        {{8, 68, 120, 96, 192, 3, 2, 1, 1}, 4644864u, 4644864u, 20766720u, {{1, 1, 0, 1, 0}, {2, 2, 1, 1, 0}, {1, 1, 0, 31, 0}}},
+        {{1, 3, 5, 8, 7, 3, 1, 1, 1}, 0u, 0u, 7168u, {{2, 1, 3, 1, 0}, {1, 1, 0, 1, 0}, {1, 1, 0, 1, 0}}},
+    };
+    for (const Pin& q : pins) {
+      const Shape& s = q.s;
+      catseg_conv_desc d = desc(s.B, s.H, s.W, s.Cin, s.Cout, s.k, s.s, s.p, s.d);
+      const size_t b3 = catseg_conv2d_bwd_weight_bf16x3_workspace(&d), h2 = catseg_conv2d_bwd_weight_f16x2_workspace(&d);
+      const size_t f32 = catseg_conv2d_bwd_weight_workspace(&d);
+      int plan[3][5];
+      bool same = b3 == q.ws_b3 && h2 == q.ws_h2 && f32 == q.ws_f32;
+      for (int op = 0; op < 3; ++op) {
+        EXPECT(catseg_debug_plan_conv(&d, op, plan[op]) == CATSEG_OK);
+        same = same && std::memcmp(plan[op], q.plan[op], sizeof plan[op]) == 0;
+      }
+      EXPECT(same);
+      if (!same) {
+        std::printf("        {{%d, %d, %d, %d, %d, %d, %d, %d, %d}, %zuu, %zuu, %zuu, {", s.B, s.H, s.W, s.Cin, s.Cout, s.k, s.s, s.p, s.d, b3, h2, f32);
+        for (int op = 0; op < 3; ++op)
+          std::printf("{%d, %d, %d, %d, %d}%s", plan[op][0], plan[op][1], plan[op][2], plan[op][3], plan[op][4], op < 2 ? ", " : "}},\n");
+      }
+    }
+  }
+
   // ---- argument validation: every call below must fail ON THE HOST, with a message, before any HIP call (there is no GPU here)
   {
     catseg_conv_desc d = desc(1, 8, 8, 6, 16, 1, 1, 0);        // Cin not a multiple of 4
@@ -120,6 +166,101 @@ int main() {
     d = desc(1, 8, 8, 8, 16, 3, 1, 1);
     d.groups = 3;                                                                           // channels not divisible by the groups
     EXPECT(catseg_conv2d_fwd(&d, p16, p16, nullptr, p16, 0, nullptr) != CATSEG_OK);
+  }
+  // ---- the split-precision convolution entry points (bf16x3: three bf16 planes; f16x2: two fp16 planes): each refuses with its own code and
+  // message -- misaligned planes, a channel count its layout cannot hold, a strided backward-data, operands past the index limits, a workspace
+  // below what its own query asks for
+  {
+    void* pl = p16;
+    void* off = (char*)p16 + 4;     // 4-byte aligned only
+    int tr = -1, ntl = -1;
+    const catseg_conv_desc ok = desc(1, 8, 8, 16, 16, 3, 1, 1);
+    const catseg_conv_desc c24 = desc(1, 8, 8, 24, 16, 3, 1, 1);       // Cin % 8 == 0, % 16 != 0
+    const catseg_conv_desc c12 = desc(1, 8, 8, 12, 16, 3, 1, 1);       // Cin % 8 != 0
+    const catseg_conv_desc s2 = desc(1, 8, 8, 16, 16, 3, 2, 1);
+    const catseg_conv_desc grp = [&] { catseg_conv_desc g = ok; g.groups = 2; return g; }();
+    const catseg_conv_desc huge = desc(64, 1024, 1024, 32, 32, 1, 1, 0);    // 2^31 elements per activation plane
+    const catseg_conv_desc big = desc(8, 1024, 1024, 96, 96, 1, 1, 0);      // < 2^31 elements, but the planes of one operand pass 4 GB
+    const catseg_conv_desc head = desc(8, 136, 240, 720, 512, 3, 1, 1);     // a layer whose backward-weight plans several splits
+
+    EXPECT_ERR(catseg_conv2d_fwd_bf16x3(&ok, off, pl, nullptr, p16, 0, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: alignment");
+    EXPECT_ERR(catseg_conv2d_fwd_bf16x3(&ok, pl, pl, nullptr, p16, 64, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: alignment");     // zero_to > ldy
+    EXPECT_ERR(catseg_conv2d_fwd_bf16x3(&c12, pl, pl, nullptr, p16, 0, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: needs Cin % 8 == 0");
+    EXPECT_ERR(catseg_conv2d_fwd_bf16x3(&grp, pl, pl, nullptr, p16, 0, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: needs Cin % 8 == 0");
+    EXPECT_ERR(catseg_conv2d_fwd_bf16x3(&huge, pl, pl, nullptr, p16, 0, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: 32-bit offsets");
+    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_bnstats(&ok, pl, off, nullptr, p16, 0, p16, 64, &tr, &ntl, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: bad args");
+    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_bnstats(&ok, pl, pl, nullptr, p16, 0, p16, 64, nullptr, &ntl, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: bad args");
+    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_bnstats(&c12, pl, pl, nullptr, p16, 0, p16, 64, &tr, &ntl, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: needs Cin % 8 == 0");
+    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_bnstats(&huge, pl, pl, nullptr, p16, 0, p16, 64, &tr, &ntl, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: 32-bit offsets");
+    EXPECT(tr == -1 && ntl == -1);                                          // a refused call leaves the tile contract untouched
+    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_blocked(&c24, pl, pl, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, nullptr), CATSEG_EINVAL,
+               "conv fwd bf16x3 blocked: needs Cin % 16 == 0");
+    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_blocked(&ok, off, pl, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, nullptr), CATSEG_EINVAL,
+               "conv fwd bf16x3 blocked: alignment");
+    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_blocked(&ok, pl, pl, nullptr, p16, 0, p16, 64, nullptr, nullptr, nullptr), CATSEG_EINVAL,
+               "conv fwd bf16x3 blocked: tile_rows / n_tiles");
+    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_blocked(&big, pl, pl, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, nullptr), CATSEG_EINVAL,
+               "bf16x3 blocked planes: an operand's three planes must stay below 4 GB");
+    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_blocked(&big, pl, pl, nullptr, p16, 0, p16, 0, &tr, &ntl, nullptr), CATSEG_EINVAL,
+               "bf16x3 blocked planes: an operand's three planes must stay below 4 GB");
+    EXPECT(tr == 0 && ntl == 0);                                            // (the partials did not fit: claimed nothing, then refused by the launcher)
+    EXPECT_ERR(catseg_conv2d_fwd_fused_bf16x3_blocked(&c24, pl, pl, nullptr, nullptr, 0, 1, p16, nullptr), CATSEG_EINVAL,
+               "conv fwd fused bf16x3: needs Cin % 16 == 0");
+    EXPECT_ERR(catseg_conv2d_fwd_fused_bf16x3_blocked(&ok, pl, pl, nullptr, p16, 8, 1, p16, nullptr), CATSEG_EINVAL, "conv fwd fused bf16x3: bad args");
+    EXPECT_ERR(catseg_conv2d_fwd_fused_bf16x3_blocked(&ok, pl, pl, nullptr, nullptr, 0, 1, (float*)off, nullptr), CATSEG_EINVAL,
+               "conv fwd fused bf16x3: bad args");
+    EXPECT_ERR(catseg_conv2d_fwd_fused_bf16x3_blocked(&big, pl, pl, nullptr, nullptr, 0, 1, p16, nullptr), CATSEG_EINVAL,
+               "bf16x3 blocked planes: an operand's three planes must stay below 4 GB");
+    EXPECT_ERR(catseg_conv2d_bwd_data_bf16x3(&s2, pl, pl, p16, 0, nullptr), CATSEG_EINVAL, "conv bwd_data bf16x3: stride 1");
+    EXPECT_ERR(catseg_conv2d_bwd_data_bf16x3(&ok, pl, off, p16, 0, nullptr), CATSEG_EINVAL, "conv bwd_data bf16x3: alignment");
+    EXPECT_ERR(catseg_conv2d_bwd_data_bf16x3(&huge, pl, pl, p16, 0, nullptr), CATSEG_EINVAL, "conv bwd_data bf16x3: 32-bit offsets");
+    EXPECT_ERR(catseg_conv2d_bwd_data_bf16x3_blocked(&s2, pl, pl, p16, 0, nullptr), CATSEG_EINVAL, "conv bwd_data bf16x3 blocked: stride 1");
+    EXPECT_ERR(catseg_conv2d_bwd_data_bf16x3_blocked(&ok, off, pl, p16, 1, nullptr), CATSEG_EINVAL, "conv bwd_data bf16x3 blocked: alignment");
+    EXPECT_ERR(catseg_conv2d_bwd_data_bf16x3_blocked(&big, pl, pl, p16, 0, nullptr), CATSEG_EINVAL,
+               "bf16x3 blocked planes: an operand's three planes must stay below 4 GB");
+    EXPECT_ERR(catseg_conv2d_bwd_weight_bf16x3(&c12, pl, pl, p16, nullptr, 0, nullptr), CATSEG_EINVAL, "conv bwd_weight bf16x3: dense, Cin % 8 == 0");
+    EXPECT_ERR(catseg_conv2d_bwd_weight_bf16x3(&ok, off, pl, p16, nullptr, 0, nullptr), CATSEG_EINVAL, "conv bwd_weight bf16x3: alignment");
+    EXPECT_ERR(catseg_conv2d_bwd_weight_bf16x3(&huge, pl, pl, p16, nullptr, 0, nullptr), CATSEG_EINVAL, "conv bwd_weight bf16x3: 32-bit offsets");
+    char msg[96];
+    std::snprintf(msg, sizeof msg, "conv bwd_weight bf16x3: workspace 256 < %zu", catseg_conv2d_bwd_weight_bf16x3_workspace(&head));
+    EXPECT(catseg_conv2d_bwd_weight_bf16x3_workspace(&head) > 256);
+    EXPECT_ERR(catseg_conv2d_bwd_weight_bf16x3(&head, pl, pl, p16, p16, 256, nullptr), CATSEG_EWORKSPACE, msg);
+    std::snprintf(msg, sizeof msg, "conv bwd_weight bf16x3: workspace %zu < %zu", (size_t)1 << 40, catseg_conv2d_bwd_weight_bf16x3_workspace(&head));
+    EXPECT_ERR(catseg_conv2d_bwd_weight_bf16x3(&head, pl, pl, p16, nullptr, (size_t)1 << 40, nullptr), CATSEG_EWORKSPACE, msg);   // null workspace
+
+    const void* sc = p16;           // {amax bits, exponent}: never read on the host
+    EXPECT_ERR(catseg_conv2d_fwd_f16x2_blocked(&c24, pl, sc, pl, sc, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, nullptr), CATSEG_EINVAL,
+               "conv fwd f16x2: needs Cin % 16 == 0");
+    EXPECT_ERR(catseg_conv2d_fwd_f16x2_blocked(&ok, off, sc, pl, sc, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, nullptr), CATSEG_EINVAL,
+               "conv fwd f16x2: alignment");
+    EXPECT_ERR(catseg_conv2d_fwd_f16x2_blocked(&ok, pl, nullptr, pl, sc, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, nullptr), CATSEG_EINVAL,
+               "conv fwd f16x2: alignment");
+    EXPECT_ERR(catseg_conv2d_fwd_f16x2_blocked(&ok, pl, sc, pl, sc, nullptr, p16, 0, p16, 64, &tr, nullptr, nullptr), CATSEG_EINVAL,
+               "conv fwd f16x2: tile_rows / n_tiles");
+    tr = ntl = -1;
+    EXPECT_ERR(catseg_conv2d_fwd_f16x2_blocked(&huge, pl, sc, pl, sc, nullptr, p16, 0, p16, (size_t)1 << 40, &tr, &ntl, nullptr), CATSEG_EINVAL,
+               "f16x2 blocked planes: an operand's two planes must stay below 4 GB");
+    EXPECT(tr == 256 && ntl == 64 * 1024 * 1024 / 256);                     // (claimed for 256-row tiles, then refused by the launcher)
+    EXPECT_ERR(catseg_conv2d_fwd_fused_f16x2_blocked(&c24, pl, sc, pl, sc, nullptr, nullptr, 0, 0, p16, nullptr), CATSEG_EINVAL,
+               "conv fwd fused f16x2: needs Cin % 16 == 0");
+    EXPECT_ERR(catseg_conv2d_fwd_fused_f16x2_blocked(&ok, pl, sc, pl, sc, nullptr, p16, 8, 0, p16, nullptr), CATSEG_EINVAL, "conv fwd fused f16x2: bad args");
+    EXPECT_ERR(catseg_conv2d_fwd_fused_f16x2_blocked(&ok, pl, sc, pl, nullptr, nullptr, nullptr, 0, 0, p16, nullptr), CATSEG_EINVAL,
+               "conv fwd fused f16x2: bad args");
+    EXPECT_ERR(catseg_conv2d_fwd_fused_f16x2_blocked(&huge, pl, sc, pl, sc, nullptr, nullptr, 0, 0, p16, nullptr), CATSEG_EINVAL,
+               "f16x2 blocked planes: an operand's two planes must stay below 4 GB");
+    EXPECT_ERR(catseg_conv2d_bwd_data_f16x2_blocked(&s2, pl, sc, pl, sc, p16, 0, nullptr), CATSEG_EINVAL, "conv bwd_data f16x2: stride 1");
+    EXPECT_ERR(catseg_conv2d_bwd_data_f16x2_blocked(&ok, pl, sc, off, sc, p16, 0, nullptr), CATSEG_EINVAL, "conv bwd_data f16x2: alignment");
+    EXPECT_ERR(catseg_conv2d_bwd_data_f16x2_blocked(&huge, pl, sc, pl, sc, p16, 1, nullptr), CATSEG_EINVAL,
+               "f16x2 blocked planes: an operand's two planes must stay below 4 GB");
+    std::snprintf(msg, sizeof msg, "conv bwd_weight f16x2: workspace 256 < %zu", catseg_conv2d_bwd_weight_f16x2_workspace(&head));
+    for (int blocked = 0; blocked < 2; ++blocked) {
+      auto wgrad = blocked ? catseg_conv2d_bwd_weight_f16x2_blocked : catseg_conv2d_bwd_weight_f16x2;
+      EXPECT_ERR(wgrad(&c12, pl, sc, pl, sc, p16, nullptr, 0, nullptr), CATSEG_EINVAL, "conv bwd_weight f16x2: dense, Cin % 8 == 0");
+      EXPECT_ERR(wgrad(&ok, pl, sc, off, sc, p16, nullptr, 0, nullptr), CATSEG_EINVAL, "conv bwd_weight f16x2: alignment");
+      EXPECT_ERR(wgrad(&ok, pl, sc, pl, nullptr, p16, nullptr, 0, nullptr), CATSEG_EINVAL, "conv bwd_weight f16x2: alignment");
+      EXPECT_ERR(wgrad(&huge, pl, sc, pl, sc, p16, nullptr, 0, nullptr), CATSEG_EINVAL, "conv bwd_weight f16x2: an operand's two planes must stay below 4 GB");
+      EXPECT_ERR(wgrad(&head, pl, sc, pl, sc, p16, p16, 256, nullptr), CATSEG_EWORKSPACE, msg);
+    }
   }
   EXPECT(catseg_lovasz_softmax(p16, (const int64_t*)p16, 100, 200, 1.0f, p16, nullptr, 0, p16, (size_t)1 << 30, nullptr) != CATSEG_OK);   // K > 64
   EXPECT(catseg_lovasz_softmax(p16, (const int64_t*)p16, 100, 8, 1.0f, p16, nullptr, 0, p16, 16, nullptr) != CATSEG_OK);                  // workspace too small

@@ -18,6 +18,9 @@ def group(name):
     m = re.search(r"igemm_f32_kernel<(\d)", name)
     if m:
         return LAY[m.group(1)]
+    if "cs_reduce_slabs" in name:
+        return "wgrad_slabs"    # slab sums of every split backward-weight family: one kernel name for all of them since csrc/slabs.h (records
+                                # from before it carry the family in the name -- h2_ / b3_reduce_slabs, dwgrad3_*_reduce -- and group as below)
     if "hf_fwd_kernel" in name or "hf_bwd_kernel" in name or "hf_reduce_kernel" in name:
         return "head"           # the class heads fused with the BatchNorm in front of them (round 6, csrc/headfuse.h): forward, both backward passes
     if "p1t_kernel" in name or "p1t_reduce" in name:
