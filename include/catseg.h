@@ -334,6 +334,31 @@ int catseg_head_backward(const float* dl, int lddl, const float* y, int ldy, con
                          float* dwh, float* dbh, void* g_record, void* y_record, void* dy_record, void* workspace, size_t workspace_bytes,
                          catseg_stream_t stream);
 
+/* nn.Dropout2d of the OCRNet heads (csrc/dropout.hip; models/OCR.py:87 interm_prediction_head[3] and :311-316 conv_bn_dropout[3] of the reference):
+ * one keep decision per (image, channel), kept channels scaled by 1 / (1 - p).
+ *   catseg_dropout2d_mask        ONE launch draws mult [B][C] (0 or 1 / (1 - p); p == 1: all zeros) and, where bits is given (C % 32 == 0), the
+ *                                packed keep bits [B][C / 32], and advances the draw counter.  state: 16 bytes of device memory {seed lo, seed hi,
+ *                                layer | rank << 16, draw counter}.  Element i = n C + c takes word i & 3 of philox4x32_10(counter = (i >> 2, draw,
+ *                                0, layer | rank << 16), key = (seed lo, seed hi)); u = (word >> 8) 2^-24; kept iff u >= p.  No host value enters
+ *                                a draw: a captured launch draws the next mask at every replay.
+ *   catseg_dropout2d_mask_fixed  the same two tables from a given 0 / 1 table keep01 [B][C]; no state
+ *   catseg_dropout2d_apply       out[row][c] = x[row][c] * mult[row / hw][c], rows = B hw NHWC pixels; C and both row strides multiples of 4;
+ *                                out may be x.  Forward and backward of the routes that do not run the fused head kernels.
+ *   catseg_head_fwd_drop / catseg_head_backward_drop   catseg_head_fwd / catseg_head_backward with the dropout between the ReLU and the
+ *                                classifier: z_d = m z feeds the logits and dWh, g = relu' m (dl Wh) everything else; bits / keep as
+ *                                catseg_dropout2d_mask wrote them (keep = 1 / (1 - p) >= 1), hw = H W of an image, C % 64 == 0 */
+int catseg_dropout2d_mask(void* state, float p, int B, int C, float* mult, unsigned* bits, catseg_stream_t stream);
+int catseg_dropout2d_mask_fixed(const float* keep01, float p, int B, int C, float* mult, unsigned* bits, catseg_stream_t stream);
+int catseg_dropout2d_apply(const float* x, int ldx, const float* mult, long long rows, int C, long long hw, float* out, int ldo,
+                           catseg_stream_t stream);
+int catseg_head_fwd_drop(const float* y, int ldy, const float* mean, const float* scale, const float* beta, const float* wh, const float* bh, int K,
+                         long long rows, int C, float* logits, int ldl, int zero_to, const unsigned* bits, long long hw, float keep,
+                         catseg_stream_t stream);
+int catseg_head_backward_drop(const float* dl, int lddl, const float* y, int ldy, const float* stats, const float* gamma, const float* beta,
+                              const float* wh, int K, long long rows, int C, void* dy_planes, void* dy_scale, float* dgamma, float* dbeta,
+                              float* dbias, float* dwh, float* dbh, void* g_record, void* y_record, void* dy_record, void* workspace,
+                              size_t workspace_bytes, const unsigned* bits, long long hw, float keep, catseg_stream_t stream);
+
 /* catseg_dwgrad3_f16x2 on producer-written planes of BOTH operands (csrc/dwgrad3_pl.hip): dw[o][ky][kx][c] = sum_px dy[px][o] x[px + tap][c]
  * for the trunk widths 48 / 96 / 192 / 384 (autograd of F.conv2d, models/HRNetv2.py:22-65); workspace = catseg_dwgrad3_pl_workspace bytes
  * (slabs of partial sums, added in a fixed order: deterministic) */

@@ -71,6 +71,11 @@ _SIGS = {
     "catseg_head_fwd": (I, [P, I, P, P, P, P, P, I, L, I, P, I, I, P]),
     "catseg_head_backward_workspace": (SZ, [L, I]),
     "catseg_head_backward": (I, [P, I, P, I, P, P, P, P, I, L, I, P, P, P, P, P, P, P, P, P, P, P, SZ, P]),
+    "catseg_head_fwd_drop": (I, [P, I, P, P, P, P, P, I, L, I, P, I, I, P, L, F, P]),
+    "catseg_head_backward_drop": (I, [P, I, P, I, P, P, P, P, I, L, I, P, P, P, P, P, P, P, P, P, P, P, SZ, P, L, F, P]),
+    "catseg_dropout2d_mask": (I, [P, F, I, I, P, P, P]),
+    "catseg_dropout2d_mask_fixed": (I, [P, F, I, I, P, P, P]),
+    "catseg_dropout2d_apply": (I, [P, I, P, L, I, L, P, I, P]),
     "catseg_maxpool2x2_fwd": (I, [P, I, P, I, P, I, I, I, I, P]),
     "catseg_maxpool2x2_bwd": (I, [P, I, P, P, I, I, I, I, I, P]),
     "catseg_bias_rows": (I, [P, P, I, L, I, P]),

@@ -29,10 +29,16 @@ typedef unsigned hf_u32x4 __attribute__((ext_vector_type(4)));
 // channels c0 + 16 h .. + 15 = 64 contiguous bytes, three chunks of loads in flight under a chunk's 16 MFMAs).  Wh lives in LDS as
 // [channel][33] (lane l31 reads class l31 of 16 channels: conflict-free), the BatchNorm constants as [3][C].
 constexpr int kHfFwdWaves = 4;      // waves per block: two blocks per CU (67.6 + 6 KB of LDS each); six waves per block measured 207 against 158 us
-__global__ __launch_bounds__(kHfFwdWaves * 64, 2) void hf_fwd_kernel(const float* __restrict__ y, int ldy, const float* __restrict__ mean,
-                                                        const float* __restrict__ scale, const float* __restrict__ beta,
-                                                        const float* __restrict__ wh, const float* __restrict__ bh, int K, long long rows, int C,
-                                                        float* __restrict__ out, int ldo, int zero_to) {
+// DROP: Dropout2d between the ReLU and the classifier (models/OCR.py:87, 316 of the reference): z_d = m[image of the row][channel] z, m = keep
+// or 0 as one packed bit per (image, channel) (csrc/dropout.hip: bits [B][C / 32]).  A 32-row group may straddle images (several where
+// H W < 32): the image index is per lane = per row.  The lane's words of a 128-channel step load one step ahead, IN FRONT of that step's ring
+// loads (a load issued between them would be waited for together with the newest y rows: the counter is in order).
+template <bool DROP>
+__device__ __forceinline__ void hf_fwd_body(const float* __restrict__ y, int ldy, const float* __restrict__ mean,
+                                            const float* __restrict__ scale, const float* __restrict__ beta,
+                                            const float* __restrict__ wh, const float* __restrict__ bh, int K, long long rows, int C,
+                                            float* __restrict__ out, int ldo, int zero_to, const unsigned* __restrict__ bits, unsigned hw,
+                                            float keep) {
   extern __shared__ __attribute__((aligned(16))) float hf_sm[];
   float* Wl = hf_sm;             // [C][33]
   float* cst = hf_sm + C * 33;   // mean[C], scale[C], beta[C]   (C % 32 == 0: 16-byte aligned)
@@ -52,6 +58,15 @@ __global__ __launch_bounds__(kHfFwdWaves * 64, 2) void hf_fwd_kernel(const float
     long long row = row0 + l31;
     if (row >= rows) row = rows - 1;   // (a clamped row's products land in accumulator rows that are not stored)
     const float* yp = y + row * ldy + 16 * h;
+    // (DROP) this row's image: its C / 32 words; words past the row's end are clamped to its last one and never used
+    const unsigned* bp = nullptr;
+    const int nwords = C >> 5;
+    unsigned bnext[4] = {0u, 0u, 0u, 0u};
+    if constexpr (DROP) {
+      bp = bits + (size_t)((unsigned)row / hw) * nwords;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) bnext[u] = bp[u < nwords ? u : nwords - 1];
+    }
     hf_f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -65,6 +80,15 @@ __global__ __launch_bounds__(kHfFwdWaves * 64, 2) void hf_fwd_kernel(const float
         for (int q = 0; q < 4; ++q) ring[u][q] = ld4(yp + 32 * u + 4 * q);
       }
     for (int c0 = 0; c0 < C; c0 += 128) {
+      unsigned bw[4] = {0u, 0u, 0u, 0u};
+      if constexpr (DROP) {
+        const int w0 = (c0 >> 5) + 4;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          bw[u] = bnext[u] >> (16 * h);
+          bnext[u] = bp[w0 + u < nwords ? w0 + u : nwords - 1];
+        }
+      }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int cc = c0 + 32 * u;
@@ -80,7 +104,8 @@ __global__ __launch_bounds__(kHfFwdWaves * 64, 2) void hf_fwd_kernel(const float
             const f32x4 m4 = *(const f32x4*)(cm + 4 * q), s4 = *(const f32x4*)(cm + C + 4 * q), b4 = *(const f32x4*)(cm + 2 * C + 4 * q);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              const float z = fmaxf(__builtin_fmaf(ring[u][q][e] - m4[e], s4[e], b4[e]), 0.f);   // = bn_affine + ReLU
+              float z = fmaxf(__builtin_fmaf(ring[u][q][e] - m4[e], s4[e], b4[e]), 0.f);   // = bn_affine + ReLU
+              if constexpr (DROP) z = ((bw[u] >> (4 * q + e)) & 1u) ? z * keep : 0.f;
               acc = __builtin_amdgcn_mfma_f32_32x32x2f32(z, wl[(4 * q + e) * 33], acc, 0, 0, 0);
             }
           }
@@ -97,6 +122,21 @@ __global__ __launch_bounds__(kHfFwdWaves * 64, 2) void hf_fwd_kernel(const float
       }
     }
   }
+}
+
+__global__ __launch_bounds__(kHfFwdWaves * 64, 2) void hf_fwd_kernel(const float* __restrict__ y, int ldy, const float* __restrict__ mean,
+                                                        const float* __restrict__ scale, const float* __restrict__ beta,
+                                                        const float* __restrict__ wh, const float* __restrict__ bh, int K, long long rows, int C,
+                                                        float* __restrict__ out, int ldo, int zero_to) {
+  hf_fwd_body<false>(y, ldy, mean, scale, beta, wh, bh, K, rows, C, out, ldo, zero_to, nullptr, 1u, 1.f);
+}
+
+__global__ __launch_bounds__(kHfFwdWaves * 64, 2) void hf_fwd_drop_kernel(const float* __restrict__ y, int ldy, const float* __restrict__ mean,
+                                                             const float* __restrict__ scale, const float* __restrict__ beta,
+                                                             const float* __restrict__ wh, const float* __restrict__ bh, int K, long long rows,
+                                                             int C, float* __restrict__ out, int ldo, int zero_to,
+                                                             const unsigned* __restrict__ bits, unsigned hw, float keep) {
+  hf_fwd_body<true>(y, ldy, mean, scale, beta, wh, bh, K, rows, C, out, ldo, zero_to, bits, hw, keep);
 }
 
 // ---- backward.  Block = NW waves; a wave owns NT 32-channel tiles (block (x, y): channels from 32 NT NW y) whose Wh fragments and BatchNorm
@@ -123,8 +163,15 @@ struct HfBwdArgs {
   float* colpart;                   // [gridDim.x][C]: column sums of dy (gradient of a bias in front of the BatchNorm), or null
 };
 
-template <bool APPLY, int NT, int NW>
-__global__ __launch_bounds__(NW * 64, 2) void hf_bwd_kernel(const HfBwdArgs p) {
+// DROP: the same bits.  g = relu' m (dl Wh) and dWh = dl^T (m z): a chunk's 32 rows x the block's NW NT words are staged through LDS with
+// its dl rows (one thread per (word, row): the image index is per row), a lane reads its 16 rows' words as four 16-byte broadcasts.
+struct HfBwdDropArgs : HfBwdArgs {
+  const unsigned* bits;             // [B][C / 32]
+  unsigned hw; float keep;          // H W of an image (rows < 2^31), the multiplier of a kept channel
+};
+
+template <bool APPLY, int NT, int NW, bool DROP = false>
+__global__ __launch_bounds__(NW * 64, 2) void hf_bwd_kernel(const std::conditional_t<DROP, HfBwdDropArgs, HfBwdArgs> p) {
   const int lane = threadIdx.x & 63, l31 = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int cw = ((int)blockIdx.y * NW + wave) * 32 * NT;
@@ -137,6 +184,7 @@ __global__ __launch_bounds__(NW * 64, 2) void hf_bwd_kernel(const HfBwdArgs p) {
   // (second pass) a tile of 32 rows x 32 channels leaves through its wave's LDS region as four 1 KB pieces (plane, 16-channel chunk), each
   // contiguous in the blocked planes [2][C / 16][rows][16].  Piece stride 1056 bytes: (plane, chunk, h) map onto eight distinct groups of 8 banks.
   __shared__ __attribute__((aligned(16))) unsigned char hf_stage[APPLY ? NW : 1][APPLY ? 4 * 1056 : 16];
+  __shared__ __attribute__((aligned(16))) unsigned mS[DROP ? 2 : 1][DROP ? NW * NT : 1][DROP ? 32 : 4];
   unsigned gm = 0, ym = 0;
   float mean_[NT], inv_[NT], sc_[NT], be_[NT], c0_[NT], c1_[NT];
   float W[NT][16];
@@ -181,6 +229,31 @@ __global__ __launch_bounds__(NW * 64, 2) void hf_bwd_kernel(const HfBwdArgs p) {
     if constexpr (!APPLY) dbl4 += v;
     if (threadIdx.x < 256) *(f32x4*)(&dlS[buf][srow * 36 + scls]) = v;
   };
+  // (DROP) thread (word = tid >> 5, row = tid & 31) of the first 32 NW NT stages that row's word of this block's channels; a row past the end
+  // reads the last row's image, a word past C / 32 is out of range = zeros
+  float keep = 1.f;
+  __amdgpu_buffer_rsrc_t rsB;
+  unsigned m_word = 0;
+  auto fetch_m = [&](long long ck) {
+    if constexpr (DROP) {
+      long long row = (ck << 5) + (threadIdx.x & 31);
+      if (row >= rows) row = rows - 1;
+      const unsigned off = ((unsigned)row / p.hw * (unsigned)(C >> 5) + m_word) * 4u;
+      return __builtin_amdgcn_raw_buffer_load_b32(rsB, (m_word < (unsigned)(C >> 5) && ck < nchunks) ? off : 0xFFFFFFF0u, 0, 0);
+    } else {
+      return 0u;
+    }
+  };
+  auto stage_m = [&](int buf, unsigned v) {
+    if constexpr (DROP) {
+      if (threadIdx.x < 32 * NW * NT) mS[buf][threadIdx.x >> 5][threadIdx.x & 31] = v;
+    }
+  };
+  if constexpr (DROP) {
+    keep = p.keep;
+    m_word = threadIdx.x < 32 * NW * NT ? (unsigned)blockIdx.y * (NW * NT) + (threadIdx.x >> 5) : 0xFFFFFFFFu;
+    rsB = __builtin_amdgcn_make_buffer_rsrc((void*)p.bits, (short)0, (int)((unsigned)((rows + p.hw - 1) / p.hw) * (unsigned)(C >> 5) * 4u), 0x00020000);
+  }
   // this lane's 16 rows (accumulator layout) of channel tile t of a chunk: rows (r & 3) + 4 h in four per-lane byte offsets, the chunk and the
   // 8 (r >> 2) rows in a wave-uniform term
   float Y[NT][16];
@@ -221,6 +294,7 @@ __global__ __launch_bounds__(NW * 64, 2) void hf_bwd_kernel(const HfBwdArgs p) {
   long long ck = blockIdx.x;
   if (ck < nchunks) {
     stage_dl(0, fetch_dl(ck));
+    stage_m(0, fetch_m(ck));
 #pragma unroll
     for (int t = 0; t < NT; ++t) load_y(Y, t, ck);
   }
@@ -233,6 +307,7 @@ __global__ __launch_bounds__(NW * 64, 2) void hf_bwd_kernel(const HfBwdArgs p) {
     const bool more = nk < nchunks;
     // the next chunk's dl and y rows start their round trips here, into a second register set; they are waited for at the END of this chunk
     const f32x4 nd = fetch_dl(nk);
+    const unsigned nm = fetch_m(nk);
     float Yn[NT][16];
 #pragma unroll
     for (int t = 0; t < NT; ++t) load_y(Yn, t, nk);      // (past the last chunk: out of range, zeros)
@@ -251,6 +326,16 @@ __global__ __launch_bounds__(NW * 64, 2) void hf_bwd_kernel(const HfBwdArgs p) {
         f32x4 a4[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) a4[q] = *(const f32x4*)(ap + 4 * q);
+        // (DROP) kept[r]: this lane's channel is kept in the image of row HF_ROW(r, h)
+        bool kept[16];
+        if constexpr (DROP) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const hf_u32x4 w4 = *(const hf_u32x4*)(&mS[buf][wave * NT + t][8 * q + 4 * h]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) kept[4 * q + e] = (w4[e] >> l31) & 1u;
+          }
+        }
         if constexpr (!APPLY) {
           // A of the dWh product: dl[row (j, h)][class l31], all sixteen reads in front of the products (issued one by one inside the chain,
           // each product waited for its own LDS round trip); B = this lane's 16 normalised values, which do not depend on dz -- the two
@@ -262,6 +347,7 @@ __global__ __launch_bounds__(NW * 64, 2) void hf_bwd_kernel(const HfBwdArgs p) {
           for (int r = 0; r < 16; ++r) {
             const float z = __builtin_fmaf(Y[t][r] - mean_[t], sc_[t], be_[t]);      // = bn_affine: the forward's expression
             zr[r] = FULL ? fmaxf(z, 0.f) : ((z > 0.f && row0 + HF_ROW(r, h) < rows) ? z : 0.f);
+            if constexpr (DROP) zr[r] = kept[r] ? zr[r] * keep : 0.f;      // (keep >= 1: still > 0 exactly where z passed the ReLU and is kept)
           }
 #pragma unroll
           for (int j = 0; j < 16; ++j) {
@@ -271,8 +357,8 @@ __global__ __launch_bounds__(NW * 64, 2) void hf_bwd_kernel(const HfBwdArgs p) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const float yy = Y[t][r];
-            const float a = acc[r];
-            const float g = zr[r] > 0.f ? a : 0.f;       // (zr > 0 <=> the element passed the ReLU and its row exists)
+            const float a = DROP ? acc[r] * keep : acc[r];
+            const float g = zr[r] > 0.f ? a : 0.f;       // (zr > 0 <=> the element passed the ReLU (and the dropout) and its row exists)
             sg[t] += g;
             sgx[t] = __builtin_fmaf(g, (yy - mean_[t]) * inv_[t], sgx[t]);
             gmf = fmaxf(gmf, fabsf(g));
@@ -286,8 +372,9 @@ __global__ __launch_bounds__(NW * 64, 2) void hf_bwd_kernel(const HfBwdArgs p) {
             const bool ok = FULL || row0 + HF_ROW(r, h) < rows;
             const float d = Y[t][r] - mean_[t];
             const float z = __builtin_fmaf(d, sc_[t], be_[t]);      // = bn_affine: the forward's expression
-            const bool on = FULL ? (z > 0.f) : ((z > 0.f) && ok);
-            const float a = acc[r];
+            bool on = FULL ? (z > 0.f) : ((z > 0.f) && ok);
+            if constexpr (DROP) on = on && kept[r];
+            const float a = DROP ? acc[r] * keep : acc[r];
             const float g = on ? a : 0.f;
             float o = __builtin_fmaf(g, sc_[t], -__builtin_fmaf(d, k1_[t], k0_[t]));
             if constexpr (!FULL) o = ok ? o : 0.f;
@@ -318,6 +405,7 @@ __global__ __launch_bounds__(NW * 64, 2) void hf_bwd_kernel(const HfBwdArgs p) {
     }
     __builtin_amdgcn_sched_barrier(0);    // (nothing below moves up into the chunk's work: the copies would drag the loads' wait with them)
     stage_dl(buf ^ 1, nd);
+    stage_m(buf ^ 1, nm);
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll

@@ -1094,26 +1094,48 @@ extern "C" int catseg_bn_backward_planes_mask(const float* dz, int lddz, const v
 // ---- the K-class classifier fused with the BatchNorm + ReLU in front of it (csrc/headfuse.h).
 // Forward: logits[rows][ldl] = relu((y - mean) * scale + beta) Wh^T + bh, columns [K, zero_to) zeroed; Wh [K][C] is the 1 x 1 convolution's
 // weight (models/OCR.py:74,97), mean / scale what catseg_bn_finalize left.  z is never written.
-extern "C" int catseg_head_fwd(const float* y, int ldy, const float* mean, const float* scale, const float* beta, const float* wh, const float* bh,
-                               int K, long long rows, int C, float* logits, int ldl, int zero_to, catseg_stream_t stream) {
+// bits != null: Dropout2d between the ReLU and the classifier (catseg_head_fwd_drop)
+static int head_fwd_launch(const float* y, int ldy, const float* mean, const float* scale, const float* beta, const float* wh, const float* bh,
+                           int K, long long rows, int C, float* logits, int ldl, int zero_to, const unsigned* bits, long long hw, float keep,
+                           catseg_stream_t stream) {
   CS_REQUIRE(rows > 0 && C >= 32 && C % 32 == 0 && C <= 512 && K >= 1 && K <= 32 && ldy % 4 == 0 && ldy >= C && ldl >= K && zero_to <= ldl &&
                  zero_to <= 32, "head forward: C a multiple of 32 up to 512, K <= 32, ld of y a multiple of 4");
   CS_REQUIRE(y && mean && scale && beta && wh && logits && cs_aligned16(y), "head forward: pointers / alignment");
   const size_t lds = (size_t)(C * 33 + 3 * C) * 4;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)hf_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (512 * 33 + 3 * 512) * 4) != hipSuccess) {
+  static bool attr_set[2] = {false, false};
+  const int drop = bits != nullptr;
+  if (!attr_set[drop]) {
+    const void* fn = drop ? (const void*)hf_fwd_drop_kernel : (const void*)hf_fwd_kernel;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (512 * 33 + 3 * 512) * 4) != hipSuccess) {
       catseg_set_error("head forward: cannot raise the dynamic LDS limit");
       return CATSEG_EHIP;
     }
-    attr_set = true;
+    attr_set[drop] = true;
   }
   const long long groups = (rows + 31) / 32;
   const long long want = (groups + kHfFwdWaves - 1) / kHfFwdWaves;
-  hipLaunchKernelGGL(hf_fwd_kernel, dim3((int)(want < 512 ? want : 512)), dim3(kHfFwdWaves * 64), lds, (hipStream_t)stream, y, ldy, mean, scale, beta, wh, bh, K,
-                     rows, C, logits, ldl, zero_to);
+  if (drop)
+    hipLaunchKernelGGL(hf_fwd_drop_kernel, dim3((int)(want < 512 ? want : 512)), dim3(kHfFwdWaves * 64), lds, (hipStream_t)stream, y, ldy, mean, scale,
+                       beta, wh, bh, K, rows, C, logits, ldl, zero_to, bits, (unsigned)hw, keep);
+  else
+    hipLaunchKernelGGL(hf_fwd_kernel, dim3((int)(want < 512 ? want : 512)), dim3(kHfFwdWaves * 64), lds, (hipStream_t)stream, y, ldy, mean, scale, beta, wh, bh, K,
+                       rows, C, logits, ldl, zero_to);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
+}
+extern "C" int catseg_head_fwd(const float* y, int ldy, const float* mean, const float* scale, const float* beta, const float* wh, const float* bh,
+                               int K, long long rows, int C, float* logits, int ldl, int zero_to, catseg_stream_t stream) {
+  return head_fwd_launch(y, ldy, mean, scale, beta, wh, bh, K, rows, C, logits, ldl, zero_to, nullptr, 1, 1.f, stream);
+}
+// the packed keep bits [rows / hw][C / 32] of catseg_dropout2d_mask and the multiplier of a kept channel: what both fused passes take
+#define CS_REQUIRE_DROP(what)                                                                                                              \
+  CS_REQUIRE(bits && hw > 0 && rows % hw == 0 && rows < (1ll << 31) && C % 64 == 0 && keep >= 1.f && keep < 3.0e38f,                            \
+             what ": Dropout2d needs the packed bits, rows a multiple of H W below 2^31, C a multiple of 64, a finite multiplier >= 1")
+extern "C" int catseg_head_fwd_drop(const float* y, int ldy, const float* mean, const float* scale, const float* beta, const float* wh,
+                                    const float* bh, int K, long long rows, int C, float* logits, int ldl, int zero_to, const unsigned* bits,
+                                    long long hw, float keep, catseg_stream_t stream) {
+  CS_REQUIRE_DROP("head forward");
+  return head_fwd_launch(y, ldy, mean, scale, beta, wh, bh, K, rows, C, logits, ldl, zero_to, bits, hw, keep, stream);
 }
 
 // Backward of the same: from the gradient of the logits dl [rows][lddl] (lddl >= 32) to
@@ -1126,10 +1148,10 @@ extern "C" size_t catseg_head_backward_workspace(long long rows, int C) {
   const size_t hb = (size_t)head_blocks(C);
   return catseg_bn_workspace(rows, C) + cs_align_up(hb * C * 4, 256) + cs_align_up(hb * 32 * C * 4, 256) + cs_align_up(hb * 32 * 4, 256);
 }
-extern "C" int catseg_head_backward(const float* dl, int lddl, const float* y, int ldy, const float* stats, const float* gamma, const float* beta,
-                                    const float* wh, int K, long long rows, int C, void* dy_planes, void* dy_scale, float* dgamma, float* dbeta,
-                                    float* dbias, float* dwh, float* dbh, void* g_record, void* y_record, void* dy_record, void* workspace,
-                                    size_t workspace_bytes, catseg_stream_t stream) {
+static int head_backward_launch(const float* dl, int lddl, const float* y, int ldy, const float* stats, const float* gamma, const float* beta,
+                                const float* wh, int K, long long rows, int C, void* dy_planes, void* dy_scale, float* dgamma, float* dbeta,
+                                float* dbias, float* dwh, float* dbh, void* g_record, void* y_record, void* dy_record, void* workspace,
+                                size_t workspace_bytes, const unsigned* bits, long long hw, float keep, catseg_stream_t stream) {
   CS_REQUIRE(rows > 0 && C >= 64 && C % 64 == 0 && C <= 512 && K >= 1 && K <= 32 && lddl >= 32 && lddl % 4 == 0 && ldy >= C,
              "head backward: C a multiple of 64 up to 512, K <= 32, ld of the logits gradient >= 32 and a multiple of 4");
   CS_REQUIRE(dl && y && stats && gamma && beta && wh && dy_planes && dy_scale && dwh && g_record && y_record && dy_record && cs_aligned16(dl) &&
@@ -1152,17 +1174,37 @@ extern "C" int catseg_head_backward(const float* dl, int lddl, const float* y, i
   float* dbs = (float*)w;
   const long long chunks = (rows + 31) / 32;
   const int nb = (int)(chunks < (long long)hb ? chunks : (long long)hb);
-  HfBwdArgs a;
+  HfBwdDropArgs a;
+  a.bits = bits; a.hw = (unsigned)hw; a.keep = keep;
   a.dl = dl; a.lddl = lddl; a.y = y; a.ldy = ldy; a.stats = stats; a.gamma = gamma; a.beta = beta; a.wh = wh; a.K = K; a.rows = rows; a.C = C;
   a.part = part; a.dws = dws; a.dbs = dbs; a.g_rec = (unsigned*)g_record; a.y_rec = (unsigned*)y_record;
   a.coef = coef; a.planes = (unsigned char*)dy_planes; a.plane_bytes = rows * C * 2; a.dy_rec = (const unsigned*)dy_record;
   a.scale = (unsigned*)dy_scale; a.colpart = dbias ? colpart : nullptr;
-  hipLaunchKernelGGL((hf_bwd_kernel<false, 1, 4>), dim3(nb, (C + 127) / 128), dim3(256), 0, st, a);
+  const HfBwdArgs& a0 = a;       // (without dropout: the kernels and arguments of before)
+  if (bits) hipLaunchKernelGGL((hf_bwd_kernel<false, 1, 4, true>), dim3(nb, (C + 127) / 128), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((hf_bwd_kernel<false, 1, 4>), dim3(nb, (C + 127) / 128), dim3(256), 0, st, a0);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(1024), 0, st, (const float*)part, nb, rows, C, dgamma, dbeta, coef,
                      (const unsigned*)a.g_rec, (const unsigned*)a.y_rec, stats, gamma, (unsigned*)dy_record);
   hipLaunchKernelGGL(hf_reduce_kernel, dim3((K * C + K + 63) / 64), dim3(256), 0, st, (const float*)dws, (const float*)dbs, nb, K, C, dwh, dbh);
-  hipLaunchKernelGGL((hf_bwd_kernel<true, 1, 4>), dim3(nb, (C + 127) / 128), dim3(256), 0, st, a);
+  if (bits) hipLaunchKernelGGL((hf_bwd_kernel<true, 1, 4, true>), dim3(nb, (C + 127) / 128), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((hf_bwd_kernel<true, 1, 4>), dim3(nb, (C + 127) / 128), dim3(256), 0, st, a0);
   if (dbias) hipLaunchKernelGGL(colsum_rows_kernel, dim3((C + 63) / 64), dim3(256), 0, st, (const float*)colpart, nb, C, dbias);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
+}
+extern "C" int catseg_head_backward(const float* dl, int lddl, const float* y, int ldy, const float* stats, const float* gamma, const float* beta,
+                                    const float* wh, int K, long long rows, int C, void* dy_planes, void* dy_scale, float* dgamma, float* dbeta,
+                                    float* dbias, float* dwh, float* dbh, void* g_record, void* y_record, void* dy_record, void* workspace,
+                                    size_t workspace_bytes, catseg_stream_t stream) {
+  return head_backward_launch(dl, lddl, y, ldy, stats, gamma, beta, wh, K, rows, C, dy_planes, dy_scale, dgamma, dbeta, dbias, dwh, dbh, g_record,
+                              y_record, dy_record, workspace, workspace_bytes, nullptr, 1, 1.f, stream);
+}
+extern "C" int catseg_head_backward_drop(const float* dl, int lddl, const float* y, int ldy, const float* stats, const float* gamma,
+                                         const float* beta, const float* wh, int K, long long rows, int C, void* dy_planes, void* dy_scale,
+                                         float* dgamma, float* dbeta, float* dbias, float* dwh, float* dbh, void* g_record, void* y_record,
+                                         void* dy_record, void* workspace, size_t workspace_bytes, const unsigned* bits, long long hw, float keep,
+                                         catseg_stream_t stream) {
+  CS_REQUIRE_DROP("head backward");
+  return head_backward_launch(dl, lddl, y, ldy, stats, gamma, beta, wh, K, rows, C, dy_planes, dy_scale, dgamma, dbeta, dbias, dwh, dbh, g_record,
+                              y_record, dy_record, workspace, workspace_bytes, bits, hw, keep, stream);
 }

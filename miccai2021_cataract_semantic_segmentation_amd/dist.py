@@ -207,17 +207,32 @@ def attach(model, bucket_bytes=None, force=None):
     """Enable data-parallel gradient averaging on an EngineNet; returns 1/world for FusedAdam.grad_scale."""
     sync = GradSync(bucket_bytes, force=force)
     model._grad_sync = sync
+    seed_dropout_by_rank(model, dist.get_rank() if dist.is_initialized() else 0)
     return 1.0 / sync.world
 
 
+def seed_dropout_by_rank(model, rank):
+    """every rank's Dropout2d layers draw with the rank in their Philox counter: independent masks on the shards of one batch (the seed itself
+    stays the shared one).  A layer that is already seeded is reseeded with its seed, its draw counter back to 0."""
+    from . import engine
+    for m in engine.dropout_layers(model):
+        m.rank = int(rank)
+        if m._seeded:
+            lo, hi = (int(v) & 0xFFFFFFFF for v in m.state[:2].tolist())
+            m.reseed(lo | hi << 32, rank)
+
+
 def broadcast_parameters(model, src=0):
-    """identical initial weights / BN running stats on every rank"""
+    """identical initial weights / BN running stats on every rank (not the Dropout2d states: those differ by rank on purpose)"""
     if not dist.is_initialized() or dist.get_world_size() == 1:
         return
+    from . import engine
+    own = {id(m.state) for m in engine.dropout_layers(model)}
     fp = model.flat()
     dist.broadcast(fp.flat, src)
     for b in model.buffers():
-        dist.broadcast(b, src)
+        if id(b) not in own:
+            dist.broadcast(b, src)
 
 
 def shard_indices(indices, rank, world, drop_last=True):

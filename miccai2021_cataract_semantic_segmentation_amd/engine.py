@@ -34,6 +34,60 @@ class BatchNorm2d(nn.BatchNorm2d):
         raise RuntimeError("engine BatchNorm2d is executed by the owning network, not called directly")
 
 
+class Dropout2d(nn.Dropout2d):
+    """nn.Dropout2d of a head (models/OCR.py:87, 311-316 of the reference), executed by conv_bn_act(drop=): no parameters, and its 16 bytes of
+    device state {seed lo, seed hi, layer | rank << 16, draw counter} are a NON-persistent buffer, so the state-dict keys stay the
+    reference's.  The mask is drawn on the device from that state and the same launch advances the counter (ops.dropout2d_mask): eager steps
+    and hipGraph replays run the same launches and draw the same masks.
+    The seed is torch.initial_seed() at the first training forward (the managers seed after construction) unless reseed() was called;
+    layer tells the dropout layers of one network apart, rank the data-parallel replicas (dist.attach).
+    fixed_mask: a test knob -- a [B, C] tensor of zeros and ones used instead of a draw (the state does not move)."""
+
+    def __init__(self, p=0.0, layer=0):
+        super().__init__(p)
+        self.layer, self.rank = int(layer), 0
+        self.register_buffer("state", torch.zeros(4, dtype=torch.int32), persistent=False)
+        self._seeded = False
+        self.fixed_mask = None
+        self.last = None            # the ops.DropMask of the last training forward
+
+    def forward(self, x):  # pragma: no cover
+        raise RuntimeError("engine Dropout2d is executed by the owning network, not called directly")
+
+    def reseed(self, seed, rank=None):
+        """(seed, rank) -> state, the draw counter back to 0"""
+        if rank is not None:
+            self.rank = int(rank)
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        words = [seed & 0xFFFFFFFF, seed >> 32, (self.layer & 0xFFFF) | (self.rank & 0xFFFF) << 16, 0]
+        host = torch.tensor([w - (1 << 32) if w >= 1 << 31 else w for w in words], dtype=torch.int32)
+        with torch.no_grad():
+            self.state.copy_(host)
+        self._seeded = True
+
+    def ensure_seeded(self):
+        if not self._seeded:
+            self.reseed(torch.initial_seed())
+
+    def active(self, cx):
+        return self.p > 0.0 and cx.train
+
+    def draw(self, B, C, device):
+        if self.fixed_mask is not None:
+            keep01 = self.fixed_mask.to(device=device, dtype=torch.float32).contiguous()
+            if tuple(keep01.shape) != (B, C):
+                raise ValueError("Dropout2d.fixed_mask must be [%d, %d], got %s" % (B, C, tuple(keep01.shape)))
+            self.last = ops.dropout2d_mask_fixed(keep01, self.p)
+        else:
+            self.ensure_seeded()
+            self.last = ops.dropout2d_mask(self.state, self.p, B, C)
+        return self.last
+
+
+def dropout_layers(module):
+    return [m for m in module.modules() if isinstance(m, Dropout2d)]
+
+
 def flush_bn_counters(module):
     for m in module.modules():
         if isinstance(m, BatchNorm2d) and m._pending_batches:
@@ -478,26 +532,26 @@ def _backward_form(inp, c, x_in, y, yrec, partials, relu, residual, out, need_dx
     return BWD_GENERIC
 
 
-def _fused_head(L, scale, head, pad_to):
+def _fused_head(L, scale, head, pad_to, dm=None):
     """BatchNorm + ReLU + the K-class 1 x 1 classifier `head` behind the head convolution whose output L.y (and batch statistics) exist:
     the normalised activation and its gradient are never written (ops.head_fwd / ops.head_backward, csrc/headfuse.h); the convolution's
     backward streams the blocked planes of dy as on the h2 form."""
     hw, K = head.weight, head.weight.shape[0]
     L.cx.claim(hw, head.bias)
     hb = head.bias.data if head.bias is not None else None
-    logits = ops.head_fwd(L.y, L.stats[:L.c.Cout], scale, L.bn.bias.data, hw.data, hb, K, max(pad_to, (K + 3) // 4 * 4))
+    logits = ops.head_fwd(L.y, L.stats[:L.c.Cout], scale, L.bn.bias.data, hw.data, hb, K, max(pad_to, (K + 3) // 4 * 4), drop=dm)
     L = L._replace(z=logits)
-    L.cx.push(lambda: _bwd_fused_head(L, head))
+    L.cx.push(lambda: _bwd_fused_head(L, head, dm))
     return logits
 
 
-def _bwd_fused_head(L, head):
+def _bwd_fused_head(L, head, dm=None):
     cx, bn = L.cx, L.bn
     dl = cx.take(L.z)
     if dl is None:
         return
     dyp, dysc = ops.head_backward(dl, L.y, L.stats, bn.weight.data, bn.bias.data, head.weight.data, cx.pgrad(head.weight), cx.pgrad(head.bias),
-                                  cx.pgrad(bn.weight), cx.pgrad(bn.bias), cx.pgrad(L.c.bias))
+                                  cx.pgrad(bn.weight), cx.pgrad(bn.bias), cx.pgrad(L.c.bias), drop=dm)
     del dl
     cx.done(head.weight, head.bias)
     _h2_tail(L, dyp, dysc)
@@ -601,12 +655,31 @@ def _bwd_generic(L, pre):
     cx.done(bn.weight, bn.bias, c.weight, c.bias)
 
 
-def conv_bn_act(cx, x, conv, bn, relu=True, residual=None, out=None, need_dx=True, private_in=False, sole_conv_out=False, head=None, z_tap=None):
+def _dropout_pass(cx, z, dm):
+    """Dropout2d as a pass of its own behind bn_apply (every form but the fused head): z_d = m z, and the tape entry dz = m dz_d"""
+    zd = ops.dropout2d_apply(z, dm)
+    if cx.record:
+        def bwd():
+            dzd = cx.take(zd)
+            if dzd is None:
+                return
+            dz, acc = cx.dest(z)
+            assert not acc, "Dropout2d is the only consumer of the activation in front of it"
+            ops.dropout2d_apply(dzd, dm, out=dz)
+        cx.push(bwd)
+    return zd
+
+
+def conv_bn_act(cx, x, conv, bn, relu=True, residual=None, out=None, need_dx=True, private_in=False, sole_conv_out=False, head=None, z_tap=None,
+                drop=None):
     """conv -> BatchNorm (batch stats in training) -> (+residual) -> (ReLU).  x NHWC (or the raw
     NCHW image for the stem).  Returns z (NHWC).
     head: a 1 x 1 classifier convolution that is the ONLY consumer of z -- the call then returns conv_bias(z, head), and in a recorded training
     pass on the head layers' route BatchNorm, ReLU and classifier run fused (_fused_head: z is never written); z_tap names z for the diagnostic
     taps where it exists.
+    drop: an engine.Dropout2d behind the ReLU (in front of `head`).  In a training forward with p > 0 it draws one mask; the fused head takes it
+    into its kernels, every other form applies it as a pass between bn_apply and what follows (z_tap then names the dropped activation, as the
+    reference's ocr_representation).  In eval mode and with p = 0 it launches nothing and its state does not move.
     private_in: the caller states that x is the output of the preceding conv_bn_act (ReLU, no residual) and has NO other consumer
     (the first half of a BasicBlock).  The backward-data kernel of this layer may then run the first pass of that BatchNorm's
     backward in its epilogue (ops.conv_bwd_data(bn_src=...)).
@@ -629,6 +702,9 @@ def conv_bn_act(cx, x, conv, bn, relu=True, residual=None, out=None, need_dx=Tru
             tap(z_tap, zf)
         return zf if head is None else conv_bias(cx, zf, head)
     partials = yrec = zrec = None
+    dropping = drop is not None and fwd == TRAIN and drop.active(cx)
+    if dropping and (not relu or residual is not None or out is not None):
+        raise NotImplementedError("conv_bn_act(drop=): Dropout2d follows BatchNorm + ReLU of a layer without residual branch or out= view")
     if fwd == TRAIN:
         # batch statistics: per-tile partial sums come out of the convolution's epilogue (no separate pass over y)
         if inp == STEM3:
@@ -640,7 +716,7 @@ def conv_bn_act(cx, x, conv, bn, relu=True, residual=None, out=None, need_dx=Tru
                                      bn_stats=FUSE_BN_STATS, train=cx.record, exact=conv.exact_operands, with_yrec=True)
         y, partials = res if FUSE_BN_STATS else (res, None)
         # planes route: the convolution streamed planes and left max|y| (yrec); then the BatchNorm's output gets planes too (exponent from a bound)
-        if (yrec is not None and partials is not None and out is None and ops.planes_ok(Cout, ops.rows_of(y))
+        if (yrec is not None and partials is not None and out is None and not dropping and ops.planes_ok(Cout, ops.rows_of(y))
                 and (residual is None or ops.amax_of(residual) is not None)):
             zrec = ops.new_amax(y.device)
         if partials is not None:
@@ -656,18 +732,21 @@ def conv_bn_act(cx, x, conv, bn, relu=True, residual=None, out=None, need_dx=Tru
         mean = bn.running_mean
         scale = ops.bn_eval_scale(bn.weight.data, bn.running_var, bn.eps)
     path = Path(inp, fwd, _backward_form(inp, c, x_in, y, yrec, partials, relu, residual, out, need_dx, head) if cx.record and fwd == TRAIN else None)
+    dm = drop.draw(y.shape[0], Cout, y.device) if dropping else None
     if path.backward == BWD_HEAD:
-        return _fused_head(_Saved(cx, path, c, bn, x, x_in, wk, y, stats, yrec, None, relu, residual, need_dx, private_in), scale, head, 32)
+        return _fused_head(_Saved(cx, path, c, bn, x, x_in, wk, y, stats, yrec, None, relu, residual, need_dx, private_in), scale, head, 32, dm)
     z = ops.bn_apply(y, mean, scale, bn.bias.data, residual, relu, out=out, planes_rec=zrec,
                      planes_only=zrec is not None and sole_conv_out and relu and residual is None,
                      want_mask=cx.record and cx.train)       # (a residual block's output: its ReLU mask as bits for the backward pass)
     if cx.record:
         if fwd != TRAIN:
             raise NotImplementedError("backward through eval-mode BatchNorm is not on the training path")
-        if relu and residual is None and out is None:
+        if relu and residual is None and out is None and dm is None:
             cx.bn_src[id(z)] = (y, stats, bn.weight.data, bn.bias.data)     # for a private_in consumer of z
         L = _Saved(cx, path, c, bn, x, x_in, wk, y, stats, yrec, z, relu, residual, need_dx, private_in)
         cx.push(lambda: _conv_bn_act_backward(L))
+    if dm is not None:
+        z = _dropout_pass(cx, z, dm)
     if z_tap is not None:
         tap(z_tap, z)
     return z if head is None else conv_bias(cx, z, head)

@@ -43,7 +43,7 @@ class SpatialOCR_Module(nn.Module):
         self.relu = nn.ReLU(inplace=True)
         self.object_context_block = ObjectAttentionBlock2D(in_channels, key_channels, scale)
         self.conv_bn_dropout = nn.Sequential(Conv2d(2 * in_channels, out_channels, 1, padding=0, bias=False),
-                                             BatchNorm2d(out_channels), self.relu, nn.Dropout2d(dropout))
+                                             BatchNorm2d(out_channels), self.relu, engine.Dropout2d(dropout, layer=1))
         self.in_channels = in_channels
 
     def run(self, cx, cat, feats, proxy, K, head=None):
@@ -52,7 +52,8 @@ class SpatialOCR_Module(nn.Module):
         C = self.in_channels
         context = self.object_context_block.run(cx, feats, proxy, K, out=cat[..., :C])
         concat_views(cx, cat, [(context, 0, C), (feats, C, 2 * C)])
-        return conv_bn_act(cx, cat, self.conv_bn_dropout[0], self.conv_bn_dropout[1], head=head, z_tap="ocr_out")
+        return conv_bn_act(cx, cat, self.conv_bn_dropout[0], self.conv_bn_dropout[1], head=head, z_tap="ocr_out",
+                           drop=self.conv_bn_dropout[3])
 
 
 class SpatialGatherModule(nn.Module):
@@ -87,8 +88,8 @@ class OCRNet(EngineNet):
         assert self.out_stride in [8, 16, 32]
         self.align_corners = True
         self.dropout = config["dropout"] if "dropout" in config else 0.0
-        if self.dropout != 0.0:
-            raise NotImplementedError("Dropout2d(p>0) is not used by the shipped configs")
+        if not 0.0 <= self.dropout <= 1.0:
+            raise ValueError("dropout probability has to be between 0 and 1, but got {}".format(self.dropout))
         self.num_classes = num_classes(experiment)
         self.get_intermediate = True
         self.relu = nn.ReLU(inplace=True)
@@ -109,7 +110,7 @@ class OCRNet(EngineNet):
             self.high_out_channels = self.low_level_channels = self.backbone.out_channels
         self.conv_high_map = nn.Sequential(Conv2d(self.high_out_channels, 512, 3, 1, 1), BatchNorm2d(512), self.relu)
         self.interm_prediction_head = nn.Sequential(
-            Conv2d(self.low_level_channels, 512, 3, 1, 1), BatchNorm2d(512), self.relu, nn.Dropout2d(self.dropout),
+            Conv2d(self.low_level_channels, 512, 3, 1, 1), BatchNorm2d(512), self.relu, engine.Dropout2d(self.dropout, layer=0),
             Conv2d(512, self.num_classes, 1, 1, 0, bias=True))
         self.spatial_gather = SpatialGatherModule(self.num_classes)
         self.spatial_ocr_head = SpatialOCR_Module(512, 256, 512, 1, self.dropout)
@@ -129,7 +130,7 @@ class OCRNet(EngineNet):
             low, high = f["low"], f["high"]
         hd = self.interm_prediction_head
         engine.tap("concat", low)
-        interm = engine.tap("interm_lowres", conv_bn_act(cx, low, hd[0], hd[1], head=hd[4]))
+        interm = engine.tap("interm_lowres", conv_bn_act(cx, low, hd[0], hd[1], head=hd[4], drop=hd[3]))
         B, h, w, _ = high.shape
         cat = torch.empty((B, h, w, 1024), dtype=torch.float32, device=x.device)
         feats = conv_bn_act(cx, high, self.conv_high_map[0], self.conv_high_map[1], out=cat[..., 512:])

@@ -1524,18 +1524,69 @@ def head_fuse_ok(y, K):
                 and 4 * rows_of(y) * C < B3_PLANE_LIMIT)
 
 
-def head_fwd(y, mean, scale, beta, wh, bh, K, ld):
-    """logits [B, H, W, K] (pixel stride ld, zero padded) = relu(bn(y)) wh^T + bh; the normalised activation is not written"""
+class DropMask:
+    """one draw of a Dropout2d layer: mult [B, C] fp32 (0 or keep = 1 / (1 - p)), bits [B, C / 32] int32 (None where C % 32 != 0)"""
+    __slots__ = ("mult", "bits", "keep")
+
+    def __init__(self, mult, bits, keep):
+        self.mult, self.bits, self.keep = mult, bits, keep
+
+
+def _drop_tables(p, B, C, device):
+    f32 = lambda v: ctypes.c_float(v).value
+    p32 = f32(p)
+    keep = f32(1.0 / f32(1.0 - p32)) if p32 < 1.0 else 0.0      # (the library's fp32 expression: both roundings are the fp32 operations')
+    mult = torch.empty((B, C), dtype=torch.float32, device=device)
+    bits = torch.empty((B, C // 32), dtype=torch.int32, device=device) if C % 32 == 0 else None
+    return p32, keep, mult, bits
+
+
+def dropout2d_mask(state, p, B, C):
+    """draws the next mask of the layer whose 16-byte device state is `state` (int32 [4]: seed lo, seed hi, layer | rank << 16, draw counter)
+    and advances the counter, in one launch (csrc/dropout.hip) -> DropMask"""
+    p32, keep, mult, bits = _drop_tables(p, B, C, state.device)
+    with _Timed("dropout2d_mask", 0.0):
+        check(lib.catseg_dropout2d_mask(ptr(state), p32, B, C, ptr(mult), ptr(bits), stream()))
+    return DropMask(mult, bits, keep)
+
+
+def dropout2d_mask_fixed(keep01, p):
+    """DropMask from a given [B, C] table of zeros and ones (fp32) instead of a draw"""
+    B, C = keep01.shape
+    p32, keep, mult, bits = _drop_tables(p, B, C, keep01.device)
+    with _Timed("dropout2d_mask", 0.0):
+        check(lib.catseg_dropout2d_mask_fixed(ptr(keep01), p32, B, C, ptr(mult), ptr(bits), stream()))
+    return DropMask(mult, bits, keep)
+
+
+def dropout2d_apply(x, drop, out=None):
+    """out = x * drop.mult[image, channel] over an NHWC tensor (out may be x): forward and backward of Dropout2d as a pass of its own"""
+    B, H, W, C = x.shape
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    with _Timed("hbm:dropout2d_apply", 4.0 * x.numel() * 2):
+        check(lib.catseg_dropout2d_apply(ptr(x), ld_of(x), ptr(drop.mult), B * H * W, C, H * W, ptr(out), ld_of(out), stream()))
+    return drop_amax(out)
+
+
+def head_fwd(y, mean, scale, beta, wh, bh, K, ld, drop=None):
+    """logits [B, H, W, K] (pixel stride ld, zero padded) = relu(bn(y)) wh^T + bh; the normalised activation is not written.
+    drop (a DropMask): Dropout2d between the ReLU and the classifier, applied in registers"""
     B, H, W, C = y.shape
     buf = torch.empty((B, H, W, ld), dtype=torch.float32, device=y.device)
     rows = rows_of(y)
+    if drop is not None:
+        with _Timed("hbm:head_fwd_drop", 4.0 * y.numel()):
+            check(lib.catseg_head_fwd_drop(ptr(y), ld_of(y), ptr(mean), ptr(scale), ptr(beta), ptr(wh), ptr(bh), K, rows, C, ptr(buf), ld, min(ld, 32),
+                                           ptr(drop.bits), H * W, drop.keep, stream()))
+        return buf[..., :K] if ld != K else buf
     with _Timed("hbm:head_fwd", 4.0 * y.numel()):
         check(lib.catseg_head_fwd(ptr(y), ld_of(y), ptr(mean), ptr(scale), ptr(beta), ptr(wh), ptr(bh), K, rows, C, ptr(buf), ld, min(ld, 32),
                                   stream()))
     return buf[..., :K] if ld != K else buf
 
 
-def head_backward(dl, y, stats, gamma, beta, wh, dwh, dbh, dgamma, dbeta, dbias=None):
+def head_backward(dl, y, stats, gamma, beta, wh, dwh, dbh, dgamma, dbeta, dbias=None, drop=None):
     """backward of head_fwd: (blocked planes of dy, their scale record) as bn_backward_h2 returns them; dwh / dbh / dgamma / dbeta / dbias written"""
     C, rows, K = y.shape[-1], rows_of(y), wh.shape[0]
     if ld_of(dl) < 32 or ld_of(dl) % 4:        # (a caller's dense gradient: the kernels read 128-byte rows)
@@ -1546,6 +1597,12 @@ def head_backward(dl, y, stats, gamma, beta, wh, dwh, dbh, dgamma, dbeta, dbias=
     scale = torch.empty(2, dtype=torch.int32, device=y.device)
     ws = workspace(lib.catseg_head_backward_workspace(rows, C), y.device)
     grec, yrec, dyrec = new_amax(y.device), new_amax(y.device), new_amax(y.device)
+    if drop is not None:
+        with _Timed("hbm:head_backward_drop", 4.0 * y.numel() * 3):
+            check(lib.catseg_head_backward_drop(ptr(dl), ld_of(dl), ptr(y), ld_of(y), ptr(stats), ptr(gamma), ptr(beta), ptr(wh), K, rows, C, ptr(blk),
+                                                ptr(scale), ptr(dgamma), ptr(dbeta), ptr(dbias), ptr(dwh), ptr(dbh), ptr(grec), ptr(yrec), ptr(dyrec),
+                                                ptr(ws), ws.numel(), ptr(drop.bits), y.shape[1] * y.shape[2], drop.keep, stream()))
+        return blk, scale
     with _Timed("hbm:head_backward", 4.0 * y.numel() * 3):
         check(lib.catseg_head_backward(ptr(dl), ld_of(dl), ptr(y), ld_of(y), ptr(stats), ptr(gamma), ptr(beta), ptr(wh), K, rows, C, ptr(blk),
                                        ptr(scale), ptr(dgamma), ptr(dbeta), ptr(dbias), ptr(dwh), ptr(dbh), ptr(grec), ptr(yrec), ptr(dyrec),
