@@ -41,6 +41,11 @@ int catseg_debug_set_dwgrad3_blocks(int blocks);
 /* persistent blocks of the planes kernel csrc/dconv3_pl.hip (default 512 = two per CU) */
 /* tuning hook: blocks of the 96+ channel backward-weight kernel on planes (0 = default 512; 768 = three per CU: faster standalone, more slab traffic, neutral in the step) */
 int catseg_debug_set_dwgrad3_pl_blocks(int blocks);
+/* A/B hook: form of the 96+ channel backward-weight kernel on planes (-1 restores the default, 3).  0 = one filter row per block
+ * (96 co x 48 ci), LDS-DMA through the compiler's builtin; 1 = the same blocks, the LDS-DMA of the next tile awaited behind this tile's MFMAs; 2 = all three filter
+ * rows per block (96 co x 48 ci: a pixel tile staged once per split and ci chunk), DMA as in 1; 3 = three rows, 48 co x 48 ci, DMA as in 1;
+ * 4 = as 2 with the builtin DMA.  Same split count and summation order in every form: bit-identical results */
+int catseg_debug_set_dwgrad3_pl_form(int form);
 int catseg_debug_set_dconv3_pl_slots(int slots);
 /* tuning hook: bit mask of channel counts (2: 96, 4: 192, 8: 384) whose planes kernel runs in the two-tiles-per-block form (eight
  * compute waves sharing one stream of weights, one block per CU) */

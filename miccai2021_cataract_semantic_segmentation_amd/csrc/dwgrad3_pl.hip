@@ -22,6 +22,15 @@ extern "C" int catseg_debug_set_dwgrad3_pl_blocks(int blocks) {
   catseg_g_wp96_blocks = blocks > 0 ? blocks : 512;
   return CATSEG_OK;
 }
+// form of the 96+ channel kernel (Wp96 ... Wp48R below; include/catseg_debug.h).  Standalone, slab reduction included, 96 / 192 / 384 channels
+// at 8 frames (profiles/r07_time_dwgrad3_pl_tiles.txt): form 0 58.7 / 58.8 / 66.9 us, 1: 55.8 / 55.8 / 62.9, 2: 57.9 / 58.0 / 67.7,
+// 3: 50.7 / 51.1 / 59.9, 4: 72.2 / 71.9 / 81.6; the training step 97.1 - 97.6 ms with form 0, 95.7 - 96.1 ms with form 3
+constexpr int WP96_FORM = 3;
+int catseg_g_wp96_form = WP96_FORM;
+extern "C" int catseg_debug_set_dwgrad3_pl_form(int form) {
+  catseg_g_wp96_form = form >= 0 && form <= 4 ? form : WP96_FORM;
+  return CATSEG_OK;
+}
 
 namespace {
 
@@ -32,8 +41,21 @@ typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 constexpr int wp_rowbytes(int c) { return ((c * 2 / 32) & 1) ? c * 2 : c * 2 + 32; }   // an odd multiple of 32 bytes (see dwgrad3_b3.hip)
 
-template <int COT_, int NCI_, int NTY_, int WM_, int WN_, int TH_, int NBUF_>
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+// One LDS-DMA instruction (16 bytes per lane to LDS bytes lds .. lds + 1023) OUTSIDE the compiler's bookkeeping.  hipcc counts the builtin
+// form as a pending LDS write and puts s_waitcnt vmcnt(0) in front of the first fragment read that follows it: the DMA of tile t + 1, issued
+// in front of tile t's MFMAs, was then awaited in front of them too, and only a co-resident block hid its round trip.  The kernel's own
+// counted wait + barrier behind the MFMAs (the order the data needs) is the only wait of this form.  M0 is the compiler's: saved, restored.
+__device__ __forceinline__ void wp_dma16(i32x4 rsrc, unsigned lds, unsigned voff, unsigned soff) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "s"(lds), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+}
+
+template <int COT_, int NCI_, int NTY_, int WM_, int WN_, int TH_, int NBUF_, bool LATE_ = false>
 struct WpCfg {
+  static constexpr bool LATE = LATE_;                   // the LDS-DMA through wp_dma16: awaited behind the tile's MFMAs only
   static constexpr int NBUF = NBUF_;                    // image buffers: the LDS-DMA of tile t + NBUF - 1 is issued in front of tile t's MFMAs
   static constexpr int COT = COT_, NCI = NCI_, NTY = NTY_, WM = WM_, WN = WN_, TH = TH_, TW = 16;
   static constexpr int NW = WM * WN, NTHR = 64 * NW;
@@ -119,6 +141,12 @@ __global__ __launch_bounds__(G::NTHR, 2) void dwgrad3_pl_kernel(const WpArgs a) 
   const unsigned plane_bytes = (unsigned)NG * a.P16;
   const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc((void*)a.xp, (short)0, (int)(2u * plane_bytes), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsd = __builtin_amdgcn_make_buffer_rsrc((void*)a.dp, (short)0, (int)(2u * plane_bytes), 0x00020000);
+  auto raw_rsrc = [&](const unsigned char* ptr) {     // the same descriptor as four scalar words (base, no stride, records, raw 32-bit data)
+    const unsigned long long v = (unsigned long long)ptr;
+    return i32x4{(int)(unsigned)v, (int)((unsigned)(v >> 32) & 0xFFFFu), (int)(2u * plane_bytes), 0x00020000};
+  };
+  const i32x4 rax = raw_rsrc(a.xp), rad = raw_rsrc(a.dp);
+  auto lds_addr = [&](unsigned char* ptr) { return (unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned char*)ptr; };
   auto dma = [&](int tile, int buf) {
     const int tx = tile % a.tiles_x, ty = (tile / a.tiles_x) % a.tiles_y, b = tile / (a.tiles_x * a.tiles_y);
     const int y0 = ty * G::TH, x0 = tx * G::TW;
@@ -133,9 +161,12 @@ __global__ __launch_bounds__(G::NTHR, 2) void dwgrad3_pl_kernel(const WpArgs a) 
         const unsigned voff = ok ? (unsigned)(org + x_rel[m]) + x_go[m] : 0xFFFFFFF0u;
 #pragma unroll
         for (int p = 0; p < 2; ++p)
-          if (j * 64 + lane < G::NPX_X * G::SX)
+          if (j * 64 + lane < G::NPX_X * G::SX) {
+            if constexpr (G::LATE) wp_dma16(rax, lds_addr(base + p * G::XPS + j * 1024), voff, (unsigned)(p * NG + ci0 / 8) * a.P16 + img);
+            else
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsx, (__attribute__((address_space(3))) void*)(base + p * G::XPS + j * 1024), 16, voff,
                                                      (unsigned)(p * NG + ci0 / 8) * a.P16 + img, 0, 0);
+          }
       }
     }
 #pragma unroll
@@ -146,9 +177,12 @@ __global__ __launch_bounds__(G::NTHR, 2) void dwgrad3_pl_kernel(const WpArgs a) 
         const unsigned voff = ok ? (unsigned)(org + d_rel[m]) + d_go[m] : 0xFFFFFFF0u;
 #pragma unroll
         for (int p = 0; p < 2; ++p)
-          if (j * 64 + lane < G::NPX_D * G::SD)
+          if (j * 64 + lane < G::NPX_D * G::SD) {
+            if constexpr (G::LATE) wp_dma16(rad, lds_addr(base + G::D0 + p * G::DPS + j * 1024), voff, (unsigned)(p * NG + cot0 / 8) * a.P16 + img);
+            else
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsd, (__attribute__((address_space(3))) void*)(base + G::D0 + p * G::DPS + j * 1024), 16, voff,
                                                      (unsigned)(p * NG + cot0 / 8) * a.P16 + img, 0, 0);
+          }
       }
     }
   };
@@ -265,21 +299,42 @@ using Wp48 = WpCfg<48, 48, 3, 1, 4, 4, 2>;   // one block: all 48 x 432 accumula
 // which is what hides the LDS-DMA round trip behind a 45-MFMA tile.  A third image buffer costs the third block: 60 -> 92 us (PMC: the same
 // wave cycles over 1.5 x the wall time), not adopted.  Differential builds (tools/ab_wp.sh, removed; last present in 0775e16) price
 // its LDS-DMA at 14 of 53 us (MFMAs alone 28, fragment reads 5, slab store 3).
-using Wp96 = WpCfg<96, 48, 1, 2, 2, 2, 2>;
+using Wp96 = WpCfg<96, 48, 1, 2, 2, 2, 2>;           // (form 0)
+using Wp96L = WpCfg<96, 48, 1, 2, 2, 2, 2, true>;   // (form 1) the same blocks, the LDS-DMA awaited behind the MFMAs only (wp_dma16)
+// The forms that stage a pixel tile ONCE for all three filter rows: the x tile carries a 4-row halo (72 pixels instead of 3 x 36) and dy is
+// fetched once instead of three times; 135 (96 co) / 63 (48 co) MFMAs per wave between two barriers instead of 45.  Same 2 x 16 pixel
+// K-steps, same tile ranges per split, same slabs: every element of dw accumulates in Wp96's order and the results are bit-identical to it
+// (tests/test_dwgrad3_pl_tiles_gpu.py).  The split count stays the one of Wp96's six variants per (96 co, 96 ci) -- which tiles a slab sums
+// is part of the result's bits -- so a launch has a third (96 co) or two thirds (48 co) of Wp96's blocks.
+using Wp96R = WpCfg<96, 48, 3, 2, 2, 2, 2, true>;    // (form 2) 96 co x (3 rows x 48 ci): 168 accumulator registers per lane, 55 KB of LDS
+using Wp48R = WpCfg<48, 48, 3, 1, 4, 2, 2, true>;    // (form 3) 48 co x (3 rows x 48 ci): 84 accumulator registers per lane, 39 KB of LDS
+using Wp96RB = WpCfg<96, 48, 3, 2, 2, 2, 2>;         // (form 4) form 2 with the builtin LDS-DMA
 
-struct WpPlan { int kind, variants, splits, TH; };
+struct WpPlan { int kind, variants, splits, TH; };   // kind: 1 = Wp48, 2 + form = the 96+ channel kernel
+
+template <class G> constexpr int wp_variants(int C) { return (C / G::COT) * (C / G::NCI) * (G::NTY == 3 ? 1 : 3); }
 
 WpPlan wp_plan(int C, int B, int H, int W) {
   WpPlan p = {0, 0, 0, 0};
   if (C == 48) { p.kind = 1; p.variants = 1; p.TH = Wp48::TH; }
-  else if (C == 96 || C == 192 || C == 384) { p.kind = 2; p.variants = (C / Wp96::COT) * (C / Wp96::NCI) * (Wp96::NTY == 3 ? 1 : 3); p.TH = Wp96::TH; }
+  else if (C == 96 || C == 192 || C == 384) { p.kind = 2; p.variants = wp_variants<Wp96>(C); p.TH = Wp96::TH; }
   else return p;
   const int ntile = B * ((H + p.TH - 1) / p.TH) * ((W + 15) / 16);
+  // (the splits of EVERY form of the 96+ channel kernel come from Wp96's variants: which tiles a slab sums is part of the result's bits)
   int s = (p.kind == 2 ? catseg_g_wp96_blocks : catseg_g_wg_blocks) / p.variants;
   if (s < 1) s = 1;
   if (s > ntile) s = ntile;
   p.splits = s;
+  if (p.kind == 2) {
+    p.kind += catseg_g_wp96_form;
+    p.variants = p.kind == 4 || p.kind == 6 ? wp_variants<Wp96R>(C) : p.kind == 5 ? wp_variants<Wp48R>(C) : p.variants;
+  }
   return p;
+}
+
+template <class G> hipError_t wp_occupancy(int* n) { return hipOccupancyMaxActiveBlocksPerMultiprocessor(n, dwgrad3_pl_kernel<G>, G::NTHR, 0); }
+template <class G> void wp_launch(int grid, hipStream_t st, const WpArgs& a) {
+  hipLaunchKernelGGL((dwgrad3_pl_kernel<G>), dim3(grid), dim3(G::NTHR), 0, st, a);
 }
 
 }  // namespace
@@ -289,8 +344,9 @@ extern "C" int catseg_dwgrad3_pl_supported(int C) { return C == 48 || C == 96 ||
 // blocks of the backward-weight kernel the runtime places on one CU (two by design: four waves per block, two waves per SIMD)
 extern "C" int catseg_debug_dwgrad3_pl_occupancy(int C) {
   int n = -1;
-  hipError_t e = C == 48 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, dwgrad3_pl_kernel<Wp48>, Wp48::NTHR, 0)
-                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, dwgrad3_pl_kernel<Wp96>, Wp96::NTHR, 0);
+  const int form = C == 48 ? -1 : catseg_g_wp96_form;
+  hipError_t e = form < 0 ? wp_occupancy<Wp48>(&n) : form == 0 ? wp_occupancy<Wp96>(&n) : form == 1 ? wp_occupancy<Wp96L>(&n)
+                 : form == 2 ? wp_occupancy<Wp96R>(&n) : form == 3 ? wp_occupancy<Wp48R>(&n) : wp_occupancy<Wp96RB>(&n);
   return e == hipSuccess ? n : -1;
 }
 
@@ -324,8 +380,14 @@ extern "C" int catseg_dwgrad3_pl(int B, int H, int W, int C, const void* x_plane
   a.splits = p.splits;
   hipStream_t st = (hipStream_t)stream;
   const int grid = (p.splits + 7) / 8 * 8 * p.variants;
-  if (p.kind == 1) hipLaunchKernelGGL((dwgrad3_pl_kernel<Wp48>), dim3(grid), dim3(Wp48::NTHR), 0, st, a);
-  else hipLaunchKernelGGL((dwgrad3_pl_kernel<Wp96>), dim3(grid), dim3(Wp96::NTHR), 0, st, a);
+  switch (p.kind) {
+    case 1: wp_launch<Wp48>(grid, st, a); break;
+    case 2: wp_launch<Wp96>(grid, st, a); break;
+    case 3: wp_launch<Wp96L>(grid, st, a); break;
+    case 4: wp_launch<Wp96R>(grid, st, a); break;
+    case 5: wp_launch<Wp48R>(grid, st, a); break;
+    default: wp_launch<Wp96RB>(grid, st, a); break;
+  }
   const long long n4 = wel / 4;
   cs_launch_reduce_slabs4((const float*)workspace, dw, n4, p.splits, st);
   CS_LAUNCH_CHECK();
