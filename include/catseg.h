@@ -621,6 +621,42 @@ int catseg_resize_nearest(const float* src, int lds, float* dst, int ldd, int B,
 int catseg_ensemble_merge(const float* const* logits, const int* ld, int M, long long P, int K, int mode, float* probs, int ld_probs,
                           int64_t* labels, catseg_stream_t stream);
 
+/* ---- egress: network output -> label maps and coloured uint8 frames (managers/BaseManager.py:690-741 demo_infer; utils/utils.py:50-142,
+ * 202-211 mask_from_network / mask_to_colormap / to_comb_image; utils/torch_utils.py:7-21 clipped_argmax) ---- */
+/* One launch per batch, every argument by value (no device-side pointer table: the launch can be captured).
+ *   rows: fp32 NHWC [B][H][W] pixels of ld >= K floats (out.permute(0, 2, 3, 1) of any model's output); 1 <= K <= 64.  Rows of up to 68
+ *     floats are staged through LDS with 16-byte loads, wider ones (views into a concat buffer) are read per lane; columns [K, ld) are
+ *     never taken for classes.
+ *   The predicted class is the FIRST maximal value of the row (torch.argmax; the rule of catseg_confusion_matrix and
+ *     catseg_ensemble_merge).
+ *   values_are_probs 0: rows are logits, the score of a pixel is 1 / sum_k exp(x_k - max) in fp32 (the maximum of nn.Softmax2d);
+ *     1: rows are probabilities (catseg_ensemble_merge's output), the score is the maximum itself.
+ *   threshold > 0: a pixel whose score is < threshold takes network id ignore_value (in [0, 255]) instead (clipped_argmax);
+ *     threshold <= 0: no score, no exp is evaluated.
+ *   crop_top, crop_bottom: rows of every image left out of the outputs (the inverse of PadNP(ver=(2, 2))): H' = H - crop_top - crop_bottom;
+ *     cropped rows are never read, in rows, frame or target.
+ *   lut: DEVICE uint8[256] network id -> dataset id (mask_from_network: the ignore id -> 255 for experiments 2 and 3); NULL = identity.
+ *   palette: DEVICE uint8[256][3], the colour of each dataset id ALREADY in the output channel order; unmapped ids 0.
+ *   frame (may be NULL): fp32 image [B][3][H][W], or [B][H][W][4] with frame_nhwc4 != 0; mean / stdv (HOST float[3], both or neither):
+ *     x * std + mean first (un_normalise, utils/utils.py:453: a rounded multiply, then a rounded add).  The byte is rintf(x * 255.f), ties
+ *     to even (np.round), clamped to [0, 255]; bgr != 0 reverses the channel order.
+ *   rows may be NULL when only the frame / target panels are wanted (mask_to_colormap of a label map): no prediction panel, no labels.
+ *   target (may be NULL): int64 [B][H][W] network-id ground truth, coloured through the same lut and palette (ids outside [0, 255]: black).
+ * Outputs (each may be NULL, not all):
+ *   labels_i64 [B][H'][W]: network ids after clipping, before lut (what argmax / clipped_argmax return);
+ *   labels_u8  [B][H'][W]: dataset ids, after lut;
+ *   canvas uint8 [B][H'][n_panels * W][3]: the panels that are present in the fixed order frame | target | prediction
+ *     (all three, RGB = to_comb_image; frame + prediction, BGR = the demo; prediction only, BGR = 'miccai_demo').
+ * With W % 4 == 0 (and 4-byte aligned byte outputs, a 16-byte aligned frame) a lane owns four consecutive pixels of one output row and
+ * stores 12 canvas bytes as three dwords, 4 label bytes as one; otherwise (unaligned canvas rows) bytes.  HBM traffic B H' W (4 ld + the
+ * output bytes) + the panels' inputs.  LDS: 1024 * (ld | 1) + 2048 bytes.
+ * CATSEG_EINVAL before anything is launched: K out of range, ld < K, crop_top + crop_bottom >= H, all outputs NULL, a canvas without a
+ * palette, threshold >= 1, ignore_value outside [0, 255] with a threshold, frame / target without a canvas, mean without std. */
+int catseg_egress_u8(const float* rows, int ld, int B, int H, int W, int K, int values_are_probs, int crop_top, int crop_bottom,
+                     float threshold, int ignore_value, const uint8_t* lut, const uint8_t* palette, const float* frame, int frame_nhwc4,
+                     const float* mean, const float* stdv, int bgr, const int64_t* target, int64_t* labels_i64, uint8_t* labels_u8,
+                     uint8_t* canvas, catseg_stream_t stream);
+
 /* ---- metrics / optimiser ------------------------------------------------------------------ */
 /* t_get_confusion_matrix (utils/torch_utils.py:221-241): cm[pred*K + gt] += 1 (int32, K x K),
  * labels outside [0, K) (>= K or negative) are dropped; pred = the FIRST maximal logit of the row (torch.argmax); cm is accumulated

@@ -195,6 +195,7 @@ _SIGS = {
     "catseg_ingest_u8": (I, [P, P, I, I, I, P, P, I, I, P, P, P, P, P, P]),
     "catseg_resize_nearest": (I, [P, I, P, I, I, I, I, I, I, I, I, I, F, P]),
     "catseg_ensemble_merge": (I, [P, P, I, L, I, I, P, I, P, P]),
+    "catseg_egress_u8": (I, [P, I, I, I, I, I, I, I, I, F, I, P, P, P, I, P, P, I, P, P, P, P, P]),
     "catseg_confusion_matrix": (I, [P, P, L, I, P, P]),
     "catseg_adam_step": (I, [P, P, P, P, L, F, F, F, F, I, F, P]),
     "catseg_pconv1_supported": (I, [I, I]),

@@ -5,7 +5,8 @@ Kept: step order ``zero_grad -> model(img.float()) -> loss -> backward -> step``
 Adam(lr) + LambdaLR(LRFcts) stepped once per epoch (BaseManager.py:439-464, OCRNet_Manager.py:132-134),
 validation with batch size 1 in eval mode under no_grad (BaseManager.py:305), best-mIoU rule on the mIoU
 rounded to 4 decimals (OCRNet_Manager.py:208-223), checkpoint file names and dictionary keys
-(BaseManager.py:471-495), inference with ``get_intermediate = False`` from the 'best' checkpoint (:640-688).
+(BaseManager.py:471-495), inference with ``get_intermediate = False`` from the 'best' checkpoint (:640-688),
+``mode: demo_video_inference`` / ``demo_infer()`` (:148-189, 690-741) with the frames' decoding and encoding outside (video_set / frame_sink).
 
 Changed on purpose (SURVEY.md "hard parts"): metrics stay on the device (one confusion-matrix kernel per
 step, no one-hot matmul, no per-step ``.item()``); TensorBoard / matplotlib logging is out of scope; data
@@ -34,6 +35,13 @@ TRAIN_DEFAULTS = {"epochs": 50, "lr_fct": "exponential", "lr_batchwise": False, 
 DATA_DEFAULTS = {"batch_size": 10, "num_workers": 0, "experiment": 1}
 
 
+def _item(v):
+    """one entry of a batch-of-one the DataLoader collated (a tensor, a list or a plain value) as a Python value"""
+    if isinstance(v, torch.Tensor):
+        return v.reshape(-1)[0].item()
+    return v[0] if isinstance(v, (list, tuple)) else v
+
+
 def merge_defaults(config):
     """utils/utils.py:533-542: flat defaults + nested defaults for 'data' / 'train' ('loss' must exist)"""
     cfg = dict(DEFAULTS)
@@ -51,7 +59,7 @@ class BaseManager:
     model_registry = _models
     loss_registry = _losses
 
-    def __init__(self, configuration, train_set=None, valid_set=None, train_sampler=None):
+    def __init__(self, configuration, train_set=None, valid_set=None, train_sampler=None, video_set=None, frame_sink=None):
         self.config = merge_defaults(configuration)
         self.start_epoch = self.epoch = 0
         self.best_loss = 1e10
@@ -77,13 +85,22 @@ class BaseManager:
             made = tuple(factory(self.config))
             train_set, valid_set, train_sampler = (made + (None, None, None))[:3]
         self.train_set, self.valid_set, self.train_sampler = train_set, valid_set, train_sampler
+        # mode 'demo_video_inference' (BaseManager.py:148-189): cv2's VideoCapture / VideoWriter stay outside -- video_set is any dataset
+        # yielding (frame float [3, H, W] in [0, 1], frame_idx, vid_id) as DatasetFromVideo does, frame_sink a callable
+        # (vid_id, frame_idx, ndarray [H, n W, 3] uint8 BGR); or config['data']['video_factory'](config) -> (video_set, frame_sink)
+        if self.config["mode"] == "demo_video_inference":
+            self.config.setdefault("demo_frame_freq", 1)       # every n-th frame: for the factory to honour
+            vfactory = self.config["data"].get("video_factory")
+            if video_set is None and frame_sink is None and callable(vfactory):
+                video_set, frame_sink = tuple(vfactory(self.config))[:2]
+        self.video_set, self.frame_sink = video_set, frame_sink
         self.load_model()
         self.loss = self.optimiser = self.scheduler = None
         if self.config["mode"] == "training":
             self.load_loss()
             torch.manual_seed(self.config["seed"])      # after model construction, as BaseManager.py:104-112
             self.load_optimiser()
-        elif self.config["mode"] != "inference":
+        elif self.config["mode"] not in ("inference", "demo_video_inference"):
             raise ValueError("mode: {} is not recognized".format(self.config["mode"]))
         self.history = []
 
@@ -276,6 +293,56 @@ class BaseManager:
             self.model = net
         m = t_get_mean_iou(cm, self.experiment, True, rare=True)
         return tuple(float(v) for v in m)
+
+    def demo_infer(self):
+        """BaseManager.py:690-741: the model over every frame of video_set, the frame_sink called once per frame, in order, with the uint8
+        BGR picture frame | coloured prediction ([H, 2 W, 3]; the prediction alone, [H, W, 3], with 'miccai_demo' in the configuration).
+        argmax, colouring, the frame's bytes and the concatenation are one kernel (utils.GpuEgress); the picture of frame i travels to
+        the host on a second stream, through a two-slot pinned ring with one event per slot, while frame i + 1 is in the network.
+        config['demo_crop'] = (top, bottom) drops the rows a padding ingest added (default (0, 0): the reference feeds 540-row frames
+        unpadded).  Returns the number of frames."""
+        from ..utils.egress import GpuEgress
+        if self.video_set is None or not callable(self.frame_sink):
+            raise ValueError("mode: demo_video_inference needs video_set= and frame_sink= (or config['data']['video_factory'])")
+        self.model.eval()
+        if hasattr(self.model, "get_intermediate"):
+            self.model.get_intermediate = False
+        if hasattr(self.model, "get_features"):
+            self.model.get_features = False
+        self.load_inference_weights()
+        probs = isinstance(self.model, _models.Ensemble)      # already softmaxed and merged (BaseManager.py:724)
+        only_pred = "miccai_demo" in self.config
+        egress = GpuEgress(self.experiment, crop=tuple(self.config.get("demo_crop", (0, 0))), bgr=True, device=self.device)
+        main, side = torch.cuda.current_stream(self.device), torch.cuda.Stream(self.device)
+        ring = [{"host": None, "event": torch.cuda.Event(), "dev": None, "tag": None} for _ in range(2)]
+
+        def flush(slot):
+            if slot["tag"] is not None:
+                slot["event"].synchronize()
+                self.frame_sink(slot["tag"][0], slot["tag"][1], slot["host"].numpy().copy())      # the array is the sink's to keep
+                slot["tag"] = slot["dev"] = None
+
+        n = 0
+        with torch.no_grad():
+            for frame, frame_idx, vid_id in DataLoader(self.video_set, batch_size=1, shuffle=False):
+                frame = frame.to(self.device, non_blocking=True).float()
+                out = self.final_output(self.model(frame))
+                if isinstance(out, (tuple, list)):              # (UPerNet: the last output, BaseManager.py:718-719)
+                    out = out[-1]
+                canvas = egress(out, frame=None if only_pred else frame, probs=probs)[0]
+                slot = ring[n % 2]                               # (emptied when frame n - 1 was enqueued)
+                if slot["host"] is None or slot["host"].shape != canvas.shape:
+                    slot["host"] = torch.empty(canvas.shape, dtype=torch.uint8, pin_memory=True)
+                side.wait_stream(main)
+                with torch.cuda.stream(side):
+                    slot["host"].copy_(canvas, non_blocking=True)
+                    slot["event"].record(side)
+                slot["dev"], slot["tag"] = canvas, (_item(vid_id), _item(frame_idx))      # the device picture lives until its copy has ended
+                flush(ring[(n + 1) % 2])                         # frame n - 1: its copy ran beside this frame's forward pass
+                n += 1
+        flush(ring[n % 2])
+        flush(ring[(n + 1) % 2])
+        return n
 
     def load_inference_weights(self):
         """BaseManager.py:649: inference scores this run's 'best' checkpoint (EnsembleManager: its members' own, loaded at construction)"""

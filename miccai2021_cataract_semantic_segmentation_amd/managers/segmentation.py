@@ -85,8 +85,9 @@ class EnsembleManager(BaseManager):
 
     def load_model(self):
         import pathlib
-        if self.config["mode"] != "inference":
-            raise ValueError("EnsembleManager runs mode: 'inference' only (got '{}'): an ensemble is not trained".format(self.config["mode"]))
+        if self.config["mode"] not in ("inference", "demo_video_inference"):
+            raise ValueError("EnsembleManager runs mode: 'inference' / 'demo_video_inference' only (got '{}'): an ensemble is not trained"
+                             .format(self.config["mode"]))
         cls = getattr(self.model_registry, self.config["graph"]["model"])
         self.model = cls(config=self.config["graph"], experiment=self.experiment).to(self.device)
         self.model.load_pretrained(pathlib.Path(self.config["log_path"]), self.device)

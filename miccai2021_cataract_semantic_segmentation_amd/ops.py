@@ -2049,6 +2049,49 @@ def ensemble_merge(members, mode="mean", want_probs=True, want_labels=False):
     return probs, labels
 
 
+def egress_u8(rows, probs=False, crop=(0, 0), threshold=0.0, ignore_value=0, lut=None, palette=None, frame=None, mean=None, std=None,
+              bgr=False, target=None, want_i64=False, want_u8=False, want_canvas=True):
+    """rows: NHWC logits (or probabilities, probs=True) [B, H, W, K], any pixel stride (None: no prediction, the other panels alone) -> (labels int64 [B, H', W] of network ids or None,
+    labels uint8 [B, H', W] of dataset ids or None, canvas uint8 [B, H', n_panels * W, 3] frame | target | prediction or None) in ONE launch
+    (csrc/egress.hip).  frame: float32 NCHW [B, 3, H, W] or NHWC-4 [B, H, W, 4]; mean / std: sequences of 3 floats (un_normalise);
+    target: int64 [B, H, W]; lut uint8[256], palette uint8[256, 3] (already in the output channel order) on the device."""
+    if rows is None:                      # no prediction: the frame / target panels alone (mask_to_colormap of a label map)
+        ref = target if target is not None else frame
+        B, H, W = ref.shape if ref.dim() == 3 else ((ref.shape[0],) + tuple(ref.shape[1:3] if ref.shape[-1] == 4 and ref.shape[1] != 3 else ref.shape[2:]))
+        K = ld = 0
+        dev = ref.device
+    else:
+        B, H, W, K = rows.shape
+        assert rows.dtype == torch.float32 and rows.is_cuda and rows.stride(-1) == 1
+        ld = ld_of(rows)
+        assert (H == 1 or W == 1 or rows.stride(1) == W * rows.stride(2)) and (B == 1 or rows.stride(0) == H * W * ld), \
+            "egress_u8: pixels must be evenly spaced (one pixel stride over the whole tensor)"
+        dev = rows.device
+    for t in (lut, palette):
+        assert t is None or (t.dtype == torch.uint8 and t.is_contiguous() and t.device == dev and t.numel() == (256 if t is lut else 768))
+    nhwc4 = False
+    if frame is not None:
+        nhwc4 = frame.dim() == 4 and frame.shape[-1] == 4 and frame.shape[1] != 3
+        assert frame.dtype == torch.float32 and frame.is_contiguous() and frame.device == dev
+        assert tuple(frame.shape) == ((B, H, W, 4) if nhwc4 else (B, 3, H, W)), "egress_u8: the frame must have the rows' B, H, W"
+    if target is not None:
+        assert target.dtype == torch.int64 and target.is_contiguous() and tuple(target.shape) == (B, H, W) and target.device == dev
+    Ho = H - crop[0] - crop[1]
+    li = torch.empty((B, max(Ho, 0), W), dtype=torch.int64, device=dev) if want_i64 else None
+    lu = torch.empty((B, max(Ho, 0), W), dtype=torch.uint8, device=dev) if want_u8 else None
+    n_panels = (rows is not None) + (frame is not None) + (target is not None)
+    canvas = torch.empty((B, max(Ho, 0), n_panels * W, 3), dtype=torch.uint8, device=dev) if want_canvas else None
+    cm = (ctypes.c_float * 3)(*mean) if mean is not None else None
+    cs = (ctypes.c_float * 3)(*std) if std is not None else None
+    nbytes = float(B) * max(Ho, 0) * W * (4 * ld + (8 if want_i64 else 0) + (1 if want_u8 else 0) + (3 * n_panels if want_canvas else 0)
+                                          + (12 if frame is not None else 0) + (8 if target is not None else 0))
+    with _Timed("hbm:egress", nbytes):
+        check(lib.catseg_egress_u8(ptr(rows), ld, B, H, W, K, 1 if probs else 0, crop[0], crop[1], float(threshold or 0.0), int(ignore_value or 0),
+                                   ptr(lut), ptr(palette), ptr(frame), 1 if nhwc4 else 0, cm, cs, 1 if bgr else 0, ptr(target), ptr(li), ptr(lu),
+                                   ptr(canvas), stream()))
+    return li, lu, canvas
+
+
 def confusion_matrix(logits, labels, cm=None):
     Pn, K = logits.shape
     if cm is None:

@@ -34,3 +34,12 @@ CLASS_REMAP = {
         255: [25, 26, 29, 30, 31, 34, 35]},
     3: dict([(i, [i]) for i in range(25)] + [(255, list(range(25, 36)))]),
 }
+
+# raw CaDIS id -> RGB, the colours the dataset is published with (36 classes; the colour of a remapped class is that of its first raw id)
+CADIS_PALETTE = (
+    (0, 137, 255), (255, 165, 0), (255, 156, 201), (99, 0, 255), (255, 0, 0), (255, 0, 165), (255, 255, 255), (141, 141, 141), (255, 218, 0),
+    (173, 156, 255), (73, 73, 73), (250, 213, 255), (255, 156, 156), (99, 255, 0), (157, 225, 255), (255, 89, 124), (173, 255, 156),
+    (255, 60, 0), (40, 0, 255), (170, 124, 0), (188, 255, 0), (0, 207, 255), (0, 255, 207), (188, 0, 255), (243, 0, 255), (0, 203, 108),
+    (252, 255, 0), (93, 182, 177), (0, 81, 203), (211, 183, 120), (231, 203, 0), (0, 124, 255), (10, 91, 44), (2, 0, 60), (0, 144, 2),
+    (133, 59, 59),
+)
