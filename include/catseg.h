@@ -91,6 +91,26 @@ int catseg_conv2d_bwd_weight(const catseg_conv_desc* d, const float* x, const fl
  * OCR head's reductions over all N = H * W pixels into a K x C result (models/OCR.py:158-170 spatial gather, the value / key gradients of
  * :266-274) run as catseg_gemm_batched over batch * splits row chunks followed by this sum */
 int catseg_sum_slabs(const float* slabs, float* out, long long n, int splits, int batch, int accumulate, catseg_stream_t stream);
+/* Operand contract of catseg_gemm_batched (tests/test_gemm_gpu.py holds the kernel to every sentence; r4(n) = n rounded up to 4).
+ * All layouts: A, Bm and C 16-byte aligned; lda, ldb, strideA, strideB multiples of 4 (ldc, strideC: any); 0 <= zero_to <= ldc; batch item
+ *   z of an operand starts z * stride floats behind its pointer, and the strides may exceed the dense item (slices of wider buffers).
+ *   Anything else returns CATSEG_EINVAL before a launch.  No row outside an item's logical rows, no float between or behind the batch
+ *   items, is ever read or written.
+ * NT  K % 4 == 0, K <= lda, ldb.  Exactly the columns [0, K) of A's M rows and of B's N rows are read: nothing has to be zero, columns
+ *     [K, ld) are never read.
+ * NN  r4(K) <= lda, r4(N) <= ldb.  A: columns [0, r4(K)) of its M rows are read, and the pad columns [K, r4(K)) MUST BE ZERO -- they are
+ *     multiplied by zeros that stand in for B's rows >= K, so an Inf / NaN there would reach every column of that row of C (the softmax
+ *     kernels that produce these operands write the zeros); columns [r4(K), lda) are never read.  B: rows [0, K) only -- rows >= K are
+ *     never read, whatever they hold; of those rows columns [0, r4(N)) are read, the pad columns [N, r4(N)) may hold anything (they
+ *     meet only accumulators that are not stored); columns [r4(N), ldb) are never read.
+ * TN  r4(M) <= lda, r4(N) <= ldb.  Exactly the K rows of A and of B are read (the last K-step of 16 is filled with zeros, not with rows
+ *     >= K); of those rows columns [0, r4(M)) of A and [0, r4(N)) of B are read, the pad columns [M, r4(M)) / [N, r4(N)) may hold
+ *     anything (not stored), the columns behind them are never read.
+ * C   Rows [0, M) of every batch item: columns [0, N) are written (accumulate == 0: previous contents are not read, NaNs are overwritten)
+ *     or added to (accumulate != 0: C = C + A B, the product summed first); columns [N, zero_to) are written as +0 in BOTH modes;
+ *     columns [max(N, zero_to), ldc) and everything between and behind the batch items keep their bits.  zero_to <= N writes no zeros.
+ * The summation order over K depends on the tile the planner picks (and is fixed for a given shape): results are deterministic, and
+ * bit-identical across tiles only where the sums are exact. */
 int catseg_gemm_batched(int layout, int batch, int M, int N, int K, const float* A, int lda,
                         long long strideA, const float* Bm, int ldb, long long strideB, float* C,
                         int ldc, long long strideC, int zero_to, int accumulate,
@@ -497,7 +517,7 @@ int catseg_adaptive_avgpool_bwd(const float* dy, float* dx, int lddx, int B, int
 
 /* ---- softmax ------------------------------------------------------------------------------ */
 /* F.softmax(probs.view(B,K,N), dim=2) at models/OCR.py:165, on NHWC logits [B][N][ld]:
- * per (b, k) over the N pixels, K <= 32.  Columns [K, ld) of the output are zeroed.
+ * per (b, k) over the N pixels, K <= 64 (one block column per 32 classes).  Columns [K, ld) of the output are zeroed.
  * _bwd: dx (+)= y * (dy - sum_n dy y) in columns [0, K); columns [K, ld) of dx are WRITTEN ZERO, also when accumulate != 0
  * (the pad columns of a class-logit buffer stay zero whatever was there). */
 size_t catseg_softmax_spatial_workspace(int B, int N);

@@ -36,6 +36,8 @@ SPATIAL = [
     # N, K, ld, B
     (1, 1, 4, 1), (7, 8, 8, 3), (8, 25, 32, 1), (9, 32, 32, 1), (511, 8, 40, 1), (512, 25, 28, 3), (513, 32, 40, 1), (519, 1, 32, 1),
     (4096, 25, 40, 3), (32640, 25, 32, 1), (32640, 32, 40, 3),
+    # more than 32 classes: a second block column (blockIdx.z) holds columns 32 ... 63
+    (9, 33, 36, 2), (513, 40, 64, 2), (4100, 64, 64, 1),
 ]
 
 
