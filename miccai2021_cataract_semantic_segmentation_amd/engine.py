@@ -7,6 +7,7 @@ torch.autograd sees exactly one node per network (``NetFunction``) and one per l
 the reference's ``loss.backward(); optimiser.step()`` calling convention working.
 """
 import collections
+import weakref
 
 import torch
 from torch import nn
@@ -1048,6 +1049,7 @@ class EngineNet(nn.Module):
         self._grads_pending = False
         self._keep_pass = False  # graph.GraphedTrainStep (segmented capture): keep the recorded pass for backward_from()
         self._last_pass = self._last_outputs = None
+        self._open_state = None  # weak reference to the state of the last recorded pass (dead once its Ctx is gone)
 
     def flat(self):
         if self._flatp is None:
@@ -1096,7 +1098,15 @@ class EngineNet(nn.Module):
         return bank
 
     def _run(self, x, record):
-        ops.release_b3_cache()          # (planes left over from a recorded forward that never saw its backward)
+        stale = self._open_state() if self._open_state is not None else None
+        if stale is not None:
+            stale.release()             # (planes left over from this network's last recorded forward if it never saw its backward)
+        # what the pass caches between its launches -- split planes, weight images, the bank of head images (whose buffers stay with the
+        # network: a captured step replays into them) -- is the pass's own: its Ctx holds it, and it is current while the pass runs
+        cx = Ctx(self.training, record, None)
+        cx.state = ops.PassState(h2w=self.__dict__.setdefault("_h2w_images", {}))
+        self._open_state = weakref.ref(cx.state) if record else None
+        ops.set_state(cx.state)
         # The per-step weight images (direct 3x3 kernels: 459 MB written for OCRNet-HRNet-W48, 0.43 ms; pointwise / gather kernels) are not
         # needed before stage 2: their launches run on a side stream beside the stem and stage 1; the launch stream waits for them at the
         # first lookup of an image or in front of the first parallel region (ops.images_ready).  Only while the step is being RECORDED into a
@@ -1110,8 +1120,7 @@ class EngineNet(nn.Module):
         if ops.P1 and ops._trunk_h2() and self.training:
             banks.append(self._p1_bank())
         banks = [b for b in banks if b]
-        ops.h2_weight_images_begin(self.__dict__.setdefault("_h2w_images", {}))
-        heads = self.training and ops.H2W_BANK and ops._h2w_bank
+        heads = ops.h2_weight_images_begin(self.flat().flat) and self.training and ops.H2W_BANK
         if banks or heads:
             if PREP_ASYNC and x.is_cuda and torch.cuda.is_current_stream_capturing():
                 main = torch.cuda.current_stream(x.device)
@@ -1128,13 +1137,11 @@ class EngineNet(nn.Module):
             else:
                 for b in banks:
                     b.refresh()
-        cx = Ctx(self.training, record, None)
         if ops._trunk_h2() and self.training:
             # the per-tensor amax records of this forward pass and of its backward: ONE chunk, zeroed here on the main stream, sized from
             # the previous pass of this network (+25 %: a rollover inside a parallel region would have to be ordered against its siblings)
             cx.amax_scope = ops.AmaxScope(x.device, max(ops.AMAX_SCOPE_RECORDS, int(1.25 * getattr(self, "_amax_records", 0)) + 64))
-            self._amax_scope_live = cx.amax_scope
-            ops.set_amax_scope(cx.amax_scope)
+            cx.state.amax_scope = cx.amax_scope
         global _cur_cx
         _cur_cx = cx
         try:
@@ -1142,8 +1149,9 @@ class EngineNet(nn.Module):
         finally:
             _cur_cx = None
             ops.images_ready()          # (a pass that looked no image up -- small maps stay on the fp32 kernels -- still joins the prep stream)
+            ops.set_state(None)
         if not record:
-            ops.release_b3_cache()      # a recorded forward keeps its split planes for the backward-weight pass (_end_backward frees them)
+            cx.state.release()          # a recorded forward keeps its split planes for the backward-weight pass (_end_backward frees them)
         return cx, outs
 
     def zero_grad(self, set_to_none=True):
@@ -1173,8 +1181,7 @@ class EngineNet(nn.Module):
                                    "(no accumulation over several backward passes); call optimiser.zero_grad() / model.zero_grad() "
                                    "between backward passes")
         fp.bind_grads()
-        if getattr(cx, "amax_scope", None) is not None:
-            ops.set_amax_scope(cx.amax_scope)           # (another forward pass may have run since this one)
+        ops.set_state(cx.state)         # (another forward pass may have run since this one: planes, images and amax records are this pass's own)
         if self._grad_sync is not None:
             cx.on_param_grad = self._grad_sync.param_ready
             cx.on_quiet = getattr(self._grad_sync, "quiet_point", None)
@@ -1206,7 +1213,8 @@ class EngineNet(nn.Module):
     def _end_backward(self, cx):
         if getattr(cx, "amax_scope", None) is not None:
             self._amax_records = max(getattr(self, "_amax_records", 0), cx.amax_scope.used)
-        ops.release_b3_cache()
+        cx.state.release()
+        ops.set_state(None)
         self._grads_pending = True
         if self._grad_sync is not None:
             self._grad_sync.finish()

@@ -112,12 +112,10 @@ class _Timed:
 # runs a layer is decided in ONE place, the route planner below (fwd_route / dgrad_route / wgrad_route); the thresholds it reads are the
 # module attributes of this file.  CATSEG_PRECISION=fp32 selects the exact fp32 path everywhere.
 PRECISION = _plan.get("precision")
-_b3_cache = {"key": None, "x": None, "planar": None, "blk": None}
 # thresholds of the layer selection (tests lower them to push small layers through the split-precision kernels)
 B3_MIN_TAPS, B3_MIN_K, B3_MIN_N, B3_MIN_TILES = 2, 2048, 192, 192
 B3_OPS = ("fwd", "dgrad", "wgrad")
 B3_MIN_WGRAD_ROWS = 32768
-_b3_cache_dy = {"key": None, "x": None, "planar": None, "blk": None}
 
 
 # wide 1x1 layers (the 1024 -> 512 bottleneck of the OCR head at stride 4): both GEMM extents >= 512, their product >= 512 * 1024,
@@ -224,12 +222,47 @@ def _cached(cache, x, key, want, both):
     return cache[want]
 
 
-_b3_kept = {}   # training step: planes of every split input, kept from the forward pass for its backward-weight pass
+def _no_planes():
+    return {"key": None, "x": None, "planar": None, "blk": None, "h2": None, "h2p": None}
+
+
+class PassState:
+    """what ONE pass (a forward and its backward) caches between its launches: the split planes of its activations and the images of its
+    weights.  engine.EngineNet._run creates one per pass, keeps it on the pass's Ctx and makes it current (set_state) for the forward and
+    again for the backward, so that passes of several networks in flight never see, overwrite or release each other's operands; callers
+    outside the engine (tests, tools) work on the module's default instance."""
+
+    def __init__(self, h2w=None):
+        self.last, self.last_dy = _no_planes(), _no_planes()    # planes of the last split activation / output gradient
+        self.kept = {}          # recorded forward: planes of every split input, kept for the layer's backward-weight pass
+        self.d3_wimg, self.p1_wimg, self.p1_keep = {}, {}, []   # weight images of the direct / pointwise + gather kernels (and one-layer banks)
+        self.h2w = h2w          # the network's bank of head weight images (the buffers outlive the pass: EngineNet._h2w_images), or None
+        self.images_event = None    # (event, origin stream): the pass's weight images are being written on a side stream
+        self.amax_scope = None      # the AmaxScope new_amax() draws from
+
+    def release(self):
+        """drops the planes and images (the memory of a finished pass); the head bank's images are no longer those of a running step"""
+        self.last, self.last_dy = _no_planes(), _no_planes()
+        self.kept.clear()
+        self.d3_wimg.clear()
+        self.p1_wimg.clear()
+        del self.p1_keep[:]
+        for e in (self.h2w or {}).values():
+            e["fresh"] = False
+
+
+_default_state = _state = PassState()
+
+
+def set_state(st):
+    """the state the cached operand functions below read and write; None: the default one"""
+    global _state
+    _state = _default_state if st is None else st
 
 
 def _split3_cached(x, want="planar", both=False, keep=False):
     """three-plane split of an activation.  The last one is always kept (the two 720-channel head convolutions of OCRNet-HRNet and
-    the ASPP branches read one tensor); keep=True (a recorded training forward) holds on to the planes until release_b3_cache(),
+    the ASPP branches read one tensor); keep=True (a recorded training forward) holds on to the planes until the pass's state is released,
     so that the layer's backward-weight pass reads what its forward produced instead of splitting x again (the planes of all
     bf16x3 layers of a step: 5.5 GB for OCRNet-HRNet-W48 at bs 8, of 288 GB)"""
     # (per stream: since round 5 a branch output may be read by fuse chains on SEVERAL branch streams -- each splits for itself; planes made
@@ -240,28 +273,24 @@ def _split3_cached(x, want="planar", both=False, keep=False):
             return hp
         _refuse_h2_only(x, "a split pass (%s planes)" % want)
     key = (x.data_ptr(), x._version, tuple(x.shape), ld_of(x), torch.cuda.current_stream(x.device).cuda_stream if x.is_cuda else 0)
-    ent = _b3_kept.get(key)
+    ent = _state.kept.get(key)
     if ent is not None and ent["x"] is x:
         return _cached(ent, x, key, want, both)
     if keep:
-        ent = {"key": None, "x": None, "planar": None, "blk": None, "h2": None, "h2p": None}
-        _b3_kept[key] = ent
+        ent = _state.kept[key] = _no_planes()
         return _cached(ent, x, key, want, both)
-    return _cached(_b3_cache, x, key, want, both)
+    return _cached(_state.last, x, key, want, both)
 
 
 def _split3_cached_dy(dy, want="planar", both=False):
     """the dy planes of a layer are used twice in its backward (backward-weight, then backward-data)"""
-    return _cached(_b3_cache_dy, dy, (dy.data_ptr(), tuple(dy.shape), ld_of(dy)), want, both)
+    return _cached(_state.last_dy, dy, (dy.data_ptr(), tuple(dy.shape), ld_of(dy)), want, both)
 
 
 def release_b3_cache():
-    _b3_cache.update(key=None, x=None, planar=None, blk=None, h2=None, h2p=None)
-    _b3_cache_dy.update(key=None, x=None, planar=None, blk=None, h2=None, h2p=None)
-    _b3_kept.clear()
-    _d3_wimg.clear()
-    _p1_wimg.clear()
-    del _p1_keep[:]
+    """releases the current state and the default one (never the state of another pass in flight)"""
+    _state.release()
+    _default_state.release()
 
 
 # Direct 3x3 / stride 1 / pad 1 convolution of the HRNet trunk widths in split precision (csrc/dconv3_b3.hip): the fp32 activation is
@@ -269,7 +298,6 @@ def release_b3_cache():
 # pixels the launch cannot fill the chip with its 128-pixel tiles and the fp32 implicit GEMM is as good (tests lower it).
 DCONV3 = True
 DCONV3_MIN_ROWS = 2048
-_d3_wimg = {}
 
 
 def d3_layer(Cin, Cout, kh, kw, stride, pad, dil, groups):
@@ -318,7 +346,6 @@ def planes_ok(C, rows):
 
 AMAX_SCOPE_RECORDS = 1024
 AMAX_WORDS = 512        # int32 words per record (include/catseg.h: CATSEG_AMAX_RECORD_BYTES): 16 slots 128 bytes apart
-_amax_scope = None
 
 
 class AmaxScope:
@@ -354,17 +381,15 @@ class AmaxScope:
 
 
 def set_amax_scope(scope):
-    """the scope new_amax() draws from (the engine sets it at the start of a recorded forward and of its backward)"""
-    global _amax_scope
-    _amax_scope = scope
+    """the scope new_amax() draws from: the current state's (the engine gives every pass its own)"""
+    _state.amax_scope = scope
 
 
 def new_amax(device):
     """a zeroed amax record (int32[AMAX_WORDS]) from the current scope (a private scope per device outside the engine)"""
-    global _amax_scope
-    if _amax_scope is None or _amax_scope.device != device:
-        _amax_scope = AmaxScope(device)
-    return _amax_scope.new()
+    if _state.amax_scope is None or _state.amax_scope.device != device:
+        _state.amax_scope = AmaxScope(device)
+    return _state.amax_scope.new()
 
 
 def amax_of(t):
@@ -398,39 +423,35 @@ def drop_amax(t):
     return t
 
 
-_images_event = None      # (event, origin stream): the step's weight images are being written on a side stream (engine.EngineNet._run)
-
-
 def images_pending(ev, origin):
-    global _images_event
-    _images_event = (ev, origin)
+    """the pass's weight images are being written on a side stream (engine.EngineNet._run): ev marks their end, origin is the launch stream"""
+    _state.images_event = (ev, origin)
 
 
 def images_ready():
     """the current stream waits for the weight-image launches of this step (once: every later stream forks from the origin stream)"""
-    global _images_event
-    if _images_event is not None:
-        ev, origin = _images_event
+    if _state.images_event is not None:
+        ev, origin = _state.images_event
         cur = torch.cuda.current_stream(origin.device)
         cur.wait_event(ev)
         if cur.cuda_stream == origin.cuda_stream:
-            _images_event = None
+            _state.images_event = None
 
 
 def dconv3_weight_image(w, backward_data=False, h2=False):
-    """pre-split weight image of the direct kernel (cached until release_b3_cache(): one per layer and direction per step);
+    """pre-split weight image of the direct kernel (cached in the current state: one per layer and direction per pass);
     h2: the two-plane fp16 image and its scale record, (image, record)"""
     images_ready()
     key = (w.data_ptr(), bool(backward_data), bool(h2))
-    img = _d3_wimg.get(key)
+    img = _state.d3_wimg.get(key)
     if img is None:
         C = w.shape[0]
         if h2:       # (layers outside a Dconv3Bank: a one-layer bank over the weight tensor itself)
             Dconv3Bank(w, [(w, 0)], h2=True).refresh()
-            return _d3_wimg[key]
+            return _state.d3_wimg[key]
         img = torch.empty(lib.catseg_dconv3_wimg_bytes(C), dtype=torch.uint8, device=w.device)
         check(lib.catseg_dconv3_prep(ptr(w), C, 1 if backward_data else 0, ptr(img), stream()))
-        _d3_wimg[key] = img
+        _state.d3_wimg[key] = img
     return img
 
 
@@ -462,15 +483,15 @@ class Dconv3Bank:
         self.records = torch.zeros(2 * self.n, dtype=torch.int32, device=flat.device) if h2 else None
 
     def refresh(self):
-        """(re)write every image from the current parameters and publish them to dconv3_weight_image's cache"""
+        """(re)write every image from the current parameters and publish them to the current state (dconv3_weight_image)"""
         if self.h2:
             check(lib.catseg_dconv3_f16x2_prep_batch(ptr(self.flat), self.n, ptr(self.entries), ptr(self.images), ptr(self.records), stream()))
             for w, dg, off, nbytes, k in self.slices:
-                _d3_wimg[(w.data_ptr(), bool(dg), True)] = (self.images[off:off + nbytes], self.records[2 * k:2 * k + 2])
+                _state.d3_wimg[(w.data_ptr(), bool(dg), True)] = (self.images[off:off + nbytes], self.records[2 * k:2 * k + 2])
             return
         check(lib.catseg_dconv3_prep_batch(ptr(self.flat), self.n, ptr(self.entries), ptr(self.images), stream()))
         for w, dg, off, nbytes, k in self.slices:
-            _d3_wimg[(w.data_ptr(), bool(dg), False)] = self.images[off:off + nbytes]
+            _state.d3_wimg[(w.data_ptr(), bool(dg), False)] = self.images[off:off + nbytes]
 
 
 # Pointwise (1 x 1, stride 1) convolutions in split precision with the split in registers (csrc/pconv1.hip): every dense 1 x 1 layer whose
@@ -487,7 +508,6 @@ P1 = _plan.get("p1")
 P1_MIN_ROWS = _plan.get("p1_min_rows")
 P1_WGRAD_MIN_DIM = _plan.get("p1_wgrad_min_dim")
 P1_OPS = _plan.get("p1_ops")
-_p1_wimg = {}
 
 
 def p1_geometry(kh, kw, stride, pad, groups):
@@ -551,19 +571,19 @@ class P1Bank:
     def refresh(self):
         check(lib.catseg_pconv1_prep_batch(ptr(self.flat), self.n, ptr(self.entries), ptr(self.images), ptr(self.records), stream()))
         for key, off, nbytes, k in self.slices:
-            _p1_wimg[key] = (self.images[off:off + nbytes], self.records[2 * k:2 * k + 2])
+            _state.p1_wimg[key] = (self.images[off:off + nbytes], self.records[2 * k:2 * k + 2])
 
 
 def p1_weight_image(w, transposed=False):
     """(image, record) of a pointwise layer's weights [O, I, 1, 1] (physical OHWI = [O][I]); layers outside a P1Bank get a one-layer bank"""
     images_ready()
     key = (w.data_ptr(), bool(transposed))
-    img = _p1_wimg.get(key)
+    img = _state.p1_wimg.get(key)
     if img is None:
         bank = P1Bank(w, [(w, 0, 1, 0, 1)])
         bank.refresh()
-        _p1_keep.append(bank)
-        img = _p1_wimg[key]
+        _state.p1_keep.append(bank)
+        img = _state.p1_wimg[key]
     return img
 
 
@@ -599,16 +619,13 @@ def g1_weight_image(w, backward_data, stride, pad, dil):
     """(image(s), record) of a gather layer: the forward image, or the stride^2 class images of backward-data back to back"""
     images_ready()
     key = (w.data_ptr(), "g", bool(backward_data), stride, pad, dil)
-    img = _p1_wimg.get(key)
+    img = _state.p1_wimg.get(key)
     if img is None:
         bank = P1Bank(w, [(w, 0, stride, pad, dil)])
         bank.refresh()
-        _p1_keep.append(bank)
-        img = _p1_wimg[key]
+        _state.p1_keep.append(bank)
+        img = _state.p1_wimg[key]
     return img
-
-
-_p1_keep = []
 
 
 def pconv1(x, wimg, bias, N, out, accumulate=False, bn_stats=False):
@@ -963,7 +980,7 @@ def _h2_only_guard(x, route, what):
 def conv_fwd(x, w_ptr_tensor, bias, Cout, kh, kw, stride=1, pad=0, dil=1, out=None, zero_to=0, stem4=False, groups=1, bn_stats=False, train=False,
              exact=False, with_yrec=False):
     """train=True (the engine's recorded forward): a backward pass will follow -- the split planes of x are written in both layouts
-    and kept for it (release_b3_cache() frees them).
+    and kept for it (in the current state, until that is released).
     exact=True (the first layers of a trunk, whose rounding error the rest of the network amplifies most: tools/error_growth.py): the
     layer runs the fp32 MFMA kernel (exact operands, two-level accumulation: csrc/igemm.hip TWO_LEVEL) whatever the split-precision
     kernels could take.  (Measured at 2 x 3 x 544 x 960, relative RMS error of layer1's output against fp64: fp32 CPU 1.22e-6, this 0.89e-6,
@@ -2264,24 +2281,24 @@ def split2h_blocked(x):
 
 # Weight images of the head layers (forward: blocked planes; backward-data: the transposed bank's).  Each was amax + split launched in line, in
 # front of its GEMM on the strictly serial head path (~55 us with the launch gaps, six times per step).  Round 6: a layer that took this route
-# once keeps its two image buffers, and while a step is being captured into a hipGraph EngineNet._run refreshes them all on the weight-image
-# side stream beside stem + stage 1 (h2_weight_images_refresh: the same hand-over as the trunk's banks, ops.images_ready); everywhere else the
-# images are made in line as before.
+# once keeps its two image buffers in its network's bank (PassState.h2w), and while a step is being captured into a hipGraph EngineNet._run
+# refreshes them all on the weight-image side stream beside stem + stage 1 (h2_weight_images_refresh: the same hand-over as the trunk's banks,
+# ops.images_ready); everywhere else the images are made in line as before.
+# A bank: (data_ptr, shape, transposed) -> {"w": weights, "planes", "scale", "fresh": made for the RUNNING step by the refresh}
 H2W_BANK = _plan.get("h2w_bank")
-_h2w_bank = None      # the running network's bank (EngineNet._run sets it: the buffers live as long as the network):
-                      # (data_ptr, shape, transposed) -> {"w": weights, "planes", "scale", "fresh": made for the CURRENT step by the refresh}
 
 
 def _h2w_entry(w, transposed):
     O, I, kh, kw = w.shape
     key = (w.data_ptr(), tuple(w.shape), transposed)
-    e = _h2w_bank.get(key) if _h2w_bank is not None else None
+    bank = _state.h2w
+    e = bank.get(key) if bank is not None else None
     if e is None:
         rows = kh * kw * ((O + 15) // 16) if transposed else kh * kw * I // 16
         e = {"w": w, "planes": torch.empty((2, rows, I if transposed else O, 16), dtype=torch.int16, device=w.device),
              "scale": torch.empty(2, dtype=torch.int32, device=w.device), "fresh": False}
-        if H2W_BANK and _h2w_bank is not None and len(_h2w_bank) < 64:
-            _h2w_bank[key] = e
+        if H2W_BANK and bank is not None and len(bank) < 64:
+            bank[key] = e
     return e
 
 
@@ -2292,17 +2309,20 @@ def _h2w_launch(e, transposed):
     check(fn(ptr(w), O, kh * kw, I, ptr(e["planes"]), ptr(e["scale"]), stream()))
 
 
-def h2_weight_images_begin(bank):
-    """a network's pass starts: its bank becomes the current one, nothing in it is valid for this step yet"""
-    global _h2w_bank
-    _h2w_bank = bank
+def h2_weight_images_begin(flat):
+    """a pass of the network whose flat parameter buffer is `flat` starts: nothing in its bank is valid for this step yet, and entries
+    whose weights are not views into `flat` (the buffer was reallocated) go; -> the bank has entries to refresh"""
+    bank, base = _state.h2w, flat.untyped_storage().data_ptr()
+    for key in [k for k, e in bank.items() if e["w"].untyped_storage().data_ptr() != base]:
+        del bank[key]
     for e in bank.values():
         e["fresh"] = False
+    return bool(bank)
 
 
 def h2_weight_images_refresh():
     """(on the weight-image side stream) both images of every head layer seen so far, for the step that starts now"""
-    for (_, _, transposed), e in _h2w_bank.items():
+    for (_, _, transposed), e in _state.h2w.items():
         _h2w_launch(e, transposed)
         e["fresh"] = True
 

@@ -258,7 +258,7 @@ def test_batched_weight_images_equal_single_prep(ops):
     bank = ops.Dconv3Bank(flat, list(zip(ws, offs)))
     ops.release_b3_cache()
     bank.refresh()
-    got = {k: v.clone() for k, v in ops._d3_wimg.items()}
+    got = {k: v.clone() for k, v in ops._state.d3_wimg.items()}
     ops.release_b3_cache()
     for w in ws:
         for dg in (False, True):
@@ -268,7 +268,7 @@ def test_batched_weight_images_equal_single_prep(ops):
     bank = ops.Dconv3Bank(flat, list(zip(ws, offs)), h2=True)
     bank.refresh()
     for w, c in zip(ws, widths):
-        img, rec = ops._d3_wimg[(w.data_ptr(), False, True)]
+        img, rec = ops._state.d3_wimg[(w.data_ptr(), False, True)]
         amax = float(w.abs().max())
         e = int(rec.cpu()[1])
         assert 2.0 ** 14 <= amax * 2.0 ** e < 2.0 ** 15 and img.numel() == lib.catseg_dconv3_f16x2_wimg_bytes(c)

@@ -190,6 +190,114 @@ def test_amax_record_scopes():
         ops.set_amax_scope(None)
 
 
+def _filled(ops, st, tag):
+    """plain tensors and stub entries in every container of a ops.PassState; -> the tensor that stands for its kept planes"""
+    t = torch.full((4,), float(tag))
+    st.last.update(key=("last", tag), x=t, planar=t)
+    st.last_dy.update(key=("dy", tag), x=t, blk=t)
+    st.kept[("kept", tag)] = {"key": ("kept", tag), "x": t, "planar": t, "blk": None, "h2": None, "h2p": None}
+    st.d3_wimg[(tag, False, False)] = t
+    st.p1_wimg[(tag, False)] = (t, t)
+    st.p1_keep.append(object())
+    return t
+
+
+def _is_empty(st):
+    return (st.last["x"] is None and st.last["planar"] is None and st.last_dy["x"] is None and st.last_dy["blk"] is None
+            and not st.kept and not st.d3_wimg and not st.p1_wimg and not st.p1_keep)
+
+
+def test_pass_states_release_only_themselves():
+    """ops.PassState: the planes and weight images of one pass are its own -- releasing one state leaves another's in place, and
+    release_b3_cache() clears the current state and the default one and no third one"""
+    from miccai2021_cataract_semantic_segmentation_amd import ops
+    default = ops._default_state
+    try:
+        a, b, c = ops.PassState(), ops.PassState(), ops.PassState()
+        ta, tb, tc = (_filled(ops, st, i) for i, st in enumerate((a, b, c), 1))
+        a.release()
+        assert _is_empty(a) and not _is_empty(b) and not _is_empty(c)
+        assert b.kept[("kept", 2)]["planar"] is tb and b.d3_wimg[(2, False, False)] is tb and b.p1_wimg[(2, False)][0] is tb
+        assert b.last["planar"] is tb and b.last_dy["blk"] is tb and len(b.p1_keep) == 1
+        td = _filled(ops, default, 9)
+        ops.set_state(b)
+        assert ops._state is b
+        ops.release_b3_cache()
+        assert _is_empty(b) and _is_empty(default), "release_b3_cache() releases the current and the default state"
+        assert not _is_empty(c) and c.kept[("kept", 3)]["planar"] is tc and c.d3_wimg[(3, False, False)] is tc, "... and no third one"
+        ops.set_state(None)
+        assert ops._state is default
+        del ta, td
+    finally:
+        ops.set_state(None)
+        ops.release_b3_cache()
+
+
+def test_amax_scope_accessors_follow_the_current_state():
+    """set_amax_scope / new_amax are accessors of the current state: each pass draws from its own scope, the default state gets a private one"""
+    from miccai2021_cataract_semantic_segmentation_amd import ops
+    dev = torch.device("cpu")
+    default = ops._default_state
+    saved = default.amax_scope
+    try:
+        default.amax_scope = None
+        a, b = ops.PassState(), ops.PassState()
+        sa = ops.AmaxScope(dev, 16)
+        ops.set_state(a)
+        ops.set_amax_scope(sa)
+        assert a.amax_scope is sa and b.amax_scope is None and default.amax_scope is None
+        r0 = ops.new_amax(dev)
+        assert sa.used == 1 and int(r0.abs().sum()) == 0
+        ops.set_state(b)
+        r1 = ops.new_amax(dev)                                  # no scope yet: a private one for this state
+        assert b.amax_scope is not None and b.amax_scope is not sa and sa.used == 1 and b.amax_scope.used == 1
+        ops.set_state(a)                                        # the first pass's backward continues in its own scope
+        assert ops.new_amax(dev).data_ptr() == r0.data_ptr() + 4 * ops.AMAX_WORDS and sa.used == 2
+        ops.set_state(None)
+        r2 = ops.new_amax(dev)
+        assert default.amax_scope is not None and default.amax_scope.used == 1 and sa.used == 2
+        assert len({r.data_ptr() for r in (r0, r1, r2)}) == 3
+        a.release()
+        assert a.amax_scope is sa, "releasing the planes leaves the records of tensors that are still alive"
+    finally:
+        ops.set_state(None)
+        default.amax_scope = saved
+
+
+def test_head_bank_drops_entries_of_a_replaced_flat_buffer():
+    """ops.h2_weight_images_begin: entries whose weights are views into the flat parameter buffer stay (their `fresh` flags cleared), entries
+    of a buffer that has been reallocated go; releasing the pass's state clears the flags again"""
+    from miccai2021_cataract_semantic_segmentation_amd import ops
+
+    def entry(w):
+        return {"w": w, "planes": torch.empty(1), "scale": torch.empty(2), "fresh": True}
+
+    old, flat = torch.zeros(4096), torch.zeros(4096)
+    w_old = old[64:64 + 512].view(8, 1, 1, 64).permute(0, 3, 1, 2)
+    w_new = flat[64:64 + 512].view(8, 1, 1, 64).permute(0, 3, 1, 2)
+    w_new2 = flat[1024:1024 + 1024].view(16, 1, 1, 64).permute(0, 3, 1, 2)
+    alone = torch.zeros(8, 64, 1, 1)
+    bank = {}
+    for w in (w_old, w_new, w_new2, alone):
+        for t in (False, True):
+            bank[(w.data_ptr(), tuple(w.shape), t)] = entry(w)
+    st = ops.PassState(h2w=bank)
+    try:
+        ops.set_state(st)
+        assert ops.h2_weight_images_begin(flat) is True
+        assert sorted(bank) == sorted((w.data_ptr(), tuple(w.shape), t) for w in (w_new, w_new2) for t in (False, True))
+        assert all(e["w"] is w for w in (w_new, w_new2) for t in (False, True) for e in [bank[(w.data_ptr(), tuple(w.shape), t)]])
+        assert not any(e["fresh"] for e in bank.values())
+        assert ops._h2w_entry(w_new, True) is bank[(w_new.data_ptr(), tuple(w_new.shape), True)]
+        for e in bank.values():
+            e["fresh"] = True
+        st.release()
+        assert len(bank) == 4 and not any(e["fresh"] for e in bank.values())
+        assert ops.h2_weight_images_begin(old) is False and not bank
+    finally:
+        ops.set_state(None)
+
+
 def test_roctx_ranges_are_optional_and_balanced():
     """CATSEG_ROCTX=1: every timed C-ABI call is bracketed by roctxRangePush(kind) / roctxRangePop(); off by default"""
     import subprocess

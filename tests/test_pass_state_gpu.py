@@ -1,0 +1,106 @@
+"""Two networks with passes in flight at the same time (engine.EngineNet._run / _begin_backward / _end_backward, ops.PassState): the split
+planes a recorded forward keeps for its backward, the weight images of the step and the bank of head weight images belong to the pass and
+its network -- a forward of network B between A's forward and A's backward neither changes A's results nor costs A's operands."""
+import copy
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+COUNTED = ("split2h", "split3", "split3_blocked", "_h2w_launch")
+
+
+def _nets():
+    """OCRNet-HRNet-W48 twice, with different weights (on the CPU: every run below starts from a fresh copy)"""
+    from oracle.state import fill_state, spec_of
+    from miccai2021_cataract_semantic_segmentation_amd.models import OCRNet
+    nets = []
+    for seed in (31, 47):
+        net = OCRNet({"backbone": "hrnet48", "pretrained": False}, 3)
+        net.load_state_dict(fill_state(spec_of(net.state_dict()), seed))
+        nets.append(net)
+    return nets
+
+
+def test_interleaved_passes_of_two_networks_match_the_sequential_order():
+    """A.forward, A.backward, B.forward, B.backward against A.forward, B.forward, A.backward, B.backward on fresh copies, on maps of 2 x 24 x 40
+    pixels with the thresholds lowered so that the trunk takes the planes route (d3p) and the head layers the blocked f16x2 route (h2):
+    every output and parameter gradient bit-identical, no more split passes and weight-image launches in the interleaved order than in the
+    sequential one, and each network's head bank holds its own weights only.
+    The count assertion FAILS on the code before ops.PassState, and that is the defect this test pins: B's forward released the planes and
+    images A's forward had kept in module globals, so A's backward split every activation again and built a one-layer image bank per
+    layer, and it entered its head images into B's bank."""
+    from miccai2021_cataract_semantic_segmentation_amd import ops
+    assert ops.TRUNK == "f16x2" and ops.HEADS == "f16x2" and ops.PLANES and ops.H2W_BANK, "shipped defaults expected"
+    saved = (ops.PRECISION, ops.B3_MIN_TAPS, ops.B3_MIN_K, ops.B3_MIN_N, ops.B3_MIN_TILES, ops.B3_MIN_WGRAD_ROWS, ops.DCONV3_MIN_ROWS)
+    real = {n: getattr(ops, n) for n in COUNTED}
+    real_d3, real_p1 = ops.Dconv3Bank.refresh, ops.P1Bank.refresh
+    counts = {}
+
+    def counted(name, fn):
+        def wrapper(*a, **k):
+            counts[name] = counts.get(name, 0) + 1
+            return fn(*a, **k)
+        return wrapper
+
+    gen = torch.Generator().manual_seed(8)
+    xs = [torch.randn(2, 3, 96, 160, generator=gen).cuda() for _ in range(2)]
+    r1, r2 = (torch.randn(2, 25, 96, 160, generator=gen).cuda() for _ in range(2))
+
+    def run(cpu_nets, order):
+        """order: 'f0 b0 f1 b1' ... -> per network (outputs, gradients, the network), the launch counts, the kernel kinds"""
+        nets = [copy.deepcopy(n).cuda().train() for n in cpu_nets]
+        outs = [None, None]
+        counts.clear()
+        ops.PROFILE = []
+        for step in order.split():
+            i = int(step[1])
+            if step[0] == "f":
+                nets[i].zero_grad()
+                outs[i] = nets[i](xs[i])
+            else:
+                interm, final = outs[i]
+                (final * r1).mean().add(0.4 * (interm * r2).mean()).backward()
+        torch.cuda.synchronize()
+        kinds, ops.PROFILE = {p[0] for p in ops.PROFILE}, None
+        res = [([o.detach().clone() for o in outs[i]], {n: p.grad.detach().clone() for n, p in nets[i].named_parameters()}, nets[i])
+               for i in (0, 1)]
+        return res, dict(counts), kinds
+
+    try:
+        ops.PRECISION, ops.B3_MIN_TAPS, ops.B3_MIN_K, ops.B3_MIN_N, ops.B3_MIN_TILES, ops.B3_MIN_WGRAD_ROWS = "bf16x3", 1, 64, 32, 1, 1
+        ops.DCONV3_MIN_ROWS = 1
+        for n in COUNTED:
+            setattr(ops, n, counted(n, real[n]))
+        ops.Dconv3Bank.refresh = counted("Dconv3Bank.refresh", real_d3)
+        ops.P1Bank.refresh = counted("P1Bank.refresh", real_p1)
+        cpu_nets = _nets()
+        seq, n_seq, kinds = run(cpu_nets, "f0 b0 f1 b1")
+        assert {"fwd_d3p", "dgrad_d3p", "wgrad_d3p", "fwd_h2", "dgrad_h2", "wgrad_h2"} <= kinds, kinds
+        assert n_seq.get("split2h", 0) > 0 and n_seq.get("_h2w_launch", 0) > 0 and n_seq.get("Dconv3Bank.refresh", 0) > 0, n_seq
+        mix, n_mix, kinds_mix = run(cpu_nets, "f0 f1 b0 b1")
+        assert kinds_mix == kinds
+        for (o_s, g_s, _), (o_m, g_m, _) in zip(seq, mix):
+            assert all(torch.equal(a, b) for a, b in zip(o_s, o_m)), "outputs differ between the two orders"
+            assert sorted(g_s) == sorted(g_m)
+            bad = [n for n in g_s if not torch.equal(g_s[n], g_m[n])]
+            assert not bad, bad[:8]
+        assert not torch.equal(seq[0][0][1], seq[1][0][1]), "the two networks are different ones"
+        print("launches, sequential order:", n_seq, "interleaved order:", n_mix)
+        for name in set(n_seq) | set(n_mix):
+            assert n_mix.get(name, 0) <= n_seq.get(name, 0), (name, n_seq, n_mix)
+        for res in (seq, mix):
+            for i in (0, 1):
+                net, other = res[i][2], res[1 - i][2]
+                bank, own, foreign = net._h2w_images, net.flat().flat.untyped_storage().data_ptr(), other.flat().flat.untyped_storage().data_ptr()
+                assert bank and len(bank) == len(other._h2w_images)
+                assert all(e["w"].untyped_storage().data_ptr() == own for e in bank.values()), "a head bank holds weights of another buffer"
+                assert not any(e["w"].untyped_storage().data_ptr() == foreign for e in bank.values())
+    finally:
+        for n in COUNTED:
+            setattr(ops, n, real[n])
+        ops.Dconv3Bank.refresh, ops.P1Bank.refresh = real_d3, real_p1
+        (ops.PRECISION, ops.B3_MIN_TAPS, ops.B3_MIN_K, ops.B3_MIN_N, ops.B3_MIN_TILES, ops.B3_MIN_WGRAD_ROWS, ops.DCONV3_MIN_ROWS) = saved
+        ops.PROFILE = None
+        ops.release_b3_cache()
