@@ -34,7 +34,7 @@ extern "C" {
 typedef void* catseg_stream_t; /* hipStream_t */
 
 const char* catseg_last_error(void);
-int catseg_version(void);
+int catseg_version(void);   /* 2: catseg_bn_apply / catseg_bn_backward take a descriptor, catseg_add_n_act its records */
 
 /* ---- convolution as implicit GEMM on v_mfma_f32_32x32x2_f32 ------------------------------
  * replaces F.conv2d behind nn.Conv2d at models/OCR.py:72-97,200-235,308-313 and
@@ -241,16 +241,15 @@ int catseg_dconv3(int B, int H, int W, int C, const float* x, int ldx, const voi
 /* backward-data of a BasicBlock's SECOND convolution fused with the first pass of the backward of the relu(bn1(q)) that produced
  * its input (models/HRNetv2.py:36-47: out = relu(bn1(conv1(x))); conv2(out)): g = (dy (*) w^T) where relu(bn1(q)) > 0 (the mask is
  * recomputed from q, stats = [mean(C), invstd(C)], gamma, beta with the forward's exact expression), and part[n_tiles][2][C] = per
- * tile sum of g and of g * xhat -- what the first pass of catseg_bn_backward computes from (dz, q).  catseg_bn_backward_pre finishes. */
+ * tile sum of g and of g * xhat -- what the first pass of catseg_bn_backward computes from (dz, q).  catseg_bn_backward given these partials finishes. */
 int catseg_dconv3_bnbwd(int B, int H, int W, int C, const float* dy, int lddy, const void* wimg_bwd, float* g, int ldg, const float* q,
                         int ldq, const float* stats, const float* gamma, const float* beta, float* part, size_t part_floats,
                         catseg_stream_t stream);
 /* The same direct kernels on TWO fp16 planes and THREE products (csrc/dconv3_f16x2.hip = dconv3_b3.hip compiled with DC_H2; the
  * arithmetic of catseg_conv2d_fwd_f16x2_blocked).  The activation is split inside the kernel, so its power-of-two prescale comes from a
  * DEVICE amax record of CATSEG_AMAX_RECORD_BYTES = 2048 bytes (16 uint32 slots 128 bytes apart; max over the slots = bits of max|x|
- * over the whole tensor) that the PRODUCER of x accumulated (catseg_bn_apply_amax, catseg_add_n_act_amax, catseg_bn_backward_amax /
- * _pre_amax: one fire-and-forget atomicMax per block into slot blockIdx % 16; the caller zeroes the record before the producer
- * runs).  A record value above the true maximum is safe, one below it overflows fp16.
+ * over the whole tensor) that the PRODUCER of x accumulated (catseg_bn_apply, catseg_add_n_act, catseg_bn_backward given a record:
+ * one fire-and-forget atomicMax per block into slot blockIdx % 16; the caller zeroes the record before the producer runs).  A record value above the true maximum is safe, one below it overflows fp16.
  *   catseg_dconv3_f16x2_prep_batch: as catseg_dconv3_prep_batch (same entry records) + `records`, n x 8 bytes: per weight image
  *                                   {bits of max|w|, exponent}, computed on the device (memset + amax launch + image launch). */
 #define CATSEG_AMAX_RECORD_BYTES 2048
@@ -306,43 +305,19 @@ int catseg_dconv3_pl_bnbwd(int B, int H, int W, int C, const void* dy_planes, co
  * csrc/pointwise.hip).  The exponent is fixed BEFORE the pass from a bound of max| |:
  *   catseg_bn_finalize_counts_bound: catseg_bn_finalize_counts, and z_record[2] = max_c |scale_c| (max|y| + |mean_c|) + |beta_c| (max|y| from
  *                                    y_record, the record catseg_dconv3_pl's epilogue filled)                  [nn.BatchNorm2d training forward]
- *   catseg_bn_apply_planes:          catseg_bn_apply writing planes (+ z itself when z != NULL); exponent from z_record's bound + max|residual|
- *   catseg_add_n_act_planes:         catseg_add_n_act writing out and its planes; exponent from the sum of the terms' max| |  [HRNet fuse sum]
- *   catseg_bn_backward_planes / _pre_planes: catseg_bn_backward / catseg_bn_backward_pre with dy as planes ONLY; bound
- *                                    |gamma invstd| (max|g| + |mean g| + max|xhat| |mean g xhat|) per channel       [autograd of BatchNorm2d] */
+ *   catseg_bn_apply with z_planes:   planes of z (+ z itself when z != NULL); exponent from the record's bound + max|residual|
+ *   catseg_add_n_act with out_planes: out and its planes; exponent from the sum of the terms' max| |                  [HRNet fuse sum]
+ *   catseg_bn_backward with dy_planes: dy as planes ONLY; bound |gamma invstd| (max|g| + |mean g| + max|xhat| |mean g xhat|) per
+ *                                    channel                                                                  [autograd of BatchNorm2d] */
 int catseg_bn_finalize_counts_bound(const float* partials, int n_blocks, const int* counts, long long rows, int C, const float* gamma,
                                     const float* beta, float eps, float momentum, float* running_mean, float* running_var, float* stats_out,
                                     float* scale, const void* y_record, void* z_record, catseg_stream_t stream);
-int catseg_bn_apply_planes(const float* y, int ldy, const float* mean, const float* scale, const float* beta, const float* residual, int ldr,
-                           const void* residual_record, float* z, int ldz, void* z_planes, long long rows, int C, int relu, void* z_record,
-                           catseg_stream_t stream);
-int catseg_add_n_act_planes(const float* const* in, const int* ld, const void* const* term_records, int n, float* out, int ldo, void* out_planes,
-                            long long rows, int C, int relu, void* out_record, catseg_stream_t stream);
-int catseg_bn_backward_planes(const float* dz, int lddz, const float* z, int ldz, const float* y, int ldy, const float* stats, const float* gamma,
-                              const float* beta, long long rows, int C, int relu, void* dy_planes, void* dy_record, void* g_record,
-                              const void* y_record, float* dgamma, float* dbeta, float* dres, int lddres, int dres_accumulate, void* workspace,
-                              size_t workspace_bytes, catseg_stream_t stream);
-int catseg_bn_backward_pre_planes(const float* g, int ldg, const float* q, int ldq, const float* stats, const float* gamma, const float* partials,
-                                  int n_blocks, long long rows, int C, void* dq_planes, void* dq_record, const void* g_record,
-                                  const void* y_record, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
-                                  catseg_stream_t stream);
-/* catseg_bn_backward with dy written ONLY as the blocked fp16 x 2 planes of catseg_split2h (dy_planes: catseg_split2h_blocked_elems(rows, C)
- * halves; dy_scale: its 8-byte record {bits of the bound, e}) -- for a layer whose backward-weight / backward-data run
- * catseg_conv2d_bwd_weight_f16x2_blocked / catseg_conv2d_bwd_data_f16x2_blocked (the BatchNorm behind the head convolutions, models/OCR.py:72-89,
- * 326-333).  dbias (may be null) = column sums of dy (gradient of a convolution bias in front of the BatchNorm).  No residual branch; C % 64 == 0.
- * g_record / y_record / dy_record: three zeroed amax records; they receive max|masked gradient|, max|y| and the bound dy's exponent came from. */
-size_t catseg_bn_backward_h2_workspace(long long rows, int C);
-int catseg_bn_backward_h2(const float* dz, int lddz, const float* z, int ldz, const float* y, int ldy, const float* stats, const float* gamma,
-                          const float* beta, long long rows, int C, int relu, void* dy_planes, void* dy_scale, float* dgamma, float* dbeta,
-                          float* dbias, void* g_record, void* y_record, void* dy_record, void* workspace, size_t workspace_bytes,
-                          catseg_stream_t stream);
-
 /* The K-class classifier of a segmentation head fused with the BatchNorm + ReLU in front of it (csrc/headfuse.h; replaces nn.BatchNorm2d + ReLU +
  * the 1 x 1 nn.Conv2d of models/OCR.py:72-74 (interm_prediction_head[1..4]) and :97 with conv_bn_dropout[1..2], and their autograd): the
  * normalised activation z and its gradient exist in registers only.
  *   catseg_head_fwd       logits[rows][ldl] = relu((y - mean) * scale + beta) Wh^T + bh, columns [K, zero_to) zeroed; Wh [K][C], K <= 32,
  *                         C % 32 == 0, C <= 512; mean / scale as catseg_bn_finalize left them
- *   catseg_head_backward  from dl [rows][lddl] (lddl >= 32): dy as the blocked planes + scale record of catseg_bn_backward_h2 (same three zeroed
+ *   catseg_head_backward  from dl [rows][lddl] (lddl >= 32): dy as the blocked planes + scale record of catseg_bn_backward's dy_h2_planes (same three zeroed
  *                         amax records), dgamma / dbeta of the BatchNorm, dbias (may be null) = column sums of dy, dwh [K][C] and dbh [K]
  *                         (may be null) of the classifier -- all WRITTEN; C % 64 == 0; workspace = catseg_head_backward_workspace bytes;
  *                         every reduction in a fixed order (deterministic) */
@@ -410,58 +385,67 @@ int catseg_bn_finalize_counts(const float* partials, int n_blocks, const int* co
 /* eval mode: scale = gamma / sqrt(running_var + eps) (use with mean = running_mean) */
 int catseg_bn_eval_scale(int C, const float* gamma, const float* running_var, float eps, float* scale,
                          catseg_stream_t stream);
-/* z = act((y - mean) * scale + beta (+ residual)),  act = relu if relu != 0 */
-int catseg_bn_apply(const float* y, int ldy, const float* mean, const float* scale, const float* beta,
-                    const float* residual, int ldr, float* z, int ldz, long long rows, int C, int relu,
-                    catseg_stream_t stream);
-/* backward of the fused op.  g = dz * (z > 0 if relu).  Produces dgamma, dbeta, dy and, when
- * dres != NULL, the residual-branch gradient (dres (+)= g if dres_accumulate).
- * z may be NULL when the forward had no residual branch: the ReLU mask is then recomputed from y, gamma, beta and
- * the saved statistics with the forward's exact expression (one tensor read less in both passes).
- * workspace >= catseg_bn_workspace(rows, C). */
-int catseg_bn_backward(const float* dz, int lddz, const float* z, int ldz, const float* y, int ldy,
-                       const float* stats, const float* gamma, const float* beta, long long rows, int C, int relu,
-                       float* dy, int lddy, float* dgamma, float* dbeta, float* dres, int lddres,
-                       int dres_accumulate, void* workspace, size_t workspace_bytes,
-                       catseg_stream_t stream);
-/* catseg_bn_apply / catseg_bn_backward / catseg_bn_backward_pre / catseg_add_n_act with the output's max |value| folded into
- * amax_record (CATSEG_AMAX_RECORD_BYTES of device memory, zeroed by the caller; NULL = the plain call): the prescale source of
- * catseg_dconv3_f16x2 */
-int catseg_bn_apply_amax(const float* y, int ldy, const float* mean, const float* scale, const float* beta, const float* residual, int ldr,
-                         float* z, int ldz, long long rows, int C, int relu, void* amax_record, catseg_stream_t stream);
-int catseg_bn_backward_amax(const float* dz, int lddz, const float* z, int ldz, const float* y, int ldy, const float* stats,
-                            const float* gamma, const float* beta, long long rows, int C, int relu, float* dy, int lddy, float* dgamma,
-                            float* dbeta, float* dres, int lddres, int dres_accumulate, void* workspace, size_t workspace_bytes,
-                            void* amax_record, catseg_stream_t stream);
-/* The ReLU mask of a residual block's output z = relu(bn(y) + residual) as BITS (catseg_bn_mask_bytes(rows, C) = rows C / 8 bytes: bit (e & 7) of byte
- * e >> 3 for the flat element index e = r C + c; C % 8 == 0): catseg_bn_apply_mask / catseg_bn_apply_planes_mask = catseg_bn_apply_amax /
- * catseg_bn_apply_planes (relu on) that also write the mask; catseg_bn_backward_mask / catseg_bn_backward_planes_mask = catseg_bn_backward_amax /
- * catseg_bn_backward_planes reading the bits instead of z in both passes (nn.BatchNorm2d + residual + ReLU of the blocks of models/HRNetv2.py:36-106
- * and of torchvision's BasicBlock / Bottleneck). */
+/* z = act((y - mean) * scale + beta (+ residual)),  act = relu if relu != 0.  The optional fields that are non-NULL say what is written:
+ *   z_planes == NULL   z (required); record (may be NULL): a zeroed amax record, max|z| is folded into it
+ *   z_planes != NULL   the fp16 x 2 planes of z (catseg_planes_bytes(rows, C); C % 8 == 0), and z itself only when z != NULL.  record
+ *                      (required) is the record catseg_bn_finalize_counts_bound left the bound in: the exponent comes from it (+ max|residual|
+ *                      from residual_record, required with a residual), max|z| is folded into its amax slots
+ *   mask != NULL       also the ReLU mask of z as BITS (catseg_bn_mask_bytes(rows, C) = rows C / 8 bytes: bit (e & 7) of byte e >> 3 for the
+ *                      flat element index e = r C + c); needs relu and C % 8 == 0.  For z = relu(bn(y) + residual) of a residual block
+ *                      (models/HRNetv2.py:36-106, torchvision's BasicBlock / Bottleneck), whose backward then reads 1 bit per element, not z */
+typedef struct {
+  const float* y; int ldy;
+  const float* mean; const float* scale; const float* beta;
+  const float* residual; int ldr;      /* may be NULL */
+  const void* residual_record;
+  float* z; int ldz;
+  void* z_planes;
+  long long rows; int C;
+  int relu;
+  void* record;
+  void* mask;
+} catseg_bn_apply_desc;
 size_t catseg_bn_mask_bytes(long long rows, int C);
-int catseg_bn_apply_mask(const float* y, int ldy, const float* mean, const float* scale, const float* beta, const float* residual, int ldr, float* z,
-                         int ldz, long long rows, int C, void* amax_record, void* mask, catseg_stream_t stream);
-int catseg_bn_backward_mask(const float* dz, int lddz, const void* mask, const float* y, int ldy, const float* stats, const float* gamma,
-                            long long rows, int C, float* dy, int lddy, float* dgamma, float* dbeta, float* dres, int lddres, int dres_accumulate,
-                            void* workspace, size_t workspace_bytes, void* amax_record, catseg_stream_t stream);
-int catseg_bn_apply_planes_mask(const float* y, int ldy, const float* mean, const float* scale, const float* beta, const float* residual, int ldr,
-                                const void* residual_record, float* z, int ldz, void* z_planes, long long rows, int C, void* z_record, void* mask,
-                                catseg_stream_t stream);
-int catseg_bn_backward_planes_mask(const float* dz, int lddz, const void* mask, const float* y, int ldy, const float* stats, const float* gamma,
-                                   long long rows, int C, void* dy_planes, void* dy_record, void* g_record, const void* y_record, float* dgamma,
-                                   float* dbeta, float* dres, int lddres, int dres_accumulate, void* workspace, size_t workspace_bytes,
-                                   catseg_stream_t stream);
-int catseg_bn_backward_pre_amax(const float* g, int ldg, const float* q, int ldq, const float* stats, const float* gamma,
-                                const float* partials, int n_blocks, long long rows, int C, float* dq, int lddq, float* dgamma,
-                                float* dbeta, void* workspace, size_t workspace_bytes, void* amax_record, catseg_stream_t stream);
-int catseg_add_n_act_amax(const float* const* in, const int* ld, int n, float* out, int ldo, long long rows, int C, int relu,
-                          void* amax_record, catseg_stream_t stream);
-/* the rest of catseg_bn_backward when g (already masked) and the per-block sums [n_blocks][2][C] of g and g * xhat come from
- * catseg_dconv3_bnbwd: merges the sums (dgamma, dbeta) and writes dq = gamma * invstd * (g - mean(g) - xhat * mean(g * xhat)).
- * workspace >= 2 * C floats (rounded up to 256 bytes). */
-int catseg_bn_backward_pre(const float* g, int ldg, const float* q, int ldq, const float* stats, const float* gamma,
-                           const float* partials, int n_blocks, long long rows, int C, float* dq, int lddq, float* dgamma,
-                           float* dbeta, void* workspace, size_t workspace_bytes, catseg_stream_t stream);
+int catseg_bn_apply(const catseg_bn_apply_desc* d, catseg_stream_t stream);
+
+/* backward of the fused op.  g = dz * (ReLU mask if relu).  Produces dgamma, dbeta (either may be NULL), the gradient of y in ONE of three
+ * forms and, when dres != NULL, the residual-branch gradient (dres (+)= g if dres_accumulate).
+ *   ReLU mask (relu != 0)  from z; or from the bits in mask (as catseg_bn_apply wrote them; C % 8 == 0; z is then not read and must be NULL);
+ *                          or, with neither and no residual branch, recomputed from y, gamma, beta and the saved statistics with the
+ *                          forward's exact expression (one tensor read less in both passes)
+ *   partials != NULL       dz is already masked and [n_blocks][2][C] per-block sums of g and g * xhat exist (catseg_dconv3_bnbwd and its
+ *                          kin): the first pass is skipped.  Not with relu, z, mask, dres or the h2 output; workspace >= 2 C floats
+ *                          (rounded up to 256 bytes), catseg_bn_workspace(rows, C) otherwise
+ *   dy                     fp32 [rows][lddy]; dy_record (may be NULL): a zeroed amax record, max|dy| is folded into it; g_record and
+ *                          y_record must be NULL
+ *   dy_planes              the fp16 x 2 planes of catseg_planes_bytes(rows, C) ONLY (C % 8 == 0).  g_record: a zeroed amax record that
+ *                          receives max|g| (with partials: the one their producer filled); y_record: max|y| of the forward pass;
+ *                          dy_record: zeroed, receives the bound the exponent comes from, and the exponent
+ *   dy_h2_planes           ONLY the blocked fp16 x 2 planes of catseg_split2h (catseg_split2h_blocked_elems(rows, C) halves) with
+ *                          dy_h2_scale, their 8-byte record {bits of the bound, e} -- for a layer whose backward-weight / backward-data run
+ *                          catseg_conv2d_bwd_weight_f16x2_blocked / catseg_conv2d_bwd_data_f16x2_blocked (the BatchNorm behind the head
+ *                          convolutions, models/OCR.py:72-89, 326-333).  dbias (may be NULL) = column sums of dy (gradient of a convolution
+ *                          bias in front of the BatchNorm).  No residual branch, no mask; C % 64 == 0; the planes below 4 GB; g_record /
+ *                          y_record / dy_record: three zeroed amax records, they receive max|g|, max|y| and the bound;
+ *                          workspace >= catseg_bn_backward_h2_workspace(rows, C) */
+typedef struct {
+  const float* dz; int lddz;
+  const float* y; int ldy;
+  const float* stats;                  /* [mean(C), invstd(C)] */
+  const float* gamma;
+  long long rows; int C;
+  int relu; const float* z; int ldz; const float* beta; const void* mask;
+  const float* partials; int n_blocks;
+  float* dres; int lddres; int dres_accumulate;
+  void* g_record; void* y_record; void* dy_record;
+  float* dgamma; float* dbeta;
+  void* workspace; size_t workspace_bytes;
+  float* dy; int lddy;
+  void* dy_planes;
+  void* dy_h2_planes; void* dy_h2_scale; float* dbias;
+} catseg_bn_backward_desc;
+size_t catseg_bn_backward_h2_workspace(long long rows, int C);
+int catseg_bn_backward(const catseg_bn_backward_desc* d, catseg_stream_t stream);
 /* eval-mode / frozen-statistics backward is not on the training path and is not provided. */
 
 /* ---- layout / pointwise helpers ---------------------------------------------------------- */
@@ -478,9 +462,11 @@ int catseg_stem_unpack_grad(const float* packed_grad, float* dw_ohwi, int O, cat
 /* dst[p, c] (+)= alpha * src[p, c] */
 int catseg_axpy2d(const float* src, int lds, float* dst, int ldd, long long rows, int C, float alpha,
                   int accumulate, catseg_stream_t stream);
-/* out = act(in_0 + ... + in_{n-1}), n <= 4 (HRNet fuse sum, models/HRNetv2.py:237-261); g = dz * (z > 0) */
-int catseg_add_n_act(const float* const* in, const int* ld, int n, float* out, int ldo, long long rows, int C,
-                     int relu, catseg_stream_t stream);
+/* out = act(in_0 + ... + in_{n-1}), n <= 4 (HRNet fuse sum, models/HRNetv2.py:237-261).  term_records and out_planes both NULL: out_record
+ * (may be NULL) is a zeroed amax record, max|out| is folded into it.  Both given (C % 8 == 0, out_record required): the fp16 x 2 planes of out
+ * are written too, with the exponent from the SUM of the terms' max| | (term_records[i] = the amax record of in[i]).  g = dz * (z > 0) */
+int catseg_add_n_act(const float* const* in, const int* ld, const void* const* term_records, int n, float* out, int ldo, void* out_planes,
+                     long long rows, int C, int relu, void* out_record, catseg_stream_t stream);
 int catseg_relu_bwd(const float* dz, int lddz, const float* z, int ldz, float* g, int ldg, long long rows, int C,
                     catseg_stream_t stream);
 /* conv weight [O][taps][cin] -> zero-padded [O][taps][cpad] (unpad = 0) or back (unpad = 1): lets a

@@ -27,6 +27,19 @@ class ConvDesc(C.Structure):
                                  "ldx", "ldy", "stem4", "groups")]
 
 
+# catseg_bn_apply_desc / catseg_bn_backward_desc, filled by keyword: a field left out is NULL / 0
+class BnApplyDesc(C.Structure):
+    _fields_ = [("y", P), ("ldy", I), ("mean", P), ("scale", P), ("beta", P), ("residual", P), ("ldr", I), ("residual_record", P), ("z", P), ("ldz", I),
+                ("z_planes", P), ("rows", L), ("C", I), ("relu", I), ("record", P), ("mask", P)]
+
+
+class BnBackwardDesc(C.Structure):
+    _fields_ = [("dz", P), ("lddz", I), ("y", P), ("ldy", I), ("stats", P), ("gamma", P), ("rows", L), ("C", I), ("relu", I), ("z", P), ("ldz", I),
+                ("beta", P), ("mask", P), ("partials", P), ("n_blocks", I), ("dres", P), ("lddres", I), ("dres_accumulate", I), ("g_record", P),
+                ("y_record", P), ("dy_record", P), ("dgamma", P), ("dbeta", P), ("workspace", P), ("workspace_bytes", SZ), ("dy", P), ("lddy", I),
+                ("dy_planes", P), ("dy_h2_planes", P), ("dy_h2_scale", P), ("dbias", P)]
+
+
 _SIGS = {
     "catseg_last_error": (C.c_char_p, []),
     "catseg_version": (I, []),
@@ -62,12 +75,7 @@ _SIGS = {
     "catseg_dwgrad3_pl_workspace": (SZ, [I, I, I, I]),
     "catseg_dwgrad3_pl": (I, [I, I, I, I, P, P, P, P, P, P, SZ, P]),
     "catseg_bn_finalize_counts_bound": (I, [P, I, P, L, I, P, P, F, F, P, P, P, P, P, P, P]),
-    "catseg_bn_apply_planes": (I, [P, I, P, P, P, P, I, P, P, I, P, L, I, I, P, P]),
-    "catseg_add_n_act_planes": (I, [P, P, P, I, P, I, P, L, I, I, P, P]),
-    "catseg_bn_backward_planes": (I, [P, I, P, I, P, I, P, P, P, L, I, I, P, P, P, P, P, P, P, I, I, P, SZ, P]),
-    "catseg_bn_backward_pre_planes": (I, [P, I, P, I, P, P, P, I, L, I, P, P, P, P, P, P, P, SZ, P]),
     "catseg_bn_backward_h2_workspace": (SZ, [L, I]),
-    "catseg_bn_backward_h2": (I, [P, I, P, I, P, I, P, P, P, L, I, I, P, P, P, P, P, P, P, P, P, SZ, P]),
     "catseg_head_fwd": (I, [P, I, P, P, P, P, P, I, L, I, P, I, I, P]),
     "catseg_head_backward_workspace": (SZ, [L, I]),
     "catseg_head_backward": (I, [P, I, P, I, P, P, P, P, I, L, I, P, P, P, P, P, P, P, P, P, P, P, SZ, P]),
@@ -79,15 +87,7 @@ _SIGS = {
     "catseg_maxpool2x2_fwd": (I, [P, I, P, I, P, I, I, I, I, P]),
     "catseg_maxpool2x2_bwd": (I, [P, I, P, P, I, I, I, I, I, P]),
     "catseg_bias_rows": (I, [P, P, I, L, I, P]),
-    "catseg_bn_apply_amax": (I, [P, I, P, P, P, P, I, P, I, L, I, I, P, P]),
-    "catseg_bn_backward_amax": (I, [P, I, P, I, P, I, P, P, P, L, I, I, P, I, P, P, P, I, I, P, SZ, P, P]),
     "catseg_bn_mask_bytes": (SZ, [L, I]),
-    "catseg_bn_apply_mask": (I, [P, I, P, P, P, P, I, P, I, L, I, P, P, P]),
-    "catseg_bn_backward_mask": (I, [P, I, P, P, I, P, P, L, I, P, I, P, P, P, I, I, P, SZ, P, P]),
-    "catseg_bn_apply_planes_mask": (I, [P, I, P, P, P, P, I, P, P, I, P, L, I, P, P, P]),
-    "catseg_bn_backward_planes_mask": (I, [P, I, P, P, I, P, P, L, I, P, P, P, P, P, P, P, I, I, P, SZ, P]),
-    "catseg_bn_backward_pre_amax": (I, [P, I, P, I, P, P, P, I, L, I, P, I, P, P, P, SZ, P, P]),
-    "catseg_add_n_act_amax": (I, [P, P, I, P, I, L, I, I, P, P]),
     "catseg_conv2d_fwd_fused": (I, [P, P, P, P, P, I, I, P, P]),
     "catseg_fold_bn": (I, [P, P, P, P, P, P, F, I, I, P, P, P]),
     "catseg_conv2d_bwd_data": (I, [P, P, P, P, I, P]),
@@ -153,15 +153,14 @@ _SIGS = {
     "catseg_bn_workspace": (SZ, [L, I]),
     "catseg_bn_train_stats": (I, [P, L, I, I, P, F, F, P, P, P, P, P, SZ, P]),
     "catseg_bn_eval_scale": (I, [I, P, P, F, P, P]),
-    "catseg_bn_apply": (I, [P, I, P, P, P, P, I, P, I, L, I, I, P]),
-    "catseg_bn_backward": (I, [P, I, P, I, P, I, P, P, P, L, I, I, P, I, P, P, P, I, I, P, SZ, P]),
-    "catseg_bn_backward_pre": (I, [P, I, P, I, P, P, P, I, L, I, P, I, P, P, P, SZ, P]),
+    "catseg_bn_apply": (I, [P, P]),
+    "catseg_bn_backward": (I, [P, P]),
     "catseg_nchw3_to_nhwc4": (I, [P, P, I, I, I, P]),
     "catseg_nchw3_to_nhwc4_norm": (I, [P, P, I, I, I, P, P, P]),
     "catseg_stem_pack_weight": (I, [P, P, I, P]),
     "catseg_stem_unpack_grad": (I, [P, P, I, P]),
     "catseg_axpy2d": (I, [P, I, P, I, L, I, F, I, P]),
-    "catseg_add_n_act": (I, [P, P, I, P, I, L, I, I, P]),
+    "catseg_add_n_act": (I, [P, P, P, I, P, I, P, L, I, I, P, P]),
     "catseg_relu_bwd": (I, [P, I, P, I, P, I, L, I, P]),
     "catseg_weight_pad_cin": (I, [P, P, I, I, I, I, I, P]),
     "catseg_scale_by_device_scalar": (I, [P, L, P, P]),
@@ -240,7 +239,7 @@ if os.environ.get("CATSEG_SYNC"):  # debugging aid: synchronise after every entr
                 return fn
 
             def call(*a):
-                desc = [[getattr(x._obj, f) for f, _ in x._obj._fields_] for x in a if isinstance(getattr(x, "_obj", None), ConvDesc)]
+                desc = [{f: getattr(x._obj, f) for f, _ in x._obj._fields_} for x in a if isinstance(getattr(x, "_obj", None), C.Structure)]
                 print("[catseg]", name, desc, [x for x in a if isinstance(x, (int, float))], flush=True)
                 rc = fn(*a)
                 torch.cuda.synchronize()

@@ -20,7 +20,7 @@
 //
 // This file compiles twice.  As it is: three bf16 planes, six products (the text above).  Through dconv3_f16x2.hip (-DDC_H2): TWO fp16
 // planes and THREE products, the arithmetic of igemm_f16x2.hip -- the activation is scaled by 2^e (e from the 8-byte amax record its
-// PRODUCER filled: catseg_bn_apply_amax / catseg_add_n_act_amax / catseg_bn_backward_amax) while it is split in registers, the weight
+// PRODUCER filled: catseg_bn_apply / catseg_add_n_act / catseg_bn_backward given a record) while it is split in registers, the weight
 // image carries its own exponent, the epilogue scales the accumulators back; entry points catseg_dconv3_f16x2*.
 #include "common.h"
 
@@ -1155,7 +1155,7 @@ extern "C" int catseg_dconv3_f16x2_prep_batch(const float* flat, int n, const vo
 }
 
 // catseg_dconv3 on two fp16 planes: x_record = the activation's amax record (16 words 128 bytes apart, their max = bits of max|x| over
-// the WHOLE tensor, as its producer left it: catseg_bn_apply_amax, catseg_add_n_act_amax, catseg_bn_backward(_pre)_amax; a larger value is safe, a
+// the WHOLE tensor, as its producer left it: catseg_bn_apply, catseg_add_n_act, catseg_bn_backward given a record; a larger value is safe, a
 // smaller one overflows fp16), w_record = the weight image's record from catseg_dconv3_f16x2_prep_batch
 extern "C" int catseg_dconv3_f16x2(int B, int H, int W, int C, const float* x, int ldx, const void* x_record, const void* wimg,
                                    const void* w_record, const float* bias, float* y, int ldy, int accumulate, float* bn_part,

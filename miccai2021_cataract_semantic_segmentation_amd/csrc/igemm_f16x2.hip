@@ -1176,8 +1176,8 @@ extern "C" int catseg_split2h(const float* x, long long rows, int C, int ld, voi
   return CATSEG_OK;
 }
 
-// catseg_split2h without its pass over x for max|x|: the producers of x left amax records (catseg_bn_apply_amax, catseg_bn_backward_amax,
-// catseg_add_n_act_amax ...; bilinear resizing and copies keep their input's), up to four of them for the channel slices of a concatenation
+// catseg_split2h without its pass over x for max|x|: the producers of x left amax records (catseg_bn_apply, catseg_bn_backward,
+// catseg_add_n_act ... given a record; bilinear resizing and copies keep their input's), up to four of them for the channel slices of a concatenation
 // (null = unused).  The records must bound |x| (an exact maximum or an upper bound: the exponent only has to keep x * 2^e inside fp16).
 extern "C" int catseg_split2h_bound(const float* x, long long rows, int C, int ld, void* blocked_planes, void* planar_planes, void* scale,
                                     const void* rec0, const void* rec1, const void* rec2, const void* rec3, catseg_stream_t stream) {

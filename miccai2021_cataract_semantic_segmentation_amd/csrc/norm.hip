@@ -116,8 +116,8 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict
 __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restrict__ part, int nrb, long long rpb, long long rows, int C,
                                                            const float* __restrict__ gamma, float eps, float momentum, float* running_mean,
                                                            float* running_var, float* __restrict__ stats, float* __restrict__ scale,
-                                                           const int* __restrict__ counts, const unsigned* __restrict__ y_rec = nullptr,
-                                                           unsigned* __restrict__ z_rec = nullptr, const float* __restrict__ beta = nullptr) {
+                                                           const int* __restrict__ counts, const unsigned* __restrict__ y_rec,
+                                                           unsigned* __restrict__ z_rec, const float* __restrict__ beta) {
   const int cl = threadIdx.x & 3, rl = threadIdx.x >> 2;
   const int c = blockIdx.x * 4 + cl;
   const bool live = c < C;
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
   if (z_rec) {
     // bound of the normalised output of this channel, BEFORE the pass that computes it: |fma(y - mean, scale, beta)| <= |scale| (max|y| +
     // |mean|) + |beta|, with max|y| from the convolution's epilogue (csrc/dconv3_pl.hip).  The maximum over the channels (positive floats
-    // order like their bit patterns) is what catseg_bn_apply_planes derives the planes' exponent from (csrc/planes.h).
+    // order like their bit patterns) is what catseg_bn_apply derives the planes' exponent from (csrc/planes.h).
     // Evaluated in fp64 from the fp32 mean and invstd just stored, rounded once: in fp32 its five roundings put it up to ~5 ulp above the formula.
     const float bound = (float)((fabs((double)gam * (double)invstd) * ((double)__uint_as_float(ym) + fabs((double)(float)mean)) + fabs((double)bet)) * 1.001);
     atomicMax(z_rec + CS_REC_BOUND, __float_as_uint(bound));
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
                                                        const float* __restrict__ scale, const float* __restrict__ beta,
                                                        const float* __restrict__ res, int ldr, float* __restrict__ z,
                                                        int ldz, long long rows, int C, int relu, unsigned* __restrict__ amax,
-                                                       unsigned char* __restrict__ mask = nullptr) {
+                                                       unsigned char* __restrict__ mask) {
   const int cpt = C >> 2;
   unsigned m = 0;
   CS_QUAD_LOOP(rows, cpt, r, c) {
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(256) void bn_apply_planes_kernel(const float* __res
                                                               const float* __restrict__ res, int ldr, const unsigned* __restrict__ res_rec,
                                                               float* __restrict__ zf, int ldz, unsigned char* __restrict__ planes,
                                                               long long rows, int C, int relu, unsigned* __restrict__ rec,
-                                                              unsigned char* __restrict__ mask = nullptr) {
+                                                              unsigned char* __restrict__ mask) {
   __shared__ __attribute__((aligned(16))) unsigned char sm[CsPlaneTile::BYTES];
   float bound = __uint_as_float(rec[CS_REC_BOUND]);
   if (res) bound += __uint_as_float(cs_amax_read(res_rec));
@@ -324,9 +324,9 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __rest
                                                              int ldz, const float* __restrict__ y, int ldy,
                                                              const float* __restrict__ stats, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, long long rows, int C, int relu,
-                                                             RowSplit s, float* __restrict__ part, unsigned* __restrict__ gmax_rec = nullptr,
-                                                             unsigned* __restrict__ ymax_rec = nullptr,
-                                                             const unsigned char* __restrict__ mask = nullptr) {
+                                                             RowSplit s, float* __restrict__ part, unsigned* __restrict__ gmax_rec,
+                                                             unsigned* __restrict__ ymax_rec,
+                                                             const unsigned char* __restrict__ mask) {
   const int t = threadIdx.x;
   const int cg = blockIdx.y * s.tpr + t % s.tpr;
   const int rl = t / s.tpr;
@@ -431,9 +431,9 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __rest
 // of ~8 L2 round trips on 3 - 24 blocks); fixed summation order
 __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __restrict__ part, int nrb, long long rows, int C,
                                                                float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ coef,
-                                                               const unsigned* __restrict__ gmax_rec = nullptr,
-                                                               const unsigned* __restrict__ y_rec = nullptr, const float* __restrict__ stats = nullptr,
-                                                               const float* __restrict__ gamma = nullptr, unsigned* __restrict__ dy_rec = nullptr) {
+                                                               const unsigned* __restrict__ gmax_rec,
+                                                               const unsigned* __restrict__ y_rec, const float* __restrict__ stats,
+                                                               const float* __restrict__ gamma, unsigned* __restrict__ dy_rec) {
   const int cl = threadIdx.x & 3, rl = threadIdx.x >> 2;
   const int c = blockIdx.x * 4 + cl;
   const bool live = c < C;
@@ -500,7 +500,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_planes_kernel(const float* _
                                                                   const float* __restrict__ coef, long long rows, int C, int relu,
                                                                   unsigned char* __restrict__ planes, unsigned* __restrict__ rec,
                                                                   float* __restrict__ dres, int lddres, int dres_acc,
-                                                                  const unsigned char* __restrict__ mask = nullptr) {
+                                                                  const unsigned char* __restrict__ mask) {
   __shared__ __attribute__((aligned(16))) unsigned char sm[CsPlaneTile::BYTES];
   const int e = cs_plane_exponent(rec[CS_REC_BOUND]);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -667,7 +667,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                                                            const float* __restrict__ beta, const float* __restrict__ coef, long long rows, int C,
                                                            int relu, float* __restrict__ dy, int lddy, float* __restrict__ dres, int lddres,
                                                            int dres_acc, unsigned* __restrict__ amax,
-                                                           const unsigned char* __restrict__ mask = nullptr) {
+                                                           const unsigned char* __restrict__ mask) {
   const int cpt = C >> 2;
   unsigned m = 0;
   CS_QUAD_LOOP(rows, cpt, r, c) {
@@ -746,7 +746,8 @@ extern "C" int catseg_bn_train_stats(const float* y, long long rows, int C, int 
   float* part = (float*)workspace;
   hipLaunchKernelGGL(bn_partial_kernel, dim3(s.nrb, s.gy), dim3(256), 0, st, y, ldy, rows, C, s, part);
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(1024), 0, st, (const float*)part, s.nrb, s.rpb, rows, C,
-                     gamma, eps, momentum, running_mean, running_var, stats_out, scale, (const int*)nullptr);
+                     gamma, eps, momentum, running_mean, running_var, stats_out, scale, (const int*)nullptr,
+                     (const unsigned*)nullptr, (unsigned*)nullptr, (const float*)nullptr);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
 }
@@ -759,7 +760,8 @@ extern "C" int catseg_bn_finalize(const float* partials, int n_blocks, long long
   CS_REQUIRE(partials && n_blocks > 0 && rows > 0 && C > 0 && (long long)(n_blocks - 1) * rows_per_block < rows &&
                  (long long)n_blocks * rows_per_block >= rows, "bn finalize: bad args");
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(1024), 0, (hipStream_t)stream, partials, n_blocks, rows_per_block, rows, C,
-                     gamma, eps, momentum, running_mean, running_var, stats_out, scale, (const int*)nullptr);
+                     gamma, eps, momentum, running_mean, running_var, stats_out, scale, (const int*)nullptr,
+                     (const unsigned*)nullptr, (unsigned*)nullptr, (const float*)nullptr);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
 }
@@ -770,7 +772,8 @@ extern "C" int catseg_bn_finalize_counts(const float* partials, int n_blocks, co
                                          catseg_stream_t stream) {
   CS_REQUIRE(partials && counts && n_blocks > 0 && rows > 0 && C > 0, "bn finalize (counts): bad args");
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(1024), 0, (hipStream_t)stream, partials, n_blocks, (long long)1, rows, C,
-                     gamma, eps, momentum, running_mean, running_var, stats_out, scale, counts);
+                     gamma, eps, momentum, running_mean, running_var, stats_out, scale, counts,
+                     (const unsigned*)nullptr, (unsigned*)nullptr, (const float*)nullptr);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
 }
@@ -783,98 +786,6 @@ extern "C" int catseg_bn_eval_scale(int C, const float* gamma, const float* runn
   return CATSEG_OK;
 }
 
-extern "C" int catseg_bn_apply_amax(const float* y, int ldy, const float* mean, const float* scale, const float* beta, const float* residual,
-                                    int ldr, float* z, int ldz, long long rows, int C, int relu, void* amax_record, catseg_stream_t stream);
-extern "C" int catseg_bn_apply(const float* y, int ldy, const float* mean, const float* scale, const float* beta,
-                               const float* residual, int ldr, float* z, int ldz, long long rows, int C, int relu,
-                               catseg_stream_t stream) {
-  return catseg_bn_apply_amax(y, ldy, mean, scale, beta, residual, ldr, z, ldz, rows, C, relu, nullptr, stream);
-}
-// the same, and max|z| folded into amax_record[0] (the 8-byte per-tensor record of catseg_dconv3_f16x2; zeroed by the caller; may be null)
-extern "C" int catseg_bn_apply_amax(const float* y, int ldy, const float* mean, const float* scale, const float* beta, const float* residual,
-                                    int ldr, float* z, int ldz, long long rows, int C, int relu, void* amax_record, catseg_stream_t stream) {
-  CS_REQUIRE(rows > 0 && C > 0 && C % 4 == 0 && ldy % 4 == 0 && ldz % 4 == 0 && (residual == nullptr || ldr % 4 == 0),
-             "bn apply: C and ld must be multiples of 4");
-  CS_REQUIRE(cs_aligned16(y) && cs_aligned16(z) && cs_aligned16(mean) && cs_aligned16(scale) && cs_aligned16(beta) &&
-                 cs_aligned16(residual), "bn apply: alignment");
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(rows * (C / 4))), dim3(256), 0, (hipStream_t)stream, y, ldy, mean, scale,
-                     beta, residual, ldr, z, ldz, rows, C, relu, (unsigned*)amax_record);
-  CS_LAUNCH_CHECK();
-  return CATSEG_OK;
-}
-
-extern "C" int catseg_bn_backward_amax(const float* dz, int lddz, const float* z, int ldz, const float* y, int ldy, const float* stats,
-                                       const float* gamma, const float* beta, long long rows, int C, int relu, float* dy, int lddy,
-                                       float* dgamma, float* dbeta, float* dres, int lddres, int dres_accumulate, void* workspace,
-                                       size_t workspace_bytes, void* amax_record, catseg_stream_t stream);
-extern "C" int catseg_bn_backward(const float* dz, int lddz, const float* z, int ldz, const float* y, int ldy,
-                                  const float* stats, const float* gamma, const float* beta, long long rows, int C, int relu,
-                                  float* dy, int lddy, float* dgamma, float* dbeta, float* dres, int lddres,
-                                  int dres_accumulate, void* workspace, size_t workspace_bytes,
-                                  catseg_stream_t stream) {
-  return catseg_bn_backward_amax(dz, lddz, z, ldz, y, ldy, stats, gamma, beta, rows, C, relu, dy, lddy, dgamma, dbeta, dres, lddres, dres_accumulate,
-                                 workspace, workspace_bytes, nullptr, stream);
-}
-// the same, and max|dy| folded into amax_record[0] (may be null)
-extern "C" int catseg_bn_backward_amax(const float* dz, int lddz, const float* z, int ldz, const float* y, int ldy, const float* stats,
-                                       const float* gamma, const float* beta, long long rows, int C, int relu, float* dy, int lddy,
-                                       float* dgamma, float* dbeta, float* dres, int lddres, int dres_accumulate, void* workspace,
-                                       size_t workspace_bytes, void* amax_record, catseg_stream_t stream) {
-  CS_REQUIRE(rows > 0 && C > 0 && C % 4 == 0 && lddz % 4 == 0 && ldy % 4 == 0 && lddy % 4 == 0, "bn bwd: C and ld must be multiples of 4");
-  CS_REQUIRE(!relu || (z != nullptr && ldz % 4 == 0) || (z == nullptr && beta != nullptr && dres == nullptr),
-             "bn bwd: relu needs z, or (no residual branch) beta to recompute the mask from y");
-  CS_REQUIRE(cs_aligned16(dz) && cs_aligned16(y) && cs_aligned16(dy) && cs_aligned16(stats) && cs_aligned16(gamma) &&
-                 cs_aligned16(z) && cs_aligned16(dres), "bn bwd: alignment");
-  if (workspace_bytes < catseg_bn_workspace(rows, C) || !workspace) {
-    catseg_set_error("bn bwd: workspace too small");
-    return CATSEG_EWORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const RowSplit s = plan_rows(rows, C);
-  float* part = (float*)workspace;
-  float* coef = part + (size_t)kMaxRowBlocks * 3 * ((C + 3) & ~3);
-  hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(s.nrb, s.gy), dim3(256), 0, st, dz, lddz, z, ldz, y, ldy, stats, gamma, beta, rows, C, relu, s, part);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(1024), 0, st, (const float*)part, s.nrb, rows, C, dgamma, dbeta, coef);
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(rows * (C / 4))), dim3(256), 0, st, dz, lddz, z, ldz, y, ldy, stats, gamma,
-                     beta, (const float*)coef, rows, C, relu, dy, lddy, dres, lddres, dres_accumulate, (unsigned*)amax_record);
-  CS_LAUNCH_CHECK();
-  return CATSEG_OK;
-}
-
-// backward of z = relu(bn(q)) when the producer of dz has already masked it (g = dz where z > 0) and left the per-block sums
-// [n_blocks][2][C] of g and g * xhat (catseg_dconv3_bnbwd): the merge of the sums and the apply pass, i.e. catseg_bn_backward
-// without its first pass over (dz, q)
-extern "C" int catseg_bn_backward_pre_amax(const float* g, int ldg, const float* q, int ldq, const float* stats, const float* gamma,
-                                           const float* partials, int n_blocks, long long rows, int C, float* dq, int lddq, float* dgamma,
-                                           float* dbeta, void* workspace, size_t workspace_bytes, void* amax_record, catseg_stream_t stream);
-extern "C" int catseg_bn_backward_pre(const float* g, int ldg, const float* q, int ldq, const float* stats, const float* gamma,
-                                      const float* partials, int n_blocks, long long rows, int C, float* dq, int lddq, float* dgamma,
-                                      float* dbeta, void* workspace, size_t workspace_bytes, catseg_stream_t stream) {
-  return catseg_bn_backward_pre_amax(g, ldg, q, ldq, stats, gamma, partials, n_blocks, rows, C, dq, lddq, dgamma, dbeta, workspace, workspace_bytes,
-                                     nullptr, stream);
-}
-extern "C" int catseg_bn_backward_pre_amax(const float* g, int ldg, const float* q, int ldq, const float* stats, const float* gamma,
-                                           const float* partials, int n_blocks, long long rows, int C, float* dq, int lddq, float* dgamma,
-                                           float* dbeta, void* workspace, size_t workspace_bytes, void* amax_record, catseg_stream_t stream) {
-  CS_REQUIRE(rows > 0 && C > 0 && C % 4 == 0 && ldg % 4 == 0 && ldq % 4 == 0 && lddq % 4 == 0 && n_blocks > 0 && partials,
-             "bn bwd (pre): C and ld must be multiples of 4");
-  CS_REQUIRE(cs_aligned16(g) && cs_aligned16(q) && cs_aligned16(dq) && cs_aligned16(stats) && cs_aligned16(gamma), "bn bwd (pre): alignment");
-  const size_t need = cs_align_up((size_t)2 * ((C + 3) & ~3) * 4, 256);
-  if (workspace_bytes < need || !workspace) {
-    catseg_set_error("bn bwd (pre): workspace too small");
-    return CATSEG_EWORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  float* coef = (float*)workspace;
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(1024), 0, st, partials, n_blocks, rows, C, dgamma, dbeta, coef);
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(rows * (C / 4))), dim3(256), 0, st, g, ldg, (const float*)nullptr, 0, q, ldq, stats,
-                     gamma, (const float*)nullptr, (const float*)coef, rows, C, 0, dq, lddq, (float*)nullptr, 0, 0, (unsigned*)amax_record);
-  CS_LAUNCH_CHECK();
-  return CATSEG_OK;
-}
-
-
-// ---- producers of fp16 x 2 operand planes (csrc/planes.h; round 4) ---------------------------------------------------------------------------
 // catseg_bn_finalize_counts + the bound of the normalised output: z_record[CS_REC_BOUND] = max over the channels of
 // |scale| (max|y| + |mean|) + |beta|, with max|y| from y_record (the amax slots catseg_dconv3_pl's epilogue filled)
 extern "C" int catseg_bn_finalize_counts_bound(const float* partials, int n_blocks, const int* counts, long long rows, int C, const float* gamma,
@@ -887,206 +798,108 @@ extern "C" int catseg_bn_finalize_counts_bound(const float* partials, int n_bloc
   return CATSEG_OK;
 }
 
-// catseg_bn_apply that writes the planes of z (z_planes, catseg_planes_bytes(rows, C)) with the exponent derived from z_record's bound
-// (+ max|residual| from residual_record), z itself only when z != NULL, and folds max|z| into z_record's amax slots
-extern "C" int catseg_bn_apply_planes(const float* y, int ldy, const float* mean, const float* scale, const float* beta, const float* residual,
-                                      int ldr, const void* residual_record, float* z, int ldz, void* z_planes, long long rows, int C, int relu,
-                                      void* z_record, catseg_stream_t stream) {
-  CS_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && ldy % 4 == 0 && (z == nullptr || ldz % 4 == 0) && (residual == nullptr || (ldr % 4 == 0 && residual_record)),
-             "bn apply (planes): C must be a multiple of 8, ld of 4; a residual needs its amax record");
-  CS_REQUIRE(cs_aligned16(y) && cs_aligned16(z) && cs_aligned16(mean) && cs_aligned16(scale) && cs_aligned16(beta) && cs_aligned16(residual) &&
-                 cs_aligned16(z_planes) && z_planes && z_record, "bn apply (planes): alignment");
+// blocks of the kernels that walk the 128-row x 64-channel tiles of CsPlaneTile (csrc/planes.h) and stride over the rest
+static int plane_tile_grid(long long rows, int C) {
   const long long tiles = ((rows + 127) / 128) * ((C / 8 + 7) / 8);
-  hipLaunchKernelGGL(bn_apply_planes_kernel, dim3((int)(tiles > 8192 ? 8192 : tiles)), dim3(256), 0, (hipStream_t)stream, y, ldy, mean, scale, beta,
-                     residual, ldr, (const unsigned*)residual_record, z, ldz, (unsigned char*)z_planes, rows, C, relu, (unsigned*)z_record);
+  return (int)(tiles > 8192 ? 8192 : tiles);
+}
+
+// ---- BatchNorm apply (include/catseg.h: catseg_bn_apply_desc).  z_planes selects bn_apply_planes_kernel, which takes the exponent of the planes
+// from the bound catseg_bn_finalize_counts_bound left in the record (+ max|residual| from the residual's own record); mask: the ReLU mask of z
+// as bits, rows x C / 8 bytes, bit (e & 7) of byte e >> 3 for the flat element index e = r C + c -- what the backward of a residual block's
+// z = relu(bn(y) + residual) reads instead of z (models/HRNetv2.py:36-106 and torchvision's blocks)
+extern "C" size_t catseg_bn_mask_bytes(long long rows, int C) { return (size_t)(rows * C / 8); }
+
+extern "C" int catseg_bn_apply(const catseg_bn_apply_desc* d, catseg_stream_t stream) {
+  CS_REQUIRE(d && d->y && d->mean && d->scale && d->beta, "catseg_bn_apply: y, mean, scale and beta are required");
+  const bool planes = d->z_planes != nullptr;
+  CS_REQUIRE(d->rows > 0 && d->C > 0 && d->C % (planes || d->mask ? 8 : 4) == 0 && d->ldy % 4 == 0 && (!d->z || d->ldz % 4 == 0) &&
+                 (!d->residual || d->ldr % 4 == 0),
+             "catseg_bn_apply: C and every ld must be multiples of 4 (C of 8 with z_planes or a mask)");
+  CS_REQUIRE(planes ? d->record && (!d->residual || d->residual_record) : d->z && !d->residual_record,
+             "catseg_bn_apply: z_planes needs record and, with a residual, residual_record; without z_planes, z is required and residual_record is not taken");
+  CS_REQUIRE(!d->mask || d->relu, "catseg_bn_apply: a mask needs relu");
+  CS_REQUIRE(cs_aligned16(d->y) && cs_aligned16(d->z) && cs_aligned16(d->mean) && cs_aligned16(d->scale) && cs_aligned16(d->beta) &&
+                 cs_aligned16(d->residual) && cs_aligned16(d->z_planes), "catseg_bn_apply: alignment");
+  if (planes)
+    hipLaunchKernelGGL(bn_apply_planes_kernel, dim3(plane_tile_grid(d->rows, d->C)), dim3(256), 0, (hipStream_t)stream, d->y, d->ldy, d->mean,
+                       d->scale, d->beta, d->residual, d->ldr, (const unsigned*)d->residual_record, d->z, d->ldz, (unsigned char*)d->z_planes,
+                       d->rows, d->C, d->relu, (unsigned*)d->record, (unsigned char*)d->mask);
+  else
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(d->rows * (d->C / 4))), dim3(256), 0, (hipStream_t)stream, d->y, d->ldy, d->mean, d->scale,
+                       d->beta, d->residual, d->ldr, d->z, d->ldz, d->rows, d->C, d->relu, (unsigned*)d->record, (unsigned char*)d->mask);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
 }
 
-// catseg_bn_backward with dy written as planes ONLY.  g_record: a zeroed amax record, receives max|masked gradient| (first pass);
-// y_record: max|y| of the forward pass; dy_record: zeroed, receives the bound, the exponent and nothing else
-extern "C" int catseg_bn_backward_planes(const float* dz, int lddz, const float* z, int ldz, const float* y, int ldy, const float* stats,
-                                         const float* gamma, const float* beta, long long rows, int C, int relu, void* dy_planes, void* dy_record,
-                                         void* g_record, const void* y_record, float* dgamma, float* dbeta, float* dres, int lddres,
-                                         int dres_accumulate, void* workspace, size_t workspace_bytes, catseg_stream_t stream) {
-  CS_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && lddz % 4 == 0 && ldy % 4 == 0 && dy_planes && dy_record && g_record && y_record,
-             "bn bwd (planes): C must be a multiple of 8, ld of 4; records required");
-  CS_REQUIRE(!relu || (z != nullptr && ldz % 4 == 0) || (z == nullptr && beta != nullptr && dres == nullptr),
-             "bn bwd (planes): relu needs z, or (no residual branch) beta to recompute the mask from y");
-  CS_REQUIRE(cs_aligned16(dz) && cs_aligned16(y) && cs_aligned16(dy_planes) && cs_aligned16(stats) && cs_aligned16(gamma) && cs_aligned16(z) &&
-                 cs_aligned16(dres), "bn bwd (planes): alignment");
-  if (workspace_bytes < catseg_bn_workspace(rows, C) || !workspace) {
-    catseg_set_error("bn bwd (planes): workspace too small");
-    return CATSEG_EWORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const RowSplit s = plan_rows(rows, C);
-  float* part = (float*)workspace;
-  float* coef = part + (size_t)kMaxRowBlocks * 3 * ((C + 3) & ~3);
-  hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(s.nrb, s.gy), dim3(256), 0, st, dz, lddz, z, ldz, y, ldy, stats, gamma, beta, rows, C, relu, s, part,
-                     (unsigned*)g_record);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(1024), 0, st, (const float*)part, s.nrb, rows, C, dgamma, dbeta, coef,
-                     (const unsigned*)g_record, (const unsigned*)y_record, stats, gamma, (unsigned*)dy_record);
-  const long long tiles = ((rows + 127) / 128) * ((C / 8 + 7) / 8);
-  hipLaunchKernelGGL(bn_bwd_apply_planes_kernel, dim3((int)(tiles > 8192 ? 8192 : tiles)), dim3(256), 0, st, dz, lddz, z, ldz, y, ldy, stats, gamma,
-                     beta, (const float*)coef, rows, C, relu, (unsigned char*)dy_planes, (unsigned*)dy_record, dres, lddres, dres_accumulate);
-  CS_LAUNCH_CHECK();
-  return CATSEG_OK;
-}
-
-// catseg_bn_backward_pre with dq written as planes only.  g_record: the amax record catseg_dconv3_pl_bnbwd filled with max|g|
-extern "C" int catseg_bn_backward_pre_planes(const float* g, int ldg, const float* q, int ldq, const float* stats, const float* gamma,
-                                             const float* partials, int n_blocks, long long rows, int C, void* dq_planes, void* dq_record,
-                                             const void* g_record, const void* y_record, float* dgamma, float* dbeta, void* workspace,
-                                             size_t workspace_bytes, catseg_stream_t stream) {
-  CS_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && ldg % 4 == 0 && ldq % 4 == 0 && n_blocks > 0 && partials && dq_planes && dq_record && g_record && y_record,
-             "bn bwd (pre, planes): bad args");
-  CS_REQUIRE(cs_aligned16(g) && cs_aligned16(q) && cs_aligned16(dq_planes) && cs_aligned16(stats) && cs_aligned16(gamma), "bn bwd (pre, planes): alignment");
-  const size_t need = cs_align_up((size_t)2 * ((C + 3) & ~3) * 4, 256);
-  if (workspace_bytes < need || !workspace) {
-    catseg_set_error("bn bwd (pre, planes): workspace too small");
-    return CATSEG_EWORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  float* coef = (float*)workspace;
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(1024), 0, st, partials, n_blocks, rows, C, dgamma, dbeta, coef,
-                     (const unsigned*)g_record, (const unsigned*)y_record, stats, gamma, (unsigned*)dq_record);
-  const long long tiles = ((rows + 127) / 128) * ((C / 8 + 7) / 8);
-  hipLaunchKernelGGL(bn_bwd_apply_planes_kernel, dim3((int)(tiles > 8192 ? 8192 : tiles)), dim3(256), 0, st, g, ldg, (const float*)nullptr, 0, q, ldq,
-                     stats, gamma, (const float*)nullptr, (const float*)coef, rows, C, 0, (unsigned char*)dq_planes, (unsigned*)dq_record,
-                     (float*)nullptr, 0, 0);
-  CS_LAUNCH_CHECK();
-  return CATSEG_OK;
-}
-
-// catseg_bn_backward with dy written ONLY as the blocked fp16 x 2 planes of catseg_split2h (dy_planes: catseg_split2h_blocked_elems(rows, C)
-// halves; dy_scale: its 8-byte record), for a layer whose backward-weight / backward-data run catseg_conv2d_bwd_weight_f16x2_blocked /
-// catseg_conv2d_bwd_data_f16x2_blocked; dbias (may be null) = the column sums of dy (the gradient of a bias in front of the BatchNorm).
-// No residual branch.  g_record / y_record / dy_record: three zeroed amax records (csrc/common.h) -- they receive max|g|, max|y|, the bound of dy.
+// ---- BatchNorm backward (include/catseg.h: catseg_bn_backward_desc): (partial ->) finalize -> one of three apply kernels.  The partial pass
+// leaves [row blocks][2][C] sums of g and g * xhat (with `partials` a convolution's backward-data epilogue already has: catseg_dconv3_bnbwd),
+// the finalize merges them into dgamma, dbeta and the two means the apply pass needs (coef) and, for the two planes outputs, derives the bound of
+// dy their exponent comes from.  The h2 output also sums the columns of dy: colpart, merged by colsum_rows_kernel.
 extern "C" size_t catseg_bn_backward_h2_workspace(long long rows, int C) {
   return catseg_bn_workspace(rows, C) + cs_align_up((size_t)256 * ((C + 3) & ~3) * 4, 256);
 }
-extern "C" int catseg_bn_backward_h2(const float* dz, int lddz, const float* z, int ldz, const float* y, int ldy, const float* stats,
-                                     const float* gamma, const float* beta, long long rows, int C, int relu, void* dy_planes, void* dy_scale,
-                                     float* dgamma, float* dbeta, float* dbias, void* g_record, void* y_record, void* dy_record, void* workspace,
-                                     size_t workspace_bytes, catseg_stream_t stream) {
-  CS_REQUIRE(rows > 0 && C > 0 && C % 64 == 0 && lddz % 4 == 0 && ldy % 4 == 0 && dy_planes && dy_scale && g_record && y_record && dy_record,
-             "bn bwd (h2 planes): C must be a multiple of 64, ld of 4; planes, scale and records required");
-  CS_REQUIRE(!relu || (z != nullptr && ldz % 4 == 0) || (z == nullptr && beta != nullptr),
-             "bn bwd (h2 planes): relu needs z, or beta to recompute the mask from y");
-  CS_REQUIRE(cs_aligned16(dz) && cs_aligned16(y) && cs_aligned16(dy_planes) && cs_aligned16(stats) && cs_aligned16(gamma) && cs_aligned16(z) &&
-                 cs_aligned16(beta) && (((uintptr_t)dy_scale) & 7) == 0, "bn bwd (h2 planes): alignment");
-  CS_REQUIRE(rows * C * 4 < (1ll << 32) - 64, "bn bwd (h2 planes): the two planes must stay below 4 GB");
-  if (workspace_bytes < catseg_bn_backward_h2_workspace(rows, C) || !workspace) {
-    catseg_set_error("bn bwd (h2 planes): workspace too small");
+
+extern "C" int catseg_bn_backward(const catseg_bn_backward_desc* d, catseg_stream_t stream) {
+  CS_REQUIRE(d && d->dz && d->y && d->stats && d->gamma, "catseg_bn_backward: dz, y, stats and gamma are required");
+  const bool h2 = d->dy_h2_planes != nullptr, planes = d->dy_planes != nullptr, pre = d->partials != nullptr;
+  const long long rows = d->rows;
+  const int C = d->C, relu = d->relu;
+  CS_REQUIRE((d->dy != nullptr) + planes + h2 == 1, "catseg_bn_backward: exactly one of dy, dy_planes and dy_h2_planes");
+  CS_REQUIRE(rows > 0 && C > 0 && C % (h2 ? 64 : planes || d->mask ? 8 : 4) == 0 && d->lddz % 4 == 0 && d->ldy % 4 == 0 && (!d->dy || d->lddy % 4 == 0) &&
+                 (!d->z || d->ldz % 4 == 0) && (!d->dres || d->lddres % 4 == 0),
+             "catseg_bn_backward: C and every ld must be multiples of 4 (C of 8 with dy_planes or a mask, of 64 with dy_h2_planes)");
+  CS_REQUIRE(d->dy ? !d->g_record && !d->y_record : d->g_record && d->y_record && d->dy_record,
+             "catseg_bn_backward: dy_planes and dy_h2_planes need g_record, y_record and dy_record; dy takes dy_record alone");
+  CS_REQUIRE(h2 ? d->dy_h2_scale && !d->mask && !d->dres : !d->dy_h2_scale && !d->dbias,
+             "catseg_bn_backward: dy_h2_planes needs dy_h2_scale and takes no mask and no dres; dy_h2_scale and dbias belong to it alone");
+  CS_REQUIRE(!h2 || rows * C * 4 < (1ll << 32) - 64, "catseg_bn_backward: the two h2 planes must stay below 4 GB");
+  CS_REQUIRE(pre ? d->n_blocks > 0 && !relu && !d->z && !d->mask && !d->dres && !h2 : d->n_blocks == 0,
+             "catseg_bn_backward: partials (n_blocks > 0 of them) come already masked: no relu, z, mask, dres or dy_h2_planes with them");
+  CS_REQUIRE(!d->mask || (relu && !d->z), "catseg_bn_backward: a mask needs relu and replaces z");
+  CS_REQUIRE(!relu || d->z || d->mask || (d->beta && !d->dres),
+             "catseg_bn_backward: relu needs z, a mask, or (no residual branch) beta to recompute the mask from y");
+  CS_REQUIRE(cs_aligned16(d->dz) && cs_aligned16(d->y) && cs_aligned16(d->stats) && cs_aligned16(d->gamma) && cs_aligned16(d->beta) && cs_aligned16(d->z) &&
+                 cs_aligned16(d->dres) && cs_aligned16(d->dy) && cs_aligned16(d->dy_planes) && cs_aligned16(d->dy_h2_planes) &&
+                 (((uintptr_t)d->dy_h2_scale) & 7) == 0, "catseg_bn_backward: alignment");
+  const size_t need = pre ? cs_align_up((size_t)2 * ((C + 3) & ~3) * 4, 256) : h2 ? catseg_bn_backward_h2_workspace(rows, C) : catseg_bn_workspace(rows, C);
+  if (d->workspace_bytes < need || !d->workspace) {
+    catseg_set_error("catseg_bn_backward: workspace too small");
     return CATSEG_EWORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
-  const RowSplit s = plan_rows(rows, C);
-  float* part = (float*)workspace;
-  float* coef = part + (size_t)kMaxRowBlocks * 3 * ((C + 3) & ~3);
-  float* colpart = (float*)((char*)workspace + catseg_bn_workspace(rows, C));
-  unsigned* g_rec = (unsigned*)g_record;
-  unsigned* y_rec = (unsigned*)y_record;
-  unsigned* dy_rec = (unsigned*)dy_record;
-  hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(s.nrb, s.gy), dim3(256), 0, st, dz, lddz, z, ldz, y, ldy, stats, gamma, beta, rows, C, relu, s, part,
-                     g_rec, y_rec);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(1024), 0, st, (const float*)part, s.nrb, rows, C, dgamma, dbeta, coef,
-                     (const unsigned*)g_rec, (const unsigned*)y_rec, stats, gamma, dy_rec);
-  const long long rblocks = (rows + 127) / 128;
-  const int gx = (int)(rblocks < 256 ? rblocks : 256);
-  hipLaunchKernelGGL(bn_bwd_apply_h2_kernel, dim3(gx, C / 64), dim3(256), 0, st, dz, lddz, z, ldz, y, ldy, stats, gamma, beta, (const float*)coef, rows,
-                     C, relu, (unsigned char*)dy_planes, (long long)rows * C * 2, (const unsigned*)dy_rec, (unsigned*)dy_scale,
-                     dbias ? colpart : (float*)nullptr);
-  if (dbias) hipLaunchKernelGGL(colsum_rows_kernel, dim3((C + 63) / 64), dim3(256), 0, st, (const float*)colpart, gx, C, dbias);
-  CS_LAUNCH_CHECK();
-  return CATSEG_OK;
-}
-
-// ---- the ReLU mask as bits (round 5): a residual block's output z = relu(bn(y) + residual) is read by its BatchNorm backward only for its
-// sign.  Mask = rows x C / 8 bytes: bit (e & 7) of byte e >> 3 for the flat element index e = r C + c (C % 8 == 0).  catseg_bn_apply_mask /
-// catseg_bn_apply_planes_mask = catseg_bn_apply_amax / catseg_bn_apply_planes (relu on) that also write it; catseg_bn_backward_mask /
-// catseg_bn_backward_planes_mask = catseg_bn_backward_amax / catseg_bn_backward_planes reading the bits instead of z in both passes (4 bytes per
-// element less each).  The residual BatchNorms of the trunk (models/HRNetv2.py:36-106) and of torchvision's blocks.
-extern "C" size_t catseg_bn_mask_bytes(long long rows, int C) { return (size_t)(rows * C / 8); }
-
-extern "C" int catseg_bn_apply_mask(const float* y, int ldy, const float* mean, const float* scale, const float* beta, const float* residual,
-                                    int ldr, float* z, int ldz, long long rows, int C, void* amax_record, void* mask, catseg_stream_t stream) {
-  CS_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && ldy % 4 == 0 && ldz % 4 == 0 && (residual == nullptr || ldr % 4 == 0) && mask,
-             "bn apply (mask): C must be a multiple of 8, ld of 4");
-  CS_REQUIRE(cs_aligned16(y) && cs_aligned16(z) && cs_aligned16(mean) && cs_aligned16(scale) && cs_aligned16(beta) && cs_aligned16(residual),
-             "bn apply (mask): alignment");
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(rows * (C / 4))), dim3(256), 0, (hipStream_t)stream, y, ldy, mean, scale, beta, residual, ldr, z,
-                     ldz, rows, C, 1, (unsigned*)amax_record, (unsigned char*)mask);
-  CS_LAUNCH_CHECK();
-  return CATSEG_OK;
-}
-
-extern "C" int catseg_bn_backward_mask(const float* dz, int lddz, const void* mask, const float* y, int ldy, const float* stats, const float* gamma,
-                                       long long rows, int C, float* dy, int lddy, float* dgamma, float* dbeta, float* dres, int lddres,
-                                       int dres_accumulate, void* workspace, size_t workspace_bytes, void* amax_record, catseg_stream_t stream) {
-  CS_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && lddz % 4 == 0 && ldy % 4 == 0 && lddy % 4 == 0 && mask, "bn bwd (mask): C must be a multiple of 8, ld of 4");
-  CS_REQUIRE(cs_aligned16(dz) && cs_aligned16(y) && cs_aligned16(dy) && cs_aligned16(stats) && cs_aligned16(gamma) && cs_aligned16(dres),
-             "bn bwd (mask): alignment");
-  if (workspace_bytes < catseg_bn_workspace(rows, C) || !workspace) {
-    catseg_set_error("bn bwd (mask): workspace too small");
-    return CATSEG_EWORKSPACE;
+  // workspace: [partials of the first pass][coef: 2 C floats][h2: the column sums per row block]; with `partials`, coef alone
+  float* part = (float*)d->workspace;
+  float* coef = pre ? part : part + (size_t)kMaxRowBlocks * 3 * ((C + 3) & ~3);
+  float* colpart = h2 && d->dbias ? (float*)((char*)d->workspace + catseg_bn_workspace(rows, C)) : nullptr;
+  const unsigned char* mask = (const unsigned char*)d->mask;
+  unsigned* dy_rec = (unsigned*)d->dy_record;
+  int n_blocks = d->n_blocks;
+  if (!pre) {
+    const RowSplit s = plan_rows(rows, C);
+    n_blocks = s.nrb;
+    hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(s.nrb, s.gy), dim3(256), 0, st, d->dz, d->lddz, d->z, d->ldz, d->y, d->ldy, d->stats, d->gamma, d->beta,
+                       rows, C, relu, s, part, (unsigned*)d->g_record, h2 ? (unsigned*)d->y_record : (unsigned*)nullptr, mask);
   }
-  hipStream_t st = (hipStream_t)stream;
-  const RowSplit s = plan_rows(rows, C);
-  float* part = (float*)workspace;
-  float* coef = part + (size_t)kMaxRowBlocks * 3 * ((C + 3) & ~3);
-  hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(s.nrb, s.gy), dim3(256), 0, st, dz, lddz, (const float*)nullptr, 0, y, ldy, stats, gamma,
-                     (const float*)nullptr, rows, C, 1, s, part, (unsigned*)nullptr, (unsigned*)nullptr, (const unsigned char*)mask);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(1024), 0, st, (const float*)part, s.nrb, rows, C, dgamma, dbeta, coef);
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(rows * (C / 4))), dim3(256), 0, st, dz, lddz, (const float*)nullptr, 0, y, ldy, stats, gamma,
-                     (const float*)nullptr, (const float*)coef, rows, C, 1, dy, lddy, dres, lddres, dres_accumulate, (unsigned*)amax_record,
-                     (const unsigned char*)mask);
-  CS_LAUNCH_CHECK();
-  return CATSEG_OK;
-}
-
-// catseg_bn_apply_planes (relu on) that also writes the mask
-extern "C" int catseg_bn_apply_planes_mask(const float* y, int ldy, const float* mean, const float* scale, const float* beta, const float* residual,
-                                           int ldr, const void* residual_record, float* z, int ldz, void* z_planes, long long rows, int C,
-                                           void* z_record, void* mask, catseg_stream_t stream) {
-  CS_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && ldy % 4 == 0 && (z == nullptr || ldz % 4 == 0) && (residual == nullptr || (ldr % 4 == 0 && residual_record)) && mask,
-             "bn apply (planes, mask): C must be a multiple of 8, ld of 4; a residual needs its amax record");
-  CS_REQUIRE(cs_aligned16(y) && cs_aligned16(z) && cs_aligned16(mean) && cs_aligned16(scale) && cs_aligned16(beta) && cs_aligned16(residual) &&
-                 cs_aligned16(z_planes) && z_planes && z_record, "bn apply (planes, mask): alignment");
-  const long long tiles = ((rows + 127) / 128) * ((C / 8 + 7) / 8);
-  hipLaunchKernelGGL(bn_apply_planes_kernel, dim3((int)(tiles > 8192 ? 8192 : tiles)), dim3(256), 0, (hipStream_t)stream, y, ldy, mean, scale, beta,
-                     residual, ldr, (const unsigned*)residual_record, z, ldz, (unsigned char*)z_planes, rows, C, 1, (unsigned*)z_record,
-                     (unsigned char*)mask);
-  CS_LAUNCH_CHECK();
-  return CATSEG_OK;
-}
-
-// catseg_bn_backward_planes (relu on) reading the mask instead of z
-extern "C" int catseg_bn_backward_planes_mask(const float* dz, int lddz, const void* mask, const float* y, int ldy, const float* stats,
-                                              const float* gamma, long long rows, int C, void* dy_planes, void* dy_record, void* g_record,
-                                              const void* y_record, float* dgamma, float* dbeta, float* dres, int lddres, int dres_accumulate,
-                                              void* workspace, size_t workspace_bytes, catseg_stream_t stream) {
-  CS_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && lddz % 4 == 0 && ldy % 4 == 0 && dy_planes && dy_record && g_record && y_record && mask,
-             "bn bwd (planes, mask): C must be a multiple of 8, ld of 4; records required");
-  CS_REQUIRE(cs_aligned16(dz) && cs_aligned16(y) && cs_aligned16(dy_planes) && cs_aligned16(stats) && cs_aligned16(gamma) && cs_aligned16(dres),
-             "bn bwd (planes, mask): alignment");
-  if (workspace_bytes < catseg_bn_workspace(rows, C) || !workspace) {
-    catseg_set_error("bn bwd (planes, mask): workspace too small");
-    return CATSEG_EWORKSPACE;
+  // (the bound of dy is derived for the planes outputs only: dy's own record takes max|dy| from the apply pass)
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(1024), 0, st, pre ? d->partials : (const float*)part, n_blocks, rows, C, d->dgamma,
+                     d->dbeta, coef, (const unsigned*)d->g_record, (const unsigned*)d->y_record, d->dy ? (const float*)nullptr : d->stats,
+                     d->dy ? (const float*)nullptr : d->gamma, d->dy ? (unsigned*)nullptr : dy_rec);
+  if (d->dy) {
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(rows * (C / 4))), dim3(256), 0, st, d->dz, d->lddz, d->z, d->ldz, d->y, d->ldy, d->stats, d->gamma,
+                       d->beta, (const float*)coef, rows, C, relu, d->dy, d->lddy, d->dres, d->lddres, d->dres_accumulate, dy_rec, mask);
+  } else if (planes) {
+    hipLaunchKernelGGL(bn_bwd_apply_planes_kernel, dim3(plane_tile_grid(rows, C)), dim3(256), 0, st, d->dz, d->lddz, d->z, d->ldz, d->y, d->ldy, d->stats,
+                       d->gamma, d->beta, (const float*)coef, rows, C, relu, (unsigned char*)d->dy_planes, dy_rec, d->dres, d->lddres,
+                       d->dres_accumulate, mask);
+  } else {
+    const long long rblocks = (rows + 127) / 128;
+    const int gx = (int)(rblocks < 256 ? rblocks : 256);
+    hipLaunchKernelGGL(bn_bwd_apply_h2_kernel, dim3(gx, C / 64), dim3(256), 0, st, d->dz, d->lddz, d->z, d->ldz, d->y, d->ldy, d->stats, d->gamma, d->beta,
+                       (const float*)coef, rows, C, relu, (unsigned char*)d->dy_h2_planes, (long long)rows * C * 2, (const unsigned*)dy_rec,
+                       (unsigned*)d->dy_h2_scale, colpart);
+    if (d->dbias) hipLaunchKernelGGL(colsum_rows_kernel, dim3((C + 63) / 64), dim3(256), 0, st, (const float*)colpart, gx, C, d->dbias);
   }
-  hipStream_t st = (hipStream_t)stream;
-  const RowSplit s = plan_rows(rows, C);
-  float* part = (float*)workspace;
-  float* coef = part + (size_t)kMaxRowBlocks * 3 * ((C + 3) & ~3);
-  hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(s.nrb, s.gy), dim3(256), 0, st, dz, lddz, (const float*)nullptr, 0, y, ldy, stats, gamma,
-                     (const float*)nullptr, rows, C, 1, s, part, (unsigned*)g_record, (unsigned*)nullptr, (const unsigned char*)mask);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(1024), 0, st, (const float*)part, s.nrb, rows, C, dgamma, dbeta, coef,
-                     (const unsigned*)g_record, (const unsigned*)y_record, stats, gamma, (unsigned*)dy_record);
-  const long long tiles = ((rows + 127) / 128) * ((C / 8 + 7) / 8);
-  hipLaunchKernelGGL(bn_bwd_apply_planes_kernel, dim3((int)(tiles > 8192 ? 8192 : tiles)), dim3(256), 0, st, dz, lddz, (const float*)nullptr, 0, y, ldy,
-                     stats, gamma, (const float*)nullptr, (const float*)coef, rows, C, 1, (unsigned char*)dy_planes, (unsigned*)dy_record, dres, lddres,
-                     dres_accumulate, (const unsigned char*)mask);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
 }
@@ -1139,7 +952,7 @@ extern "C" int catseg_head_fwd_drop(const float* y, int ldy, const float* mean, 
 }
 
 // Backward of the same: from the gradient of the logits dl [rows][lddl] (lddl >= 32) to
-//   dy_planes / dy_scale   the gradient of y as the blocked fp16 x 2 planes of catseg_bn_backward_h2 (same records: g / y / dy_record zeroed)
+//   dy_planes / dy_scale   the gradient of y as the blocked fp16 x 2 planes of catseg_bn_backward's dy_h2_planes (same records: g / y / dy_record zeroed)
 //   dgamma, dbeta          of the BatchNorm;  dbias (may be null): column sums of dy
 //   dwh [K][C], dbh [K]    of the classifier (written, not accumulated; dbh may be null)
 // row blocks of the backward launches: x (C / 128) channel blocks of 4 waves = 512 blocks, two per CU, all resident

@@ -847,46 +847,33 @@ extern "C" int catseg_axpy2d(const float* src, int lds, float* dst, int ldd, lon
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
 }
-extern "C" int catseg_add_n_act_amax(const float* const* in, const int* ld, int n, float* out, int ldo, long long rows, int C, int relu,
-                                     void* amax_record, catseg_stream_t stream);
-extern "C" int catseg_add_n_act(const float* const* in, const int* ld, int n, float* out, int ldo, long long rows, int C, int relu,
-                                catseg_stream_t stream) {
-  return catseg_add_n_act_amax(in, ld, n, out, ldo, rows, C, relu, nullptr, stream);
-}
-// the same, and max|out| folded into amax_record[0] (may be null)
-extern "C" int catseg_add_n_act_amax(const float* const* in, const int* ld, int n, float* out, int ldo, long long rows, int C, int relu,
-                                     void* amax_record, catseg_stream_t stream) {
-  CS_REQUIRE(n >= 1 && n <= 4 && rows > 0 && C > 0 && C % 4 == 0 && ldo % 4 == 0 && cs_aligned16(out), "add_n: bad args");
-  AddArgs a;
-  a.n = n;
-  for (int i = 0; i < 4; ++i) {
-    a.in[i] = i < n ? in[i] : nullptr;
-    a.ld[i] = i < n ? ld[i] : 0;
-    if (i < n) CS_REQUIRE(cs_aligned16(in[i]) && ld[i] % 4 == 0, "add_n: input %d misaligned", i);
-  }
-  hipLaunchKernelGGL(add_n_act_kernel, dim3(grid_for(rows * (C / 4))), dim3(256), 0, (hipStream_t)stream, a, out, ldo, rows, C, relu,
-                     (unsigned*)amax_record);
-  CS_LAUNCH_CHECK();
-  return CATSEG_OK;
-}
-// catseg_add_n_act_amax that also writes the planes of out (exponent from the SUM of the terms' amax records: term_records[i] = the amax
-// record of in[i], each the max over its 16 slots)
-extern "C" int catseg_add_n_act_planes(const float* const* in, const int* ld, const void* const* term_records, int n, float* out, int ldo,
-                                       void* out_planes, long long rows, int C, int relu, void* out_record, catseg_stream_t stream) {
-  CS_REQUIRE(n >= 1 && n <= 4 && rows > 0 && C > 0 && C % 8 == 0 && ldo % 4 == 0 && cs_aligned16(out) && cs_aligned16(out_planes) && out_planes &&
-                 out_record && term_records, "add_n (planes): bad args");
+// out = act(sum of the terms).  Without term_records / out_planes: out_record (may be null) receives max|out|.  With both: the planes of out are
+// written too (exponent from the SUM of the terms' amax records: term_records[i] = the amax record of in[i], each the max over its 16 slots)
+extern "C" int catseg_add_n_act(const float* const* in, const int* ld, const void* const* term_records, int n, float* out, int ldo, void* out_planes,
+                                long long rows, int C, int relu, void* out_record, catseg_stream_t stream) {
+  const bool planes = out_planes != nullptr;
+  CS_REQUIRE(in && ld && n >= 1 && n <= 4 && rows > 0 && C > 0 && C % (planes ? 8 : 4) == 0 && ldo % 4 == 0 && out && cs_aligned16(out) &&
+                 cs_aligned16(out_planes), "catseg_add_n_act: 1 to 4 terms, C a multiple of 4 (of 8 with planes), ldo of 4, 16-byte aligned");
+  CS_REQUIRE(planes ? term_records && out_record : !term_records,
+             "catseg_add_n_act: out_planes needs term_records and out_record; term_records come with out_planes alone");
   AddArgs a;
   AddRecs rr;
   a.n = n;
   for (int i = 0; i < 4; ++i) {
     a.in[i] = i < n ? in[i] : nullptr;
     a.ld[i] = i < n ? ld[i] : 0;
-    rr.rec[i] = i < n ? (const unsigned*)term_records[i] : nullptr;
-    if (i < n) CS_REQUIRE(cs_aligned16(in[i]) && ld[i] % 4 == 0 && term_records[i], "add_n (planes): input %d misaligned / without a record", i);
+    rr.rec[i] = planes && i < n ? (const unsigned*)term_records[i] : nullptr;
+    if (i < n) CS_REQUIRE(in[i] && cs_aligned16(in[i]) && ld[i] % 4 == 0 && (!planes || term_records[i]),
+                          "catseg_add_n_act: input %d misaligned, or without its record", i);
   }
-  const long long tiles = ((rows + 127) / 128) * ((C / 8 + 7) / 8);
-  hipLaunchKernelGGL(add_n_act_planes_kernel, dim3((int)(tiles > 8192 ? 8192 : tiles)), dim3(256), 0, (hipStream_t)stream, a, rr, out, ldo,
-                     (unsigned char*)out_planes, rows, C, relu, (unsigned*)out_record);
+  if (planes) {
+    const long long tiles = ((rows + 127) / 128) * ((C / 8 + 7) / 8);
+    hipLaunchKernelGGL(add_n_act_planes_kernel, dim3((int)(tiles > 8192 ? 8192 : tiles)), dim3(256), 0, (hipStream_t)stream, a, rr, out, ldo,
+                       (unsigned char*)out_planes, rows, C, relu, (unsigned*)out_record);
+  } else {
+    hipLaunchKernelGGL(add_n_act_kernel, dim3(grid_for(rows * (C / 4))), dim3(256), 0, (hipStream_t)stream, a, out, ldo, rows, C, relu,
+                       (unsigned*)out_record);
+  }
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
 }

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from . import plan as _plan
-from ._lib import ConvDesc, check, lib, ptr, stream
+from ._lib import BnApplyDesc, BnBackwardDesc, ConvDesc, check, lib, ptr, stream
 
 _ws = {}
 
@@ -1298,7 +1298,7 @@ def bn_eval_scale(gamma, running_var, eps):
     return scale
 
 
-# The ReLU mask of a residual block's output as bits (csrc/norm.hip: catseg_bn_apply_mask / catseg_bn_backward_mask): the BatchNorm backward of
+# The ReLU mask of a residual block's output as bits (csrc/norm.hip: the mask field of catseg_bn_apply / catseg_bn_backward): the BatchNorm backward of
 # z = relu(bn(y) + residual) reads 1 bit per element instead of z in both of its passes.  CATSEG_RELU_BITS=0: z is read, as before.
 RELU_BITS = _plan.get("relu_bits")
 
@@ -1308,83 +1308,76 @@ def relu_bits_ok(y, residual, relu, out):
                 and (out is None or ld_of(out) % 4 == 0))
 
 
+def _ld(t):
+    return 0 if t is None else ld_of(t)
+
+
 def bn_apply(y, mean, scale, beta, residual, relu, out=None, planes_rec=None, planes_only=False, want_mask=False):
     """the output carries an amax record (out._amax: max|out| accumulated by the kernel) when the trunk runs the f16x2 kernels.
     planes_rec (the record bn_finalize(bound=...) left the bound in): the kernel also writes the fp16 x 2 planes of the output (out._planes);
     planes_only: and NOT the fp32 output -- `out` is then an unwritten placeholder that only plane-streaming kernels may consume"""
+    rows, C = rows_of(y), y.shape[-1]
+    planes = planes_rec is not None
     if out is None:
         out = torch.empty(y.shape, dtype=torch.float32, device=y.device)
-    if planes_rec is not None:
-        buf = torch.empty(lib.catseg_planes_bytes(rows_of(y), y.shape[-1]), dtype=torch.uint8, device=y.device)
-        mask = None
-        if want_mask and not planes_only and relu_bits_ok(y, residual, relu, out):
-            mask = torch.empty(lib.catseg_bn_mask_bytes(rows_of(y), y.shape[-1]), dtype=torch.uint8, device=y.device)
-        # algorithmic bytes: y (+ residual) read, planes written (4 B / element, like fp32), z written unless planes only
-        with _Timed("hbm:bn_apply", 4.0 * y.numel() * ((3 if residual is not None else 2) + (0 if planes_only else 1))):
-            if mask is not None:
-                check(lib.catseg_bn_apply_planes_mask(ptr(y), ld_of(y), ptr(mean), ptr(scale), ptr(beta), ptr(residual), ld_of(residual),
-                                                      ptr(amax_of(residual)), ptr(out), ld_of(out), ptr(buf), rows_of(y), y.shape[-1], ptr(planes_rec),
-                                                      ptr(mask), stream()))
-                out._relu_mask = mask
-            else:
-                check(lib.catseg_bn_apply_planes(ptr(y), ld_of(y), ptr(mean), ptr(scale), ptr(beta), ptr(residual),
-                                                 ld_of(residual) if residual is not None else 0, ptr(amax_of(residual)) if residual is not None else None,
-                                                 None if planes_only else ptr(out), ld_of(out), ptr(buf), rows_of(y), y.shape[-1], 1 if relu else 0,
-                                                 ptr(planes_rec), stream()))
-        out._amax = planes_rec
+    buf = torch.empty(lib.catseg_planes_bytes(rows, C), dtype=torch.uint8, device=y.device) if planes else None
+    mask = None
+    if want_mask and not (planes and planes_only) and relu_bits_ok(y, residual, relu, out):
+        mask = torch.empty(lib.catseg_bn_mask_bytes(rows, C), dtype=torch.uint8, device=y.device)
+    rec = planes_rec if planes else new_amax(y.device) if _trunk_h2() else None
+    d = BnApplyDesc(y=ptr(y), ldy=ld_of(y), mean=ptr(mean), scale=ptr(scale), beta=ptr(beta), residual=ptr(residual), ldr=_ld(residual),
+                    residual_record=ptr(amax_of(residual)) if planes and residual is not None else None,
+                    z=None if planes and planes_only else ptr(out), ldz=ld_of(out), z_planes=ptr(buf), rows=rows, C=C, relu=1 if relu else 0,
+                    record=ptr(rec), mask=ptr(mask))
+    # algorithmic bytes: y (+ residual) read, z written unless planes only, planes written (4 B / element, like fp32)
+    with _Timed("hbm:bn_apply", 4.0 * y.numel() * ((3 if residual is not None else 2) + (1 if planes and not planes_only else 0))):
+        check(lib.catseg_bn_apply(ctypes.byref(d), stream()))
+    if rec is not None:
+        out._amax = rec
+    if planes:
         out._planes = Planes(buf, planes_rec, y.shape)
         out._planes_only = bool(planes_only)
-        return out
-    if want_mask and relu_bits_ok(y, residual, relu, out):
-        rows, C = rows_of(y), y.shape[-1]
-        mask = torch.empty(lib.catseg_bn_mask_bytes(rows, C), dtype=torch.uint8, device=y.device)
-        rec = new_amax(y.device) if _trunk_h2() else None
-        with _Timed("hbm:bn_apply", 4.0 * y.numel() * 3):
-            check(lib.catseg_bn_apply_mask(ptr(y), ld_of(y), ptr(mean), ptr(scale), ptr(beta), ptr(residual), ld_of(residual), ptr(out), ld_of(out),
-                                           rows, C, ptr(rec), ptr(mask), stream()))
-        if rec is not None:
-            out._amax = rec
+    if mask is not None:
         out._relu_mask = mask
-        return out
-    with _Timed("hbm:bn_apply", 4.0 * y.numel() * (3 if residual is not None else 2)):
-        _bn_apply(y, mean, scale, beta, residual, relu, out)
     return out
+
+
+def _relu_source(z, relu, beta):
+    """the ReLU fields of a catseg_bn_backward_desc: a z that carries its mask as bits (bn_apply(want_mask=True)) is not read, the bits are"""
+    mask = getattr(z, "_relu_mask", None) if (z is not None and relu) else None
+    if mask is not None:
+        return dict(relu=1, mask=ptr(mask))
+    return dict(relu=1 if relu else 0, z=ptr(z), ldz=_ld(z), beta=ptr(beta))
+
+
+def _bn_backward_call(dz, y, stats, gamma, dgamma, dbeta, passes, ws_bytes=None, **fields):
+    """one catseg_bn_backward call: the fields every form fills and the workspace here, the ReLU source, the residual branch, the records and
+    the output in `fields`.  passes: the algorithmic bytes, in tensors of y's size"""
+    rows, C = rows_of(y), y.shape[-1]
+    ws = workspace(ws_bytes or lib.catseg_bn_workspace(rows, C), y.device)
+    d = BnBackwardDesc(dz=ptr(dz), lddz=ld_of(dz), y=ptr(y), ldy=ld_of(y), stats=ptr(stats), gamma=ptr(gamma), rows=rows, C=C, dgamma=ptr(dgamma),
+                       dbeta=ptr(dbeta), workspace=ptr(ws), workspace_bytes=ws.numel(), **fields)
+    with _Timed("hbm:bn_backward", 4.0 * y.numel() * passes):
+        check(lib.catseg_bn_backward(ctypes.byref(d), stream()))
 
 
 def bn_backward_planes(dz, z, y, stats, gamma, relu, dgamma, dbeta, dres, dres_accumulate, beta, y_rec):
     """bn_backward whose result exists as planes only (returned: Planes); y_rec: the forward convolution's max|y| record"""
-    C = y.shape[-1]
-    rows = rows_of(y)
-    ws = workspace(lib.catseg_bn_workspace(rows, C), y.device)
-    buf = torch.empty(lib.catseg_planes_bytes(rows, C), dtype=torch.uint8, device=y.device)
+    buf = torch.empty(lib.catseg_planes_bytes(rows_of(y), y.shape[-1]), dtype=torch.uint8, device=y.device)
     rec, grec = new_amax(y.device), new_amax(y.device)
-    mask = getattr(z, "_relu_mask", None) if (z is not None and relu) else None
-    if mask is not None:
-        with _Timed("hbm:bn_backward", 4.0 * y.numel() * (5 + (1 if dres is not None else 0))):
-            check(lib.catseg_bn_backward_planes_mask(ptr(dz), ld_of(dz), ptr(mask), ptr(y), ld_of(y), ptr(stats), ptr(gamma), rows, C, ptr(buf), ptr(rec),
-                                                     ptr(grec), ptr(y_rec), ptr(dgamma), ptr(dbeta), ptr(dres), ld_of(dres) if dres is not None else 0,
-                                                     1 if dres_accumulate else 0, ptr(ws), ws.numel(), stream()))
-        return Planes(buf, rec, y.shape)
-    with _Timed("hbm:bn_backward", 4.0 * y.numel() * (5 + (1 if dres is not None else 0))):
-        check(lib.catseg_bn_backward_planes(ptr(dz), ld_of(dz), ptr(z), ld_of(z) if z is not None else 0, ptr(y), ld_of(y), ptr(stats), ptr(gamma),
-                                            ptr(beta), rows, C, 1 if relu else 0, ptr(buf), ptr(rec), ptr(grec), ptr(y_rec), ptr(dgamma), ptr(dbeta),
-                                            ptr(dres), ld_of(dres) if dres is not None else 0, 1 if dres_accumulate else 0, ptr(ws), ws.numel(),
-                                            stream()))
+    _bn_backward_call(dz, y, stats, gamma, dgamma, dbeta, 5 + (1 if dres is not None else 0), dy_planes=ptr(buf), dy_record=ptr(rec), g_record=ptr(grec),
+                      y_record=ptr(y_rec), dres=ptr(dres), lddres=_ld(dres), dres_accumulate=1 if dres_accumulate else 0, **_relu_source(z, relu, beta))
     return Planes(buf, rec, y.shape)
 
 
 def bn_backward_pre_planes(g, q, stats, gamma, pre, y_rec, dgamma, dbeta):
     """bn_backward_pre (g already masked, its per-wave sums and max|g| from catseg_dconv3_pl_bnbwd: pre = (partials, rows, g_record)) whose
     result exists as planes only"""
-    C = q.shape[-1]
-    rows = rows_of(q)
     part, nr, grec = pre
-    ws = workspace(lib.catseg_bn_workspace(rows, C), q.device)
-    buf = torch.empty(lib.catseg_planes_bytes(rows, C), dtype=torch.uint8, device=q.device)
+    buf = torch.empty(lib.catseg_planes_bytes(rows_of(q), q.shape[-1]), dtype=torch.uint8, device=q.device)
     rec = new_amax(q.device)
-    with _Timed("hbm:bn_backward", 4.0 * q.numel() * 3):
-        check(lib.catseg_bn_backward_pre_planes(ptr(g), ld_of(g), ptr(q), ld_of(q), ptr(stats), ptr(gamma), ptr(part), nr, rows, C, ptr(buf), ptr(rec),
-                                                ptr(grec), ptr(y_rec), ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), stream()))
+    _bn_backward_call(g, q, stats, gamma, dgamma, dbeta, 3, partials=ptr(part), n_blocks=nr, dy_planes=ptr(buf), dy_record=ptr(rec), g_record=ptr(grec),
+                      y_record=ptr(y_rec))
     return Planes(buf, rec, q.shape)
 
 
@@ -1409,38 +1402,17 @@ def conv_bwd_data_pl(dyp, w, out, accumulate=False, bn_src=None, with_pre=False)
     return (out, None) if with_pre else out
 
 
-def _bn_apply(y, mean, scale, beta, residual, relu, out):
-    rec = new_amax(y.device) if _trunk_h2() else None
-    check(lib.catseg_bn_apply_amax(ptr(y), ld_of(y), ptr(mean), ptr(scale), ptr(beta), ptr(residual),
-                                   ld_of(residual) if residual is not None else 0, ptr(out), ld_of(out), rows_of(y),
-                                   y.shape[-1], 1 if relu else 0, ptr(rec), stream()))
-    if rec is not None:
-        out._amax = rec
-    return out
-
-
 def bn_backward(dz, z, y, stats, gamma, relu, dgamma, dbeta, dres=None, dres_accumulate=False, dy_out=None, beta=None):
     """z=None (only without a residual branch): the ReLU mask is recomputed from y and beta instead of being read; a z that carries its mask as
     bits (bn_apply(want_mask=True)) is not read either"""
-    C = y.shape[-1]
-    rows = rows_of(y)
     if dy_out is None:
         dy_out = torch.empty(y.shape, dtype=torch.float32, device=y.device)
-    ws = workspace(lib.catseg_bn_workspace(rows, C), y.device)
-    mask = getattr(z, "_relu_mask", None) if (z is not None and relu) else None
-    if mask is not None:
-        rec = new_amax(y.device) if _trunk_h2() else None
-        # algorithmic bytes: two passes over (dz, y) + dy written (+ the residual gradient)
-        with _Timed("hbm:bn_backward", 4.0 * y.numel() * (5 + (1 if dres is not None else 0))):
-            check(lib.catseg_bn_backward_mask(ptr(dz), ld_of(dz), ptr(mask), ptr(y), ld_of(y), ptr(stats), ptr(gamma), rows, C, ptr(dy_out),
-                                              ld_of(dy_out), ptr(dgamma), ptr(dbeta), ptr(dres), ld_of(dres) if dres is not None else 0,
-                                              1 if dres_accumulate else 0, ptr(ws), ws.numel(), ptr(rec), stream()))
-        if rec is not None:
-            dy_out._amax = rec
-        return dy_out
-    # algorithmic bytes: two passes over (dz, y [or z]) + dy written (+ the residual gradient)
-    with _Timed("hbm:bn_backward", 4.0 * y.numel() * (5 + (1 if dres is not None else 0))):
-        _bn_backward(dz, z, y, stats, gamma, relu, dgamma, dbeta, dres, dres_accumulate, dy_out, beta, rows, C, ws)
+    rec = new_amax(y.device) if _trunk_h2() else None
+    # algorithmic bytes: two passes over (dz, y [or z, or its mask]) + dy written (+ the residual gradient)
+    _bn_backward_call(dz, y, stats, gamma, dgamma, dbeta, 5 + (1 if dres is not None else 0), dy=ptr(dy_out), lddy=ld_of(dy_out), dy_record=ptr(rec),
+                      dres=ptr(dres), lddres=_ld(dres), dres_accumulate=1 if dres_accumulate else 0, **_relu_source(z, relu, beta))
+    if rec is not None:
+        dy_out._amax = rec
     return dy_out
 
 
@@ -1521,13 +1493,9 @@ def bn_backward_h2(dz, y, stats, gamma, relu, dgamma, dbeta, beta, dbias=None):
     C, rows = y.shape[-1], rows_of(y)
     blk = torch.empty((2, C // 16, rows, 16), dtype=torch.int16, device=y.device)
     scale = torch.empty(2, dtype=torch.int32, device=y.device)
-    need = lib.catseg_bn_backward_h2_workspace(rows, C)
-    ws = workspace(need, y.device)
     grec, yrec, dyrec = new_amax(y.device), new_amax(y.device), new_amax(y.device)
-    with _Timed("hbm:bn_backward", 4.0 * y.numel() * 5):
-        check(lib.catseg_bn_backward_h2(ptr(dz), ld_of(dz), None, 0, ptr(y), ld_of(y), ptr(stats), ptr(gamma), ptr(beta), rows, C, 1 if relu else 0,
-                                        ptr(blk), ptr(scale), ptr(dgamma), ptr(dbeta), ptr(dbias), ptr(grec), ptr(yrec), ptr(dyrec), ptr(ws),
-                                        ws.numel(), stream()))
+    _bn_backward_call(dz, y, stats, gamma, dgamma, dbeta, 5, ws_bytes=lib.catseg_bn_backward_h2_workspace(rows, C), relu=1 if relu else 0, beta=ptr(beta),
+                      dy_h2_planes=ptr(blk), dy_h2_scale=ptr(scale), dbias=ptr(dbias), g_record=ptr(grec), y_record=ptr(yrec), dy_record=ptr(dyrec))
     return blk, scale
 
 
@@ -1656,30 +1624,15 @@ def conv_bwd_data_h2(dyp, dysc, w, xshape, Cout, kh, kw, pad, dil, out, accumula
 def bn_backward_pre(g, q, stats, gamma, partials, dgamma, dbeta, dq_out=None):
     """backward of relu(bn(q)) from the masked gradient g and the per-tile sums (partials, n_tiles) that conv_bwd_data(bn_src=...)
     returned: merge + apply pass only"""
-    C = q.shape[-1]
-    rows = rows_of(q)
     part, nt = partials[:2]
     if dq_out is None:
         dq_out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
-    ws = workspace(lib.catseg_bn_workspace(rows, C), q.device)
-    with _Timed("hbm:bn_backward", 4.0 * q.numel() * 3):      # one pass: g and q read, dq written
-        rec = new_amax(q.device) if _trunk_h2() else None
-        check(lib.catseg_bn_backward_pre_amax(ptr(g), ld_of(g), ptr(q), ld_of(q), ptr(stats), ptr(gamma), ptr(part), nt, rows, C, ptr(dq_out),
-                                              ld_of(dq_out), ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), ptr(rec), stream()))
+    rec = new_amax(q.device) if _trunk_h2() else None
+    # one pass: g and q read, dq written
+    _bn_backward_call(g, q, stats, gamma, dgamma, dbeta, 3, partials=ptr(part), n_blocks=nt, dy=ptr(dq_out), lddy=ld_of(dq_out), dy_record=ptr(rec))
     if rec is not None:
         dq_out._amax = rec
     return dq_out
-
-
-def _bn_backward(dz, z, y, stats, gamma, relu, dgamma, dbeta, dres, dres_accumulate, dy_out, beta, rows, C, ws):
-    rec = new_amax(y.device) if _trunk_h2() else None
-    check(lib.catseg_bn_backward_amax(ptr(dz), ld_of(dz), ptr(z), ld_of(z) if z is not None else 0, ptr(y), ld_of(y), ptr(stats),
-                                      ptr(gamma), ptr(beta), rows, C, 1 if relu else 0, ptr(dy_out), ld_of(dy_out), ptr(dgamma), ptr(dbeta),
-                                      ptr(dres), ld_of(dres) if dres is not None else 0, 1 if dres_accumulate else 0, ptr(ws),
-                                      ws.numel(), ptr(rec), stream()))
-    if rec is not None:
-        dy_out._amax = rec
-    return dy_out
 
 
 def nchw3_to_nhwc4(x):
@@ -2135,24 +2088,21 @@ def adam_step_dev(p, g, m, v, hyper, beta1=0.9, beta2=0.999, eps=1e-8):
 def add_n_act(terms, relu, out=None):
     """out = act(sum(terms)); terms: up to 4 NHWC tensors of one shape (row strides may differ)"""
     t0 = terms[0]
+    rows, C = rows_of(t0), t0.shape[-1]
     if out is None:
         out = torch.empty(t0.shape, dtype=torch.float32, device=t0.device)
     n = len(terms)
     ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in terms])
     lds = (ctypes.c_int * n)(*[ld_of(t) for t in terms])
-    if planes_ok(t0.shape[-1], rows_of(t0)) and all(amax_of(t) is not None for t in terms):
-        rec = new_amax(t0.device)
-        recs = (ctypes.c_void_p * n)(*[amax_of(t).data_ptr() for t in terms])
-        buf = torch.empty(lib.catseg_planes_bytes(rows_of(t0), t0.shape[-1]), dtype=torch.uint8, device=t0.device)
-        check(lib.catseg_add_n_act_planes(ptrs, lds, recs, n, ptr(out), ld_of(out), ptr(buf), rows_of(t0), t0.shape[-1], 1 if relu else 0, ptr(rec),
-                                          stream()))
-        out._amax = rec
-        out._planes = Planes(buf, rec, t0.shape)
-        return out
-    rec = new_amax(t0.device) if _trunk_h2() else None
-    check(lib.catseg_add_n_act_amax(ptrs, lds, n, ptr(out), ld_of(out), rows_of(t0), t0.shape[-1], 1 if relu else 0, ptr(rec), stream()))
+    planes = planes_ok(C, rows) and all(amax_of(t) is not None for t in terms)
+    rec = new_amax(t0.device) if planes or _trunk_h2() else None
+    recs = (ctypes.c_void_p * n)(*[amax_of(t).data_ptr() for t in terms]) if planes else None
+    buf = torch.empty(lib.catseg_planes_bytes(rows, C), dtype=torch.uint8, device=t0.device) if planes else None
+    check(lib.catseg_add_n_act(ptrs, lds, recs, n, ptr(out), ld_of(out), ptr(buf), rows, C, 1 if relu else 0, ptr(rec), stream()))
     if rec is not None:
         out._amax = rec
+    if planes:
+        out._planes = Planes(buf, rec, t0.shape)
     return out
 
 

@@ -90,7 +90,7 @@ BQ_CASES = [(2, 16, 32, 48), (1, 19, 37, 48), (2, 5, 7, 48), (2, 8, 64, 96), (1,
 @pytest.mark.parametrize("case", BQ_CASES)
 def test_backward_data_with_fused_bn_backward_pass(ops, case, spec, h2):
     """out = relu(bn1(q)); y = conv2(out) (models/HRNetv2.py:36-47): the backward-data launch of conv2 masks its result with
-    relu(bn1(q)) > 0 and leaves the per-tile sums of the first pass of bn1's backward (catseg_dconv3_bnbwd), catseg_bn_backward_pre
+    relu(bn1(q)) > 0 and leaves the per-tile sums of the first pass of bn1's backward (catseg_dconv3_bnbwd), catseg_bn_backward given them
     finishes.  dq, dgamma, dbeta against fp64 autograd through relu(batch_norm(q)) -> conv2d, and against the two-pass route
     (plain backward-data + catseg_bn_backward): the masked gradient must be bit-identical (same products, same mask expression)."""
     from miccai2021_cataract_semantic_segmentation_amd._lib import lib

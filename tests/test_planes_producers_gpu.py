@@ -1,5 +1,5 @@
-"""The producers of fp16 x 2 operand planes (csrc/norm.hip: catseg_bn_finalize_counts_bound, catseg_bn_apply_planes,
-catseg_bn_backward_planes / _pre_planes; csrc/pointwise.hip: catseg_add_n_act_planes) through the C ABI, against the fp32 kernels they
+"""The producers of fp16 x 2 operand planes (csrc/norm.hip: catseg_bn_finalize_counts_bound, the planes outputs of
+catseg_bn_apply and catseg_bn_backward; csrc/pointwise.hip: those of catseg_add_n_act) through the C ABI, against the fp32 kernels they
 extend: same fp32 results bit for bit, planes that reproduce them to 2^-22, exponents that can never overflow fp16 (they come from
 bounds proven before the pass), and the true max| | left in the records."""
 import pytest
@@ -133,7 +133,7 @@ def test_add_n_act_planes_and_bilinear_record_propagation():
 
 
 def test_backward_data_with_fused_bn_backward_pass_on_planes():
-    """catseg_dconv3_pl_bnbwd + catseg_bn_backward_pre_planes against the two-pass route (dx by the plain kernel, then catseg_bn_backward)"""
+    """catseg_dconv3_pl_bnbwd + catseg_bn_backward (partials in, planes out) against the two-pass route (dx by the plain kernel, then catseg_bn_backward)"""
     _need_gpu()
     from miccai2021_cataract_semantic_segmentation_amd import ops
     dev = torch.device("cuda")

@@ -1,4 +1,4 @@
-"""The ReLU mask of a residual block's output as bits (csrc/norm.hip: catseg_bn_apply_mask / catseg_bn_backward_mask; the BatchNorm + residual + ReLU
+"""The ReLU mask of a residual block's output as bits (csrc/norm.hip: the mask field of catseg_bn_apply / catseg_bn_backward; the BatchNorm + residual + ReLU
 of the stage-1 bottlenecks, models/HRNetv2.py:68-106 of the reference): the bits are the signs of z, and the backward pass that reads them is
 bit-identical to the one that reads z."""
 import pytest
@@ -76,7 +76,7 @@ def test_hrnet_step_takes_the_bits_and_reproduces_the_gradients():
 @pytest.mark.parametrize("shape", [(2, 12, 20, 96), (1, 9, 13, 192), (2, 5, 7, 384), (1, 130, 3, 48), (1, 9, 13, 720)])
 @pytest.mark.parametrize("acc", [False, True])
 def test_planes_route_mask_bits_and_backward_bit_identical(shape, acc):
-    """the trunk's residual BatchNorm on the planes route (catseg_bn_apply_planes_mask / catseg_bn_backward_planes_mask): the mask bytes are the
+    """the trunk's residual BatchNorm on the planes route (catseg_bn_apply / catseg_bn_backward with planes and a mask): the mask bytes are the
     signs of z; dy planes, dgamma, dbeta and the residual gradient bit-identical to the z-reading route"""
     from miccai2021_cataract_semantic_segmentation_amd import ops
     B, H, W, C = shape

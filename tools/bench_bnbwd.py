@@ -1,5 +1,5 @@
 """standalone times of the two routes through the backward of relu(bn1(.)) -> conv2: (a) plain backward-data + catseg_bn_backward,
-(b) catseg_dconv3_bnbwd + catseg_bn_backward_pre, at the HRNet-W48 trunk shapes of the bs-8 step"""
+(b) catseg_dconv3_bnbwd + catseg_bn_backward from its partials, at the HRNet-W48 trunk shapes of the bs-8 step"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -39,7 +39,7 @@ def restore():
 is_dgrad = lambda a: a[7] is None and a[11] is None          # catseg_dconv3(..., bias, ..., bn_part, ...): backward-data calls have neither
 SETS = [
     ("nothing", [], None),
-    ("BatchNorm backward (all)", ["catseg_bn_backward", "catseg_bn_backward_pre"], None),
+    ("BatchNorm backward (all)", ["catseg_bn_backward"], None),
     ("direct backward-weight (trunk)", ["catseg_dwgrad3"], None),
     ("direct backward-data (trunk)", ["catseg_dconv3", "catseg_dconv3_bnbwd"], is_dgrad),
     ("fp32 backward-weight", ["catseg_conv2d_bwd_weight"], None),
