@@ -589,6 +589,23 @@ int catseg_ingest_u8(const uint8_t* img, const uint8_t* lbl, int B, int H, int W
                      int pad_top, int pad_bottom, const float* mean, const float* stdv, float* x_nchw, float* x_nhwc4,
                      int64_t* labels, catseg_stream_t stream);
 
+/* The same with the geometric augmentations of the reference's `transforms` list fused in (csrc/warp.hip): after remap and flip,
+ * AffineNP(crop_to_fit=False) warps the frame onto an Hc x Wc canvas (the reference: 2H x 2W; utils/transforms.py:38-61), CropNP keeps an
+ * Hw x Ww window of the canvas at a per-image origin (:270-303), PadNP reflect-pads the rows when nothing was cropped (utils/utils.py:394-401).
+ * Only the window's pixels are computed: one gather of up to four source pixels each.
+ *   minv: DEVICE double [B][6], rows 0 and 1 of the inverse of the frame -> canvas matrix (NULL = identity, then the canvas is the frame);
+ *   source coordinates in 1/32 pixel: X = rint(((m00 x + m01 y) + m02) * 32) in fp64 without contraction, clamped to int32; bilinear weights
+ *   are integers over 1024, neighbours outside the frame count as 0 (constant border); colour = the weighted sum rounded half to even;
+ *   label = the remapped label with the largest summed weight, ties to the smaller id, 0 where no neighbour is inside the frame;
+ *   origin: DEVICE int32 [B][2] = (row, column) of the window in the canvas (NULL = (0, 0)); window pixels outside the canvas are zeros;
+ *   pad_top / pad_bottom reflect the canvas rows and need Hw == Hc.  No source read is unguarded, whatever minv / origin hold.
+ *   Outputs (any combination): x_nchw f32 [B][3][H'][Ww], x_nhwc4 f32 [B][H'][Ww][4], x_u8 u8 [B][H'][Ww][3] (the warped frame before
+ *   ToTensor: the input of the blur / colour jitter kernels below), labels int64 [B][H'][Ww]; H' = Hw + pad_top + pad_bottom. */
+int catseg_ingest_warp_u8(const uint8_t* img, const uint8_t* lbl, int B, int H, int W, const uint8_t* lut, const int32_t* flips,
+                          const double* minv, int Hc, int Wc, const int32_t* origin, int Hw, int Ww, int pad_top, int pad_bottom,
+                          const float* mean, const float* stdv, float* x_nchw, float* x_nhwc4, uint8_t* x_u8, int64_t* labels,
+                          catseg_stream_t stream);
+
 /* PIL-based training augmentations on uint8 NHWC batches [B][H][W][3], bit-exact with Pillow (csrc/augment.hip; reference call
  * sites utils/utils.py:412-417, utils/transforms.py:242-251):
  *   catseg_aug_pad_flip_u8: FlipNP (bit 0 horizontal, bit 1 vertical) + PadNP reflect rows, uint8 -> uint8 (what precedes ToPILImage);

@@ -192,6 +192,7 @@ _SIGS = {
     "catseg_focal_fwd": (I, [P, P, L, I, F, P, P, P, P, SZ, P]),
     "catseg_focal_bwd": (I, [P, P, L, I, F, P, P, P, P]),
     "catseg_ingest_u8": (I, [P, P, I, I, I, P, P, I, I, P, P, P, P, P, P]),
+    "catseg_ingest_warp_u8": (I, [P, P, I, I, I, P, P, P, I, I, P, I, I, I, I, P, P, P, P, P, P, P]),
     "catseg_resize_nearest": (I, [P, I, P, I, I, I, I, I, I, I, I, I, F, P]),
     "catseg_ensemble_merge": (I, [P, P, I, L, I, I, P, I, P, P]),
     "catseg_egress_u8": (I, [P, I, I, I, I, I, I, I, I, F, I, P, P, P, I, P, P, I, P, P, P, P, P]),

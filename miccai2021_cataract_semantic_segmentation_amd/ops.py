@@ -8,6 +8,7 @@ channels_last memory format (physical OHWI).  Nothing here touches autograd.
 import collections
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1982,6 +1983,54 @@ def ingest_u8(img, lbl, lut=None, flips=None, pad_top=0, pad_bottom=0, mean=None
     check(lib.catseg_ingest_u8(ptr(img), ptr(lbl), B, H, W, ptr(lut), ptr(flips), pad_top, pad_bottom, ptr(mean), ptr(std),
                                ptr(x), ptr(x4), ptr(labels), stream()))
     return (x4 if nhwc4 else x), labels
+
+
+def ingest_warp_u8(img, lbl, lut=None, flips=None, minv=None, canvas=None, origin=None, window=None, pad_top=0, pad_bottom=0,
+                   mean=None, std=None, outputs=("nchw",)):
+    """ingest_u8 with the geometric augmentations fused in (csrc/warp.hip): remap -> flip -> warp onto `canvas` (Hc, Wc) -> `window`
+    (Hw, Ww) of the canvas at the per-frame `origin` -> reflect pad of the rows -> ToTensor / Normalize.
+    minv: HOST float64 [B,3,3] (or [B,2,3]) canvas -> frame matrices (utils.geometry.affine_inverse), None = identity on canvas = frame;
+    origin: HOST int [B,2] = (v, h), None = (0, 0); outputs: any of "nchw", "nhwc4", "u8" (the image forms; ignored without img).
+    Returns {"nchw" | "nhwc4" | "u8": tensor, ..., "labels": int64 [B,H',Ww] or None}.  The host-side values are checked here (finite
+    matrices, windows inside the canvas); whatever reaches the kernel regardless yields zeros, never an unguarded read."""
+    ref = img if img is not None else lbl
+    B, H, W = ref.shape[:3]
+    dev = ref.device
+    for t in (img, lbl, lut):
+        assert t is None or (t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda)
+    assert flips is None or (flips.dtype == torch.int32 and flips.numel() == B)
+    assert set(outputs) <= {"nchw", "nhwc4", "u8"} and (img is None or len(outputs) > 0)
+    Hc, Wc = (int(canvas[0]), int(canvas[1])) if canvas is not None else (H, W)
+    Hw, Ww = (int(window[0]), int(window[1])) if window is not None else (Hc, Wc)
+    minv_d = origin_d = None
+    if minv is not None:
+        m = np.ascontiguousarray(np.asarray(minv, dtype=np.float64)[:, :2, :])
+        if m.shape != (B, 2, 3) or not np.isfinite(m).all():
+            raise ValueError("ingest_warp_u8: the inverse matrices must be finite float64 [B, 3, 3], got shape %s" % (np.shape(minv),))
+        minv_d = torch.from_numpy(m.reshape(B, 6)).to(dev, non_blocking=True)
+    if origin is not None:
+        o = np.ascontiguousarray(np.asarray(origin, dtype=np.int64))
+        if o.shape != (B, 2) or (o < 0).any() or (o[:, 0] + Hw > Hc).any() or (o[:, 1] + Ww > Wc).any():
+            raise ValueError("ingest_warp_u8: window origins must be [B, 2] = (v, h) with the %d x %d window inside the %d x %d canvas"
+                             % (Hw, Ww, Hc, Wc))
+        origin_d = torch.from_numpy(o.astype(np.int32)).to(dev, non_blocking=True)
+    Ho = Hw + pad_top + pad_bottom
+    out = {"labels": None}
+    if img is not None:
+        assert img.shape == (B, H, W, 3)
+        if "nchw" in outputs:
+            out["nchw"] = torch.empty((B, 3, Ho, Ww), dtype=torch.float32, device=dev)
+        if "nhwc4" in outputs:
+            out["nhwc4"] = torch.empty((B, Ho, Ww, 4), dtype=torch.float32, device=dev)
+        if "u8" in outputs:
+            out["u8"] = torch.empty((B, Ho, Ww, 3), dtype=torch.uint8, device=dev)
+    if lbl is not None:
+        assert lbl.shape == (B, H, W)
+        out["labels"] = torch.empty((B, Ho, Ww), dtype=torch.int64, device=dev)
+    check(lib.catseg_ingest_warp_u8(ptr(img), ptr(lbl), B, H, W, ptr(lut), ptr(flips), ptr(minv_d), Hc, Wc, ptr(origin_d), Hw, Ww,
+                                    pad_top, pad_bottom, ptr(mean), ptr(std), ptr(out.get("nchw")), ptr(out.get("nhwc4")),
+                                    ptr(out.get("u8")), ptr(out["labels"]), stream()))
+    return out
 
 
 def resize_nearest(src, Ho, Wo, flip=0, out=None, accumulate=False, divide_by=0.0):

@@ -4,7 +4,8 @@ Mirror of what ``DatasetFromDF.__getitem__`` (datasets/Dataset_from_df.py:31-69 
 host: ``remap_mask(..., to_network=True)`` (utils/utils.py:23-47), ``FlipNP`` (utils/transforms.py:222-240),
 ``PadNP(ver=(2, 2), hor=(0, 0), 'reflect')`` (utils/transforms.py:8-20, wired at utils/utils.py:394-401), ``ToTensor`` and the
 optional ``Normalize`` (utils/utils.py:440-447); optionally the PIL blur / colour jitter between pad and ToTensor (utils/augment.py).
-The affine / crop augmentations stay on the host side of the boundary."""
+The affine / crop augmentations (``AffineNP`` with crop_to_fit=False, ``CropNP`` 'random': utils/transforms.py:23-105, 254-303) run in the
+same launch (csrc/warp.hip): ``GpuIngest(...)(..., affine=matrices, crop=(origins, px))``, parameters drawn by utils/geometry.py."""
 import numpy as np
 import torch
 
@@ -46,8 +47,11 @@ class GpuIngest:
         self.mean = torch.tensor(TORCHVISION_MEAN, device=self.device) if normalise else None
         self.std = torch.tensor(TORCHVISION_STD, device=self.device) if normalise else None
 
-    def __call__(self, img, lbl, flips=None, nhwc4=False, blur_radii=None, jitter=None):
-        """blur_radii: per-frame GaussianBlur radius (0 = none; utils.augment.sample_blur); jitter: (orders, factors) of
+    def __call__(self, img, lbl, flips=None, nhwc4=False, blur_radii=None, jitter=None, affine=None, crop=None):
+        """affine: float64 [B,3,3] frame -> canvas matrices (utils.geometry.sample_affine): the frame is warped onto the reference's
+        2H x 2W canvas; crop: (origins int32 [B,2] = (v, h), px) (utils.geometry.crop_px / sample_crops): only that px x px window of
+        the canvas (without an affine: of the frame) is computed, and -- the reference's pad rule -- the rows are not padded.
+        blur_radii: per-frame GaussianBlur radius (0 = none; utils.augment.sample_blur); jitter: (orders, factors) of
         utils.augment.sample_color_jitter.  With either, the image takes the reference's order of operations on uint8
         (flip + reflect pad -> blur -> colour jitter -> ToTensor / Normalize: utils/utils.py:394-447) in a few more kernels."""
         img = img.to(self.device, non_blocking=True) if img is not None else None
@@ -55,6 +59,8 @@ class GpuIngest:
         if flips is not None:
             flips = torch.as_tensor(np.asarray(flips, dtype=np.int32)).to(self.device, non_blocking=True)
         from .. import ops   # needs libcatseg_hip.so; the table / flag helpers above do not
+        if affine is not None or crop is not None:
+            return self._warped(ops, img, lbl, flips, nhwc4, blur_radii, jitter, affine, crop)
         if img is not None and (blur_radii is not None or jitter is not None):
             from .augment import GpuAugment
             aug = GpuAugment(self.device)
@@ -67,3 +73,27 @@ class GpuIngest:
             labels = ops.ingest_u8(None, lbl, self.lut, flips, self.pad[0], self.pad[1], self.mean, self.std)[1] if lbl is not None else None
             return x, labels
         return ops.ingest_u8(img, lbl, self.lut, flips, self.pad[0], self.pad[1], self.mean, self.std, nhwc4=nhwc4)
+
+    def _warped(self, ops, img, lbl, flips, nhwc4, blur_radii, jitter, affine, crop):
+        """one warp launch for image and labels; with blur / jitter the image leaves it as uint8 and goes on as in __call__"""
+        from .geometry import affine_inverse
+        ref = img if img is not None else lbl
+        H, W = int(ref.shape[1]), int(ref.shape[2])
+        minv = affine_inverse(affine) if affine is not None else None
+        canvas = (2 * H, 2 * W) if affine is not None else (H, W)
+        origin, window = (crop[0], (int(crop[1]), int(crop[1]))) if crop is not None else (None, canvas)
+        pad = self.pad if crop is None else (0, 0)          # utils/utils.py:396: padding only if no cropping has happened
+        staged = img is not None and (blur_radii is not None or jitter is not None)
+        form = "u8" if staged else ("nhwc4" if nhwc4 else "nchw")
+        out = ops.ingest_warp_u8(img.contiguous() if img is not None else None, lbl.contiguous() if lbl is not None else None, self.lut, flips,
+                                 minv, canvas, origin, window, pad[0], pad[1], self.mean, self.std, outputs=(form,))
+        x = out.get(form)
+        if staged:
+            from .augment import GpuAugment
+            aug = GpuAugment(self.device)
+            if blur_radii is not None:
+                x = aug.blur(x, blur_radii)
+            if jitter is not None:
+                x = aug.color_jitter(x, jitter[0], jitter[1])
+            x = ops.ingest_u8(x, None, self.lut, None, 0, 0, self.mean, self.std, nhwc4=nhwc4)[0]
+        return x, out["labels"]

@@ -12,17 +12,21 @@ computes, and remap / flip / reflect-pad / ToTensor / Normalize happen in one ke
 ``dataset[i]`` returns ``(img uint8 [H,W,3] RGB, lbl uint8 [H,W] raw CaDIS ids)`` (numpy arrays or tensors; anything after the
 second element is ignored) -- e.g. ``cv2.imread`` + BGR->RGB as datasets/Dataset_from_df.py:36-44 does.  With WORLD_SIZE > 1
 the index stream is sharded by rank (dist.ShardedSampler).  blur= / colorjitter= apply BlurPIL / ColorJitter on the GPU (utils/augment.py).
+affine= / crop= (the dicts utils.geometry.geometry_from_transforms returns for the 'rot' / 'shift' / 'shear' / 'affine' / 'crop' keywords) apply
+AffineNP / CropNP('random') in the ingest's own launch (csrc/warp.hip): x is then [B,3,px,px] for a crop, [B,3,2H+4,2W] for an affine alone.
 """
 import multiprocessing
 import multiprocessing.connection
 import os
 import queue
+import random
 import threading
 
 import numpy as np
 import torch
 
 from .augment import sample_blur, sample_color_jitter
+from .geometry import check_affine, check_crop, crop_px, sample_affine, sample_crops
 from .ingest import GpuIngest, sample_flips
 
 
@@ -123,15 +127,22 @@ class _WorkerPool:
 class PinnedFrameLoader:
     def __init__(self, dataset, batch_size, experiment, sampler=None, shuffle=True, drop_last=True, flip_probability=(0.0, 0.5),
                  pad=(2, 2), normalise=False, nhwc4=False, device="cuda", prefetch=3, workers=0, seed=0, rank=0, world=1,
-                 blur=False, colorjitter=False, worker_processes=0):
+                 blur=False, colorjitter=False, worker_processes=0, affine=None, crop=None):
         """blur / colorjitter: the 'blur' / 'colorjitter' entries of the reference's `transforms` config list (utils/utils.py:412-417):
         BlurPIL(probability=.05, kernel_limits=(3, 7)) and ColorJitter((2/3, 1.5) x 3, hue (-.05, .05)) on the padded uint8 frames,
-        as GPU kernels (utils/augment.py)"""
+        as GPU kernels (utils/augment.py).
+        affine / crop: the "affine" / "crop" entries of utils.geometry.geometry_from_transforms (AffineNP's parameters; {"size", "mode"}).
+        Their draws are seeded per epoch like the flips; with a crop the rows are not padded (the reference's pad rule)"""
         self.dataset, self.batch, self.drop_last = dataset, int(batch_size), drop_last
         self.device = torch.device(device)
         self.ingest = GpuIngest(experiment, pad=pad, normalise=normalise, device=device)
         self.flip_p, self.nhwc4 = flip_probability, nhwc4
         self.blur, self.colorjitter = bool(blur), bool(colorjitter)
+        self.affine, self.crop = affine, crop
+        if affine is not None:
+            check_affine(affine)        # (crop_to_fit=True is refused)
+        if crop is not None:
+            check_crop(crop)            # (crop_mode 'freq' is refused)
         # workers = 0: no fill thread -- each batch is stacked into its staging slot by the CONSUMER's thread inside next(), i.e. after the
         # previous step's kernels have been enqueued and while the GPU runs them (a fill thread shares the interpreter lock with the
         # launch loop of ~3000 kernels per step: on a busy host that stretched an HRNet-W48 step by 10 - 30 ms; the inline fill costs the
@@ -209,7 +220,25 @@ class PinnedFrameLoader:
         self._slots = [(torch.empty((self.batch, h, w, 3), dtype=torch.uint8).pin_memory(),
                         torch.empty((self.batch, h, w), dtype=torch.uint8).pin_memory()) for _ in range(self.prefetch + 1)]
 
-    def _emit(self, slot, n, fl, br, jt):
+    def _geometry(self, batches, frame, rng):
+        """per batch {"affine": matrices, "crop": (origins, px)} for GpuIngest (empty dicts without affine= / crop=).  The affine draws
+        continue the epoch's numpy stream after the flips and blurs; the crops take Python's random module, as CropNP does"""
+        if self.affine is None and self.crop is None:
+            return [{} for _ in batches]
+        h, w = (2 * frame[0], 2 * frame[1]) if self.affine is not None else frame     # CropNP sees the canvas
+        px = crop_px(self.crop["size"], h, w) if self.crop is not None else None
+        pyrng = random.Random(self.seed * 1000003 + self.epoch)
+        out = []
+        for b in batches:
+            g = {}
+            if self.affine is not None:
+                g["affine"] = sample_affine(len(b), frame, self.affine, rng)[1]
+            if self.crop is not None:
+                g["crop"] = (sample_crops(len(b), (h, w), px, pyrng), px)
+            out.append(g)
+        return out
+
+    def _emit(self, slot, n, fl, br, jt, geo):
         """host -> device copy of a filled staging slot on the side stream + the ingest kernels; returns (x, labels, copy event)"""
         img_buf, lbl_buf = self._slots[slot]
         with torch.cuda.stream(self.copy_stream):          # pinned: truly asynchronous
@@ -221,10 +250,10 @@ class PinnedFrameLoader:
         cur.wait_event(done)                               # the ingest kernel waits for the copy, the host does not
         img_d.record_stream(cur)
         lbl_d.record_stream(cur)
-        x, labels = self.ingest(img_d, lbl_d, fl, nhwc4=self.nhwc4, blur_radii=br, jitter=jt)
+        x, labels = self.ingest(img_d, lbl_d, fl, nhwc4=self.nhwc4, blur_radii=br, jitter=jt, **geo)
         return x, labels, done
 
-    def _iter_processes(self, batches, flips, blurs, jitters):
+    def _iter_processes(self, batches, flips, blurs, jitters, geos):
         """the worker processes run `prefetch` batches ahead; a staging slot returns to them when its copy has left it"""
         pool = self._pool
         free = list(range(len(self._slots)))
@@ -249,7 +278,7 @@ class PinnedFrameLoader:
                     continue
                 pool.wait(base + bi)
                 sl = slot_of.pop(bi)
-                x, labels, done = self._emit(sl, len(batches[bi]), flips[bi], blurs[bi], jitters[bi])
+                x, labels, done = self._emit(sl, len(batches[bi]), flips[bi], blurs[bi], jitters[bi], geos[bi])
                 in_copy.append((done, sl))
                 bi += 1
                 yield x, labels
@@ -278,11 +307,12 @@ class PinnedFrameLoader:
         ready = queue.Queue(maxsize=self.prefetch)
         free = queue.Queue()
         first = self.dataset[batches[0][0]] if batches else None
+        geos = self._geometry(batches, tuple(int(v) for v in np.asarray(first[0]).shape[:2]), rng) if batches else []
         if first is not None and (self._slots is None or tuple(self._slots[0][0].shape[1:3]) != tuple(np.asarray(first[0]).shape[:2])
                                   or (self.nproc and self._pool is None)):
             self._alloc(*np.asarray(first[0]).shape[:2])
         if self.nproc and batches:
-            yield from self._iter_processes(batches, flips, blurs, jitters)
+            yield from self._iter_processes(batches, flips, blurs, jitters, geos)
             return
         for s in range(len(self._slots or [])):
             free.put(s)
@@ -325,7 +355,7 @@ class PinnedFrameLoader:
                     if stop.is_set():
                         return
                     fill(slot, ids)
-                    if not put(ready, (slot, len(ids), flips[bi], blurs[bi], jitters[bi])):
+                    if not put(ready, (slot, len(ids), flips[bi], blurs[bi], jitters[bi], geos[bi])):
                         return
             finally:
                 put(ready, None)
@@ -359,13 +389,13 @@ class PinnedFrameLoader:
                         free.put(sl)
                     sl = free.get()
                     fill(sl, batches[nxt])
-                    item = (sl, len(batches[nxt]), flips[nxt], blurs[nxt], jitters[nxt])
+                    item = (sl, len(batches[nxt]), flips[nxt], blurs[nxt], jitters[nxt], geos[nxt])
                     nxt += 1
                 else:
                     item = ready.get()
                 if item is None:
                     break
-                slot, n, fl, br, jt = item
+                slot, n, fl, br, jt, geo = item
                 img_buf, lbl_buf = self._slots[slot]
                 with torch.cuda.stream(self.copy_stream):          # host -> device on the side stream (pinned: truly asynchronous)
                     img_d = img_buf[:n].to(self.device, non_blocking=True)
@@ -375,7 +405,7 @@ class PinnedFrameLoader:
                 torch.cuda.current_stream(self.device).wait_event(done)   # the ingest kernel waits for the copy, the host does not
                 img_d.record_stream(torch.cuda.current_stream(self.device))
                 lbl_d.record_stream(torch.cuda.current_stream(self.device))
-                x, labels = self.ingest(img_d, lbl_d, fl, nhwc4=self.nhwc4, blur_radii=br, jitter=jt)
+                x, labels = self.ingest(img_d, lbl_d, fl, nhwc4=self.nhwc4, blur_radii=br, jitter=jt, **geo)
                 in_copy.append((done, slot))
                 yield x, labels
         finally:
