@@ -280,6 +280,27 @@ int catseg_maxpool2x2_fwd(const float* x, int ldx, float* y, int ldy, uint8_t* i
 int catseg_maxpool2x2_bwd(const float* dy, int lddy, const uint8_t* idx, float* dx, int lddx, int B, int H, int W, int C, catseg_stream_t stream);
 int catseg_bias_rows(const float* bias, float* out, int ld, long long rows, int C, catseg_stream_t stream);
 
+/* ---- UNet pieces (models/UNet.py:6-63 of the reference: conv + bias + ReLU without BatchNorm, MaxPool2d(2), 2x bilinear Upsample with
+ * align_corners=True, torch.cat([up, skip], 1)); csrc/unet.hip.  The passes a skip junction needs anyway also leave the amax records
+ * (CATSEG_AMAX_RECORD_BYTES, zeroed by the caller; max|.| of exactly what was written is folded into the slots) that let the layers reach
+ * the split-precision direct / pointwise / gather kernels.  NHWC fp32, every C and ld a multiple of 4, 16-byte aligned tensors; anything
+ * else returns CATSEG_EINVAL and launches nothing.  Pad columns (ld > C) are never read.
+ *   catseg_amax_record         record <- max|x| over [rows][0 .. C): a read-only pass
+ *   catseg_maxpool2x2_fwd_rec  y, idx exactly as catseg_maxpool2x2_fwd; x_record <- max|x| over the whole input (an odd last row / column
+ *                              included), y_record <- max|y|; either record may be NULL
+ *   catseg_upcat2x_fwd         cat[B, 2h, 2w, 0 .. Cx) = catseg_bilinear_fwd(x [B, h, w, Cx], align_corners = 1) bit for bit,
+ *                              cat[B, 2h, 2w, Cx .. Cx + Cs) = skip [B, 2h, 2w, Cs]; record (may be NULL) <- max|cat|
+ *   catseg_relu_bwd_rec        g = d * (z > 0) on [B, H, W, C], record (may be NULL) <- max|g|.  dpool == idx == NULL: d = dz.  Junction
+ *                              form (z fed a 2x2 max-pool AND a concatenation): d = dz + catseg_maxpool2x2_bwd(dpool [B, H/2, W/2, C], idx),
+ *                              dz being the channel slice of the concatenation's gradient (pointer to its first column, lddz its ld) */
+int catseg_amax_record(const float* x, int ld, long long rows, int C, void* record, catseg_stream_t stream);
+int catseg_maxpool2x2_fwd_rec(const float* x, int ldx, float* y, int ldy, uint8_t* idx, int B, int H, int W, int C, void* x_record,
+                              void* y_record, catseg_stream_t stream);
+int catseg_upcat2x_fwd(const float* x, int ldx, const float* skip, int lds, float* cat, int ldc, int B, int h, int w, int Cx, int Cs,
+                       void* record, catseg_stream_t stream);
+int catseg_relu_bwd_rec(const float* dz, int lddz, const float* dpool, int lddp, const uint8_t* idx, const float* z, int ldz, float* g,
+                        int ldg, int B, int H, int W, int C, void* record, catseg_stream_t stream);
+
 /* ---- fp16 x 2 OPERAND PLANES written by the producer of a tensor, and the direct 3x3 kernels that stream them (round 4;
  * csrc/planes.h, csrc/dconv3_pl.hip).  Replaces, for the same reference layers as catseg_dconv3_f16x2 (conv3x3(planes, planes) of
  * models/HRNetv2.py:22-65), the in-kernel fp32 -> 2 x fp16 split: planes = [plane h / l][C / 8 channel groups][pixel][8] fp16,

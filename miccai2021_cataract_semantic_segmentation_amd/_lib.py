@@ -87,6 +87,10 @@ _SIGS = {
     "catseg_maxpool2x2_fwd": (I, [P, I, P, I, P, I, I, I, I, P]),
     "catseg_maxpool2x2_bwd": (I, [P, I, P, P, I, I, I, I, I, P]),
     "catseg_bias_rows": (I, [P, P, I, L, I, P]),
+    "catseg_amax_record": (I, [P, I, L, I, P, P]),
+    "catseg_maxpool2x2_fwd_rec": (I, [P, I, P, I, P, I, I, I, I, P, P, P]),
+    "catseg_upcat2x_fwd": (I, [P, I, P, I, P, I, I, I, I, I, I, P, P]),
+    "catseg_relu_bwd_rec": (I, [P, I, P, I, P, P, I, P, I, I, I, I, I, P, P]),
     "catseg_bn_mask_bytes": (SZ, [L, I]),
     "catseg_conv2d_fwd_fused": (I, [P, P, P, P, P, I, I, P, P]),
     "catseg_fold_bn": (I, [P, P, P, P, P, P, F, I, I, P, P, P]),

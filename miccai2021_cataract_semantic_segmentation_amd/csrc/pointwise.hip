@@ -2,6 +2,7 @@
 // global average pool and the two softmaxes of the OCR head.  All NHWC fp32, all
 // deterministic (backward passes are written as gathers, never atomics).
 #include "planes.h"
+#include "lerp.h"
 
 // 1 (default): catseg_bilinear_bwd runs as one launch with its intermediate row in LDS where the layout allows; 0: the two separable passes
 int catseg_g_bilinear_bwd_fused = 1;
@@ -231,25 +232,6 @@ __global__ void maxpool_bwd_kernel(const float* __restrict__ dy, int lddy, const
 
 // ------------------------------------------------------------------ bilinear
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *(const f32x4*)p; }
-// ATen's area_pixel_compute_source_index in fp32
-__device__ __forceinline__ float src_index(float scale, int dst, bool align) {
-  if (align) return scale * dst;
-  const float s = scale * (dst + 0.5f) - 0.5f;
-  return s < 0.f ? 0.f : s;
-}
-__device__ __forceinline__ void lerp_setup(float scale, int dst, bool align, int in_size, int& i0, int& i1, float& l0, float& l1) {
-  const float s = src_index(scale, dst, align);
-  i0 = (int)s;
-  if (i0 > in_size - 1) i0 = in_size - 1;
-  i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-  l1 = s - i0;
-  l0 = 1.f - l1;
-}
-__host__ __device__ inline float resize_scale(int in, int out, bool align) {
-  if (align) return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
-  return (float)in / (float)out;
-}
-
 // MODE 0: scalar (any C / ld); MODE 1: contiguous output rows (ldy == C), 4 consecutive floats of the flat (ox, c) index per
 // thread, 16-byte stores (the K-class logits at full resolution: C = 25); MODE 2: C % 4 == 0, 4 channels of one pixel per thread,
 // 16-byte loads and stores (HRNet / ASPP / decoder feature maps, also into channel slices of a concat buffer).

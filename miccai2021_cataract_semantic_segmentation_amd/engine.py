@@ -202,6 +202,7 @@ class Ctx:
         self._deferred = []            # backward: parameters whose 'gradient ready' signal waits for the join
         self.bn_src = {}               # id(z) -> (y, stats, gamma, beta) of a conv_bn_act output z = relu(bn(y))
         self.bn_pre = {}               # backward: id(z) -> per-tile sums of the already masked gradient of z (conv_bn_act private_in)
+        self.pool_pending = {}         # backward: id(z) -> (dpool, idx) of maxpool2(record=True) for the junction backward of conv_act(record="pool")
 
     def claim(self, *params):
         """every parameter may feed exactly one recorded layer: the backward tape WRITES (does not accumulate) parameter
@@ -397,6 +398,7 @@ class Ctx:
         self.shared.clear()
         self.bn_src.clear()
         self.bn_pre.clear()
+        self.pool_pending.clear()
 
 
 # --------------------------------------------------------------------------- fused layers
@@ -765,6 +767,11 @@ def conv_bias(cx, x, conv, pad_to=32):
             dy = cx.take(y)
             if dy is None:
                 return
+            if ops.ld_of(dy) % 4:   # the layer is the network's output (models/UNet.py) and the loss hands its gradient over as a dense
+                #                     [B, H, W, K] tensor: re-pitch it (a copy), as conv_transpose_bwd does
+                padded = ops.new_act(dy.shape[0], dy.shape[1], dy.shape[2], Cout, dy.device, ld=ld, zero=True)
+                padded.copy_(dy)
+                dy = padded
             ops.conv_bwd_weight(x, dy, cx.pgrad(w), cx.pgrad(b), kh, kw, s, p, d)
             dx, acc = cx.dest(x)
             ops.conv_bwd_data(dy, w.data, tuple(x.shape), kh, kw, s, p, d, out=dx, accumulate=acc)
@@ -773,21 +780,47 @@ def conv_bias(cx, x, conv, pad_to=32):
     return y
 
 
-def conv_act(cx, x, conv, relu=True):
+def conv_act(cx, x, conv, relu=True, record=False):
     """conv + bias (+ ReLU) without normalisation -- the VGG-style layers of models/FCN.py:42-55 of the reference: bias and ReLU run in
-    the convolution's epilogue.  x NHWC (or the raw NCHW image for a 3-channel first layer)."""
+    the convolution's epilogue.  x NHWC (or the raw NCHW image for a 3-channel first layer).
+    record (models/UNet.py; needs relu; a no-op unless ops.bnfree_records()): the layer works on amax records -- its forward takes the
+    route the planner gives an input with a record, its output z carries one, and its backward masks dz with ops.relu_bwd_rec, so that
+    backward-data and backward-weight see the record of dy.  record=True: z's record comes from a pass of its own (ops.amax_record) unless
+    the ReLU pass behind a direct / gather kernel has left it; record="pool": z is read by maxpool2(record=True) and upcat alone -- the pool
+    leaves z's record, and the layer's backward adds the pooled gradient to the concatenation's slice in the same pass (junction form)."""
     c = ops.conv_args(conv)
     inp = PAD3 if c.weight.shape[1] == 3 else PLAIN
     x_in, wk = _conv_input(inp, x, c)
     cx.claim(c.weight, c.bias)
-    z = ops.conv_fwd_fused(x_in, wk, c.bias.data if c.bias is not None else None, None, relu, c.Cout, c.kh, c.kw, c.stride, c.pad, c.dil)
+    rec = bool(record) and relu and ops.bnfree_records()
+    bias = c.bias.data if c.bias is not None else None
+    direct = rec and inp == PLAIN and ops.fwd_route(ops.Layer(x_in.shape, c.Cout, c.kh, c.kw, c.stride, c.pad, c.dil, ldx=ops.ld_of(x_in), bias=bias is not None,
+                                                              x_amax=ops.amax_of(x_in) is not None)).kind in ("d3h", "d3", "p1", "s2p")
+    if direct:
+        # the direct / pointwise / gather kernels add the bias but have no ReLU epilogue: the ReLU pass that follows leaves z's record
+        z = ops.conv_fwd(x_in, wk, bias, c.Cout, c.kh, c.kw, c.stride, c.pad, c.dil, train=cx.record)
+        ops.add_n_act([z], True, out=z)
+    else:
+        z = ops.conv_fwd_fused(x_in, wk, bias, None, relu, c.Cout, c.kh, c.kw, c.stride, c.pad, c.dil)
+        if rec and record != "pool":
+            ops.amax_record(z)
+    if rec and record == "pool":
+        z._junction = True
     if cx.record:
         def bwd():
             dz = cx.take(z)
+            pend = cx.pool_pending.pop(id(z), None)
+            if dz is None and pend is not None:     # (only the pool consumed z)
+                dz = torch.empty(z.shape, dtype=torch.float32, device=z.device)
+                ops.maxpool2_bwd(pend[0], pend[1], dz)
+                pend = None
             if dz is None:
                 return
-            dy = ops.relu_bwd(dz, z) if relu else dz
-            del dz
+            if rec:
+                dy = ops.relu_bwd_rec(dz, z, pool=pend)
+            else:
+                dy = ops.relu_bwd(dz, z) if relu else dz
+            del dz, pend
             _conv_weight_grad(cx, inp, c, x_in, wk, dy)
             if inp == PLAIN:
                 dx, acc = cx.dest(x)
@@ -797,18 +830,50 @@ def conv_act(cx, x, conv, relu=True):
     return z
 
 
-def maxpool2(cx, x):
-    """F.max_pool2d(x, 2) (models/FCN.py:44-53 of the reference)"""
-    y, idx = ops.maxpool2_fwd(x)
+def maxpool2(cx, x, record=False):
+    """F.max_pool2d(x, 2) (models/FCN.py:44-53 of the reference).  record (a no-op unless ops.bnfree_records()): the pass also leaves the
+    amax records of x and of the result (ops.maxpool2_fwd_rec); where x is the output of conv_act(record="pool") the pooled gradient is
+    not scattered here but handed to that layer's backward (Ctx.pool_pending)."""
+    rec = record and ops.bnfree_records()
+    y, idx = ops.maxpool2_fwd_rec(x) if rec else ops.maxpool2_fwd(x)
     if cx.record:
+        junction = rec and getattr(x, "_junction", False)
+
         def bwd():
             dy = cx.take(y)
             if dy is None:
+                return
+            if junction:
+                cx.pool_pending[id(x)] = (dy, idx)
                 return
             dx, acc = cx.dest(x)
             ops.maxpool2_bwd(dy, idx, dx, acc)
         cx.push(bwd)
     return y
+
+
+def upcat(cx, x, skip):
+    """torch.cat([Upsample(2, bilinear, align_corners=True)(x), skip], 1) (models/UNet.py:48-57 of the reference).  With ops.bnfree_records()
+    one launch that also leaves the concatenation's amax record (ops.upcat2x_fwd); otherwise composed of bilinear(out=slice), copy_into
+    and concat_views.  Either way the gradient of the resized half goes back through bilinear_bwd on its slice and skip receives its slice."""
+    B, h, w, Cx = x.shape
+    Cs = skip.shape[-1]
+    if not ops.bnfree_records():
+        cat = torch.empty((B, 2 * h, 2 * w, Cx + Cs), dtype=torch.float32, device=x.device)
+        up = bilinear(cx, x, 2 * h, 2 * w, True, out=cat[..., :Cx])
+        sk = copy_into(cx, skip, cat[..., Cx:])
+        return concat_views(cx, cat, [(up, 0, Cx), (sk, Cx, Cx + Cs)])
+    cat = ops.upcat2x_fwd(x, skip)
+    if cx.record:
+        def bwd():
+            dcat = cx.take(cat)
+            if dcat is None:
+                return
+            dx, acc = cx.dest(x)
+            ops.bilinear_bwd(dcat[..., :Cx], tuple(x.shape), True, out=dx, accumulate=acc)
+            cx.give(skip, dcat[..., Cx:])
+        cx.push(bwd)
+    return cat
 
 
 class ConvTranspose2d(nn.ConvTranspose2d):

@@ -1715,6 +1715,72 @@ def maxpool2_bwd(dy, idx, out, accumulate=False):
     return out
 
 
+# Records without BatchNorm (csrc/unet.hip).  The f16x2 direct / pointwise / gather kernels take a layer only when its input (backward: its
+# output gradient) carries an amax record; in a conv + bias + ReLU network (models/UNet.py) none of the record producers above runs.  With
+# the plan field `bnfree_records` the engine's recording layers (conv_act(record=), maxpool2(record=True), upcat) leave the records in the
+# passes the skip junction needs anyway.  CATSEG_BNFREE_RECORDS=0: the composed passes without records (fp32 MFMA / bf16x3 routes).
+# Measured (tools/time_unet.py, profiles/unet_step_time.json, one run: 8 x 3 x 544 x 960, five alternating rounds of four steps, medians):
+# UNet train step 125.3 -> 82.7 ms in the launch loop, 125.2 -> 82.6 ms as hipGraph replay -- the field is on by default.
+BNFREE_RECORDS = _plan.get("bnfree_records")
+
+
+def bnfree_records():
+    return bool(BNFREE_RECORDS and _trunk_h2())
+
+
+def amax_record(x):
+    """attaches the record of max|x| to x (a read-only pass over its valid columns) and returns x"""
+    rec = new_amax(x.device)
+    with _Timed("hbm:amax_record", 4.0 * x.numel()):
+        check(lib.catseg_amax_record(ptr(x), ld_of(x), rows_of(x), x.shape[-1], ptr(rec), stream()))
+    x._amax = rec
+    return x
+
+
+def maxpool2_fwd_rec(x):
+    """maxpool2_fwd + the amax records of its input (attached to x when it has none) and of its output"""
+    B, H, W, C = x.shape
+    y = torch.empty((B, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
+    idx = torch.empty((B, H // 2, W // 2, C), dtype=torch.uint8, device=x.device)
+    xrec = new_amax(x.device) if amax_of(x) is None else None
+    yrec = new_amax(x.device)
+    with _Timed("hbm:maxpool2_fwd_rec", 4.0 * x.numel() + 5.0 * y.numel()):
+        check(lib.catseg_maxpool2x2_fwd_rec(ptr(x), ld_of(x), ptr(y), C, ptr(idx), B, H, W, C, ptr(xrec), ptr(yrec), stream()))
+    if xrec is not None:
+        x._amax = xrec
+    y._amax = yrec
+    return y, idx
+
+
+def upcat2x_fwd(x, skip, record=True):
+    """cat = [bilinear 2x (align_corners=True) of x, skip] along the channels in one launch; record: with the amax record of cat"""
+    B, h, w, Cx = x.shape
+    Cs = skip.shape[-1]
+    assert tuple(skip.shape[:3]) == (B, 2 * h, 2 * w)
+    cat = torch.empty((B, 2 * h, 2 * w, Cx + Cs), dtype=torch.float32, device=x.device)
+    rec = new_amax(x.device) if record else None
+    with _Timed("hbm:upcat2x_fwd", 4.0 * (x.numel() + skip.numel() + cat.numel())):
+        check(lib.catseg_upcat2x_fwd(ptr(x), ld_of(x), ptr(skip), ld_of(skip), ptr(cat), Cx + Cs, B, h, w, Cx, Cs, ptr(rec), stream()))
+    if rec is not None:
+        cat._amax = rec
+    return cat
+
+
+def relu_bwd_rec(dz, z, pool=None, record=True):
+    """g = d * (z > 0) with the amax record of g.  pool = (dpool, idx): z also fed a 2x2 max-pool, d = dz + the pooled gradient routed
+    through idx (maxpool2_bwd), in the same pass; dz may be a channel slice of a wider gradient buffer"""
+    B, H, W, C = z.shape
+    g = torch.empty(z.shape, dtype=torch.float32, device=z.device)
+    rec = new_amax(z.device) if record else None
+    dpool, idx = pool if pool is not None else (None, None)
+    with _Timed("hbm:relu_bwd_rec", 4.0 * 3 * z.numel() + (5.0 * dpool.numel() if dpool is not None else 0.0)):
+        check(lib.catseg_relu_bwd_rec(ptr(dz), ld_of(dz), ptr(dpool), ld_of(dpool) if dpool is not None else 0, ptr(idx), ptr(z), ld_of(z), ptr(g), C,
+                                      B, H, W, C, ptr(rec), stream()))
+    if rec is not None:
+        g._amax = rec
+    return g
+
+
 def widen(t):
     """the [B, H, W, ld] tensor behind a class-logit view [B, H, W, K] whose rows are zero padded to ld floats (conv_fwd(zero_to=),
     engine.Ctx.dest): the 16-byte-granular kernels run on all ld columns"""

@@ -50,6 +50,7 @@ FIELDS = {
     "g1_dgrad_min_cin": (48, int, "ops:G1_DGRAD_MIN_CIN", "gather route, backward-data: minimum input channels"),
     "g1_min_cin": (0, int, "ops:G1_MIN_CIN", "gather route: minimum input channels"),
     "g1_ops": (("fwd", "dgrad", "wgrad"), _csv_str, "ops:G1_OPS", "directions of the gather route"),
+    "bnfree_records": (True, _bool, "ops:BNFREE_RECORDS", "conv + bias + ReLU networks without BatchNorm (models/UNet.py): the pool / skip-junction / ReLU-backward passes leave amax records (csrc/unet.hip), so their layers reach the f16x2 direct and gather kernels (UNet step 125.2 -> 82.6 ms, profiles/unet_step_time.json); off: the composed passes, no records"),
     "stem3": (True, _bool, "ops:STEM3", "HRNet stem conv1 on the direct fp64-accumulating kernels (csrc/stem3.hip)"),
     "stem7": (True, _bool, "ops:STEM7", "ResNet stem conv1, training forward, on the direct fp64-accumulating kernel (csrc/stem7.hip)"),
     "exact_early": ("all", str, None, "HRNet layers whose forward stays on exact fp32 operands: 'layer1' / 'stem' / 'all' (models/HRNetv2.py)"),
