@@ -763,6 +763,41 @@ size_t catseg_gconv_wgrad_workspace(const catseg_conv_desc* d);
 int catseg_gconv_bwd_weight(const catseg_conv_desc* d, const float* dy, const void* dy_rec, const float* x, const void* x_rec,
                             float* dw, void* workspace, size_t workspace_bytes, catseg_stream_t stream);
 
+/* ---- PointRend, eval-mode refinement (models/PointRend.py:74-90 of the reference: F.interpolate x 2, calculate_uncertainty, torch.topk,
+ * five point_sample = F.grid_sample calls, torch.cat, scatter_; csrc/pointrend.hip).  The point head's layers are 1 x 1 convolutions over
+ * the N k points and run through catseg_conv2d_fwd / catseg_conv2d_fwd_fused; the upsampling is the catseg_bilinear_fwd launch.  Nothing here synchronises with the host or allocates: a
+ * refinement step can be captured in a hipGraph.
+ *   uncertainty: uncertainty[p] = second-largest - largest of y[p ldy + 0 .. K) (<= 0; equal logits give 0), p < pixels: the rows the resize
+ *               launch (catseg_bilinear_fwd, align_corners = 0, x 2) stored.  Columns K .. ldy are never read.  K >= 2 (one class has no
+ *               second logit: CATSEG_EINVAL), ldy >= K.
+ *   topk:       idx [N, k] (int32, ascending) = the k largest of uncertainty [N, n] per image; among equal values the LOWER index is
+ *               taken, -0.0 equals +0.0; deterministic.  1 <= k <= n < 2^31 (k = n selects everything), N <= 65535; workspace of
+ *               the size the workspace query returns, 16-byte aligned (CATSEG_EWORKSPACE otherwise).
+ *   gather:     per image b and point p: the centre of cell idx[b, p] of the h x w grid, x = (1/w)/2 + (idx % w) (1/w), y likewise, every
+ *               operation rounded to fp32 as utils/pointrend_utils.py:146-147 does; from every source s (NHWC [N, H_s, W_s, C_s], pixel
+ *               stride ld_s) F.grid_sample(bilinear, align_corners = False, ZERO padding) at 2 (x, y) - 1; out[b k + p] = the sources'
+ *               blocks side by side, each C_s rounded up to 4 columns wide, the pad columns zero.  The LAST source's block is also
+ *               written to extra[q] + (b k + p) extra_ld[q] + extra_off[q], q < n_extra (the coarse logits that every layer of the
+ *               point head concatenates to its input).  ld_s >= C_s; a source whose pixels are 16-byte aligned rows of at least C_s rounded
+ *               up to 4 floats is read with 16-byte loads, any other (dense K-class logits) one channel per lane; out and extra 16-byte aligned.
+ *   scatter:    seg[b, idx[b, p], 0:K] = rows[b k + p, 0:K] (seg: [N, hw] pixels of ld_seg floats). */
+typedef struct {
+  const float* src[5]; int ld[5], H[5], W[5], C[5];
+  int n_sources;                 /* 1 .. 5 */
+  const int* idx;                /* [N, k] pixel indices of the h x w grid */
+  int N, k, h, w;
+  float* out; int ld_out;        /* [N k] rows */
+  float* extra[4]; int extra_ld[4], extra_off[4];
+  int n_extra;                   /* 0 .. 4 */
+} catseg_pointrend_gather_desc;
+int catseg_pointrend_uncertainty(const float* y, int ldy, float* uncertainty, long long pixels, int K, catseg_stream_t stream);
+size_t catseg_pointrend_topk_workspace(int N, long long n);
+int catseg_pointrend_topk(const float* uncertainty, int N, long long n, int k, int* idx, void* workspace, size_t workspace_bytes,
+                          catseg_stream_t stream);
+int catseg_pointrend_gather(const catseg_pointrend_gather_desc* d, catseg_stream_t stream);
+int catseg_pointrend_scatter(const float* rows, int ld_rows, const int* idx, int N, int k, long long hw, float* seg, int ld_seg, int K,
+                             catseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

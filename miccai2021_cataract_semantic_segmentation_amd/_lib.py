@@ -40,6 +40,11 @@ class BnBackwardDesc(C.Structure):
                 ("dy_planes", P), ("dy_h2_planes", P), ("dy_h2_scale", P), ("dbias", P)]
 
 
+class PointrendGatherDesc(C.Structure):
+    _fields_ = [("src", P * 5), ("ld", I * 5), ("H", I * 5), ("W", I * 5), ("C", I * 5), ("n_sources", I), ("idx", P), ("N", I), ("k", I), ("h", I),
+                ("w", I), ("out", P), ("ld_out", I), ("extra", P * 4), ("extra_ld", I * 4), ("extra_off", I * 4), ("n_extra", I)]
+
+
 _SIGS = {
     "catseg_last_error": (C.c_char_p, []),
     "catseg_version": (I, []),
@@ -225,6 +230,11 @@ _SIGS = {
     "catseg_adam_hyper": (None, [F, F, F, I, F, P]),
     "catseg_adam_step_dev": (I, [P, P, P, P, L, P, F, F, F, P]),
     "catseg_lds_limits": (I, [P, P]),
+    "catseg_pointrend_uncertainty": (I, [P, I, P, L, I, P]),
+    "catseg_pointrend_topk_workspace": (SZ, [I, L]),
+    "catseg_pointrend_topk": (I, [P, I, L, I, P, P, SZ, P]),
+    "catseg_pointrend_gather": (I, [P, P]),
+    "catseg_pointrend_scatter": (I, [P, I, P, I, I, L, P, I, I, P]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header / library mismatch

@@ -1021,6 +1021,15 @@ def concat_views(cx, cat, parts):
     return cat
 
 
+def pointrend_refine(cx, seg, feats, head, k0, steps):
+    """models/PointRend.py:74-90 of the reference, the eval-mode refinement loop (ops.pointrend_refine).  Forward only: nothing differentiates
+    through the point branch, so a training or recorded pass is refused"""
+    if cx.train or cx.record:
+        raise NotImplementedError("the PointRend refinement runs in eval mode only: its train-mode forward (random point sampling, point loss) "
+                                  "and the backward of the point gather are not on the accelerated path")
+    return ops.pointrend_refine(seg, feats, head, k0, steps)
+
+
 def spatial_gather(cx, feats, logits, K):
     """models/OCR.py:158-170: proxy[b, k, :] = sum_n softmax_n(logits[b, n, k]) * feats[b, n, :]"""
     B, H, W, C = feats.shape

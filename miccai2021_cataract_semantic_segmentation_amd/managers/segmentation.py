@@ -54,6 +54,12 @@ class EncDecManager(BaseManager):
     (:16-21, configs/UPN_rf_lvsz.json has no 'graph'), the loss is always a LossWrapper (:23-29), and the step is
     ``deep_features, prediction = model(img); loss = LossWrapper(deep_features, prediction, lbl, epoch=epoch)`` (:158-185)."""
 
+    def __init__(self, configuration, *args, **kwargs):
+        if configuration.get("mode") == "training" and configuration.get("decoder", {}).get("model") == "PointRend":
+            from ..models.EncDec import POINTREND_TRAINING_REFUSAL
+            raise NotImplementedError(POINTREND_TRAINING_REFUSAL)        # (before anything is built: validate / infer / demo_infer run)
+        super().__init__(configuration, *args, **kwargs)
+
     def load_model(self):
         from .. import dist as D
         from ..models import EncDec

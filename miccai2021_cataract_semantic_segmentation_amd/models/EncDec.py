@@ -1,12 +1,15 @@
 """Encoder-decoder segmentation nets on the HIP engine: the reference's EncDec (models/EncDec.py:7-53) with
 the ResNet / ResNeXt encoder wrappers (models/ResNet.py:5-94, models/ResNeXt.py:5-60: torchvision trunks
-returning the four stage outputs) and the UPerNet decoder (models/UPerNet.py:7-145).  State-dict keys as
-in the reference: ``enc_model.layer1.0.conv1.weight``, ``dec_model.ppm_conv.0.0.weight`` ..."""
+returning the four stage outputs), the UPerNet decoder (models/UPerNet.py:7-145) and, for evaluation and inference, the PointRend
+decoder (models/PointRend.py:8-141).  State-dict keys as in the reference: ``enc_model.layer1.0.conv1.weight``,
+``dec_model.ppm_conv.0.0.weight``, ``dec_model.partial_upernet.ppm_conv.0.0.weight``, ``dec_model.point_head.fc1.weight`` ..."""
+import math
+
 import torch
 from torch import nn
 
 from ..engine import (BatchNorm2d, Conv2d, EngineNet, adaptive_avgpool, add_n, bilinear, concat_views, conv_bias,
-                      conv_bn_act, copy_into, maxpool)
+                      conv_bn_act, copy_into, maxpool, pointrend_refine)
 from ..utils import num_classes
 from .backbone import BasicBlock, Bottleneck, _c1, load_pretrained_trunk
 
@@ -158,23 +161,94 @@ class UPerNet(nn.Module):
         return x
 
 
+POINTREND_TRAINING_REFUSAL = ("PointRend's train-mode forward is not on the accelerated path: the random point sampling "
+                              "(get_uncertain_point_coords_with_randomness), the point cross-entropy loss and the backward of the point gather "
+                              "are missing; the eval-mode forward (model.eval(): validation, inference, Ensemble member, TTA, demo_infer) is there")
+
+
+class StandardPointHead(nn.Module):
+    """models/PointRend.py:93-141 of the reference: num_fc layers nn.Conv1d(kernel_size=1) + ReLU over the points, the coarse logits
+    concatenated to every layer's input, and the predictor.  The parameters keep the reference's shapes [out, in, 1]; the layers run as
+    1 x 1 convolutions over the N k points (ops.pointrend_refine)."""
+
+    def __init__(self, config, num_classes):
+        super().__init__()
+        self.num_classes = num_classes
+        self.fc_dim = config.get("ph_fc_dim", 256)
+        self.num_fc = config.get("ph_num_fc", 3)
+        self.coarse_pred_each_layer = config.get("ph_coarse_in_each_layer", True)
+        coarse = num_classes if self.coarse_pred_each_layer else 0
+        widths = [sum(config["input_channels"]) + num_classes] + [self.fc_dim + coarse] * self.num_fc      # input width of fc1 .. fcN, predictor
+        for i, cin in enumerate(widths[:-1], 1):
+            setattr(self, "fc%d" % i, nn.Conv1d(cin, self.fc_dim, 1))
+        self.predictor = nn.Conv1d(widths[-1], num_classes, 1)
+        nn.init.normal_(self.predictor.weight, std=0.001)      # (the reference's start: point logits near zero)
+        nn.init.zeros_(self.predictor.bias)
+        self._images = {}       # zero-padded device images of the weights (ops.pointrend_refine), per parameter version
+
+    @property
+    def fc_layers(self):
+        return [getattr(self, "fc%d" % i) for i in range(1, self.num_fc + 1)]
+
+    def tensors(self):
+        """the head as ops.pointrend_refine takes it (detached parameters: they share the parameters' version counters)"""
+        pair = lambda m: (m.weight.detach(), m.bias.detach())
+        return {"fc": [pair(fc) for fc in self.fc_layers], "predictor": pair(self.predictor), "coarse_in_each_layer": self.coarse_pred_each_layer,
+                "images": self._images}
+
+
+class PointRend(nn.Module):
+    """models/PointRend.py:8-90 of the reference, the eval-mode forward: UPerNet's logits at 1/s resolution, then log2(s) times upsample x 2,
+    pick the pr_subdivision_num_pts most uncertain pixels, re-predict them from point features of the four encoder stages and the coarse
+    logits, write them back.  The train-mode forward (random points, point loss) is refused: POINTREND_TRAINING_REFUSAL."""
+
+    def __init__(self, config, experiment):
+        super().__init__()
+        self.num_classes = num_classes(experiment)
+        if self.num_classes < 2:
+            raise ValueError("PointRend's uncertainty is the difference of the two largest logits: it needs at least 2 classes (got %d)" % self.num_classes)
+        self.train_num_pts = config["pr_train_num_pts"]                                 # (train-only: read and kept, unused)
+        self.oversample_ratio = config.get("pr_oversample_ratio", 3)                    # (train-only)
+        self.importance_sample_ratio = config.get("pr_importance_sample_ratio", .75)    # (train-only)
+        self.subdivision_num_pts = config["pr_subdivision_num_pts"]
+        self.in_channels = config["input_channels"]
+        self.in_scales = config["input_scales"]
+        self.fpn_num_lvl = min(max(config.get("fpn_num_lvl", len(self.in_scales)), 1), len(self.in_scales))
+        config["interpolate_result_up"] = False     # the coarse prediction stays at 1/s resolution
+        self.partial_upernet = UPerNet(config, experiment)
+        self.point_head = StandardPointHead(config, self.num_classes)
+
+    def run(self, cx, conv_out):
+        coarse = self.partial_upernet.run(cx, conv_out)
+        steps = int(math.log2(self.in_scales[-self.fpn_num_lvl]))
+        return pointrend_refine(cx, coarse, conv_out, self.point_head.tensors(), self.subdivision_num_pts, steps)
+
+
+_DECODERS = {"UPerNet": UPerNet, "PointRend": PointRend}
+
+
 class EncDec(EngineNet):
     def __init__(self, config, experiment):
         super().__init__()
         self.config = config
         self.experiment = experiment
         self.enc_model = Encoder(config["encoder"]["model"], config["encoder"])
-        if config["decoder"]["model"] != "UPerNet":
-            raise NotImplementedError("only the UPerNet decoder is on the accelerated path")
+        if config["decoder"]["model"] not in _DECODERS:
+            raise NotImplementedError("only the UPerNet and PointRend decoders are on the accelerated path")
         config["decoder"]["input_channels"] = self.enc_model.out_channels()
         config["decoder"]["input_scales"] = [4, 8, 16, 32]
-        self.dec_model = UPerNet(config["decoder"], experiment)
+        self.dec_model = _DECODERS[config["decoder"]["model"]](config["decoder"], experiment)
         if "projector" in config:
             raise NotImplementedError("the contrastive projector is outside the accelerated path")
         self.projector_model = None
         self.get_features = True
         self.num_classes = self.dec_model.num_classes
         self.out_stride = 32
+
+    def forward(self, x):
+        if self.training and isinstance(self.dec_model, PointRend):
+            raise NotImplementedError(POINTREND_TRAINING_REFUSAL)
+        return super().forward(x)
 
     def _body(self, cx, x):
         feats = self.enc_model.run(cx, x)

@@ -2517,3 +2517,136 @@ def aug_color_op(img, op, factor):
     ws = workspace(8 * B + 256, img.device)
     check(lib.catseg_aug_color_op(ptr(img), B, H, W, ptr(op), ptr(factor), ptr(ws), ws.numel(), stream()))
     return img
+
+
+# ---------------------------------------------------------------------------------------------- PointRend refinement (csrc/pointrend.hip)
+def pointrend_upsample2x(seg):
+    """seg [B, h, w, K] class logits (any pixel stride >= K) -> (up [B, 2h, 2w, K] dense, uncertainty [B, 2h, 2w]): up IS the launch
+    bilinear_fwd(seg, 2h, 2w, False); uncertainty = second-largest - largest of the K logits it stored (utils/pointrend_utils.py:220-232
+    of the reference).  The pad columns of seg's rows never take part."""
+    B, H, W, K = seg.shape
+    if K < 2:
+        raise ValueError("PointRend's uncertainty is the difference of the two largest logits: it needs at least 2 classes (got %d)" % K)
+    up = bilinear_fwd(seg, 2 * H, 2 * W, False)
+    unc = torch.empty((B, 2 * H, 2 * W), dtype=torch.float32, device=seg.device)
+    with _Timed("hbm:pointrend_uncertainty", 4.0 * (up.numel() + unc.numel())):
+        check(lib.catseg_pointrend_uncertainty(ptr(up), ld_of(up), ptr(unc), unc.numel(), K, stream()))
+    return up, unc
+
+
+def pointrend_topk(unc, k):
+    """indices (int32 [N, k], ascending) of the k largest entries of every row of unc [N, ...]; among equal values the lower index is
+    selected (-0.0 == +0.0); k >= the row length selects everything.  No host synchronisation: capturable."""
+    assert unc.dtype == torch.float32 and unc.is_contiguous()
+    N = unc.shape[0]
+    n = unc.numel() // N
+    k = min(int(k), n)
+    idx = torch.empty((N, k), dtype=torch.int32, device=unc.device)
+    need = lib.catseg_pointrend_topk_workspace(N, n)
+    ws = workspace(need, unc.device)
+    check(lib.catseg_pointrend_topk(ptr(unc), N, n, k, ptr(idx), ptr(ws), ws.numel(), stream()))
+    return idx
+
+
+def pointrend_gather(sources, idx, h, w, out=None, extras=()):
+    """the point matrix [N k, sum of the sources' channels, each rounded up to 4]: for every selected cell idx[b, p] of the h x w grid
+    F.grid_sample(bilinear, align_corners=False, zero padding) of every source (NHWC [N, H_s, W_s, C_s]) at the cell's centre, the blocks
+    side by side in the order given (models/PointRend.py:81-83: deepest stage first, the coarse logits last).  extras: [(buffer [N k, ld],
+    first column)] -- further places the LAST source's block is written to."""
+    N, k = idx.shape
+    cols = sum((s.shape[-1] + 3) // 4 * 4 for s in sources)
+    if out is None:
+        out = torch.empty((N * k, cols), dtype=torch.float32, device=idx.device)
+    d = _lib.PointrendGatherDesc()
+    for i, s in enumerate(sources):
+        assert s.shape[0] == N and s.dtype == torch.float32
+        d.src[i], d.ld[i], d.H[i], d.W[i], d.C[i] = ptr(s), ld_of(s), s.shape[1], s.shape[2], s.shape[3]
+    d.n_sources, d.idx, d.N, d.k, d.h, d.w, d.out, d.ld_out = len(sources), ptr(idx), N, k, h, w, ptr(out), out.stride(0)
+    for i, (buf, c0) in enumerate(extras):
+        d.extra[i], d.extra_ld[i], d.extra_off[i] = ptr(buf), buf.stride(0), c0
+    d.n_extra = len(extras)
+    check(lib.catseg_pointrend_gather(ctypes.byref(d), stream()))
+    return out
+
+
+def pointrend_scatter(rows, idx, seg):
+    """seg[b, idx[b, p], :] = rows[b k + p, :K] in place (seg NHWC [N, h, w, K])"""
+    N, k = idx.shape
+    _, h, w, K = seg.shape
+    check(lib.catseg_pointrend_scatter(ptr(rows), rows.stride(0), ptr(idx), N, k, h * w, ptr(seg), ld_of(seg), K, stream()))
+    return seg
+
+
+def _pointrend_weight(w, main, K, cache=None, slot=None):
+    """device image of a point-head layer's weight [O, main + K (, 1)] for an input whose coarse block is K rounded up to 4 columns wide:
+    the columns of the pad are zero (the parameter keeps the reference's shape).  cache (a dict the head owns) keeps the image until the
+    parameter moves or is written in place (data_ptr, version), as the other layers' device images are kept."""
+    Kq = (K + 3) // 4 * 4
+    w2 = w.reshape(w.shape[0], -1)
+    if w2.shape[1] == main or Kq == K:
+        return w2.contiguous()
+    key = (w.data_ptr(), w._version, tuple(w.shape), str(w.device))
+    if cache is not None and slot in cache and cache[slot][0] == key and not torch.cuda.is_current_stream_capturing():
+        return cache[slot][1]
+    img = torch.zeros((w2.shape[0], main + Kq), dtype=torch.float32, device=w.device)
+    img[:, :main + K].copy_(w2)
+    if cache is not None and not torch.cuda.is_current_stream_capturing():     # (an image built inside a capture lives in the graph's pool)
+        cache[slot] = (key, img)
+    return img
+
+
+def pointrend_refine(seg, feats, head, k0, steps, record=None):
+    """The eval-mode loop of the reference's PointRend.forward (models/PointRend.py:74-90).  seg: coarse logits NHWC [N, h, w, K]; feats: the
+    encoder stages NHWC, shallow to deep; head: {"fc": [(weight [O, I(, 1)], bias)], "predictor": (weight, bias), "coarse_in_each_layer":
+    bool}; k0 = pr_subdivision_num_pts.  Per step: upsample x 2 + uncertainty, the min(h w, k0) most uncertain pixels, the point matrix
+    [c5 | c4 | c3 | c2 | coarse], the head's 1 x 1 layers over the N k points, the scatter.  Returns the refined logits [N, h 2^steps,
+    w 2^steps, K]; record (a list) receives per step {"idx": int32 [N, k] ascending, "uncertainty": [N, h, w]}.  No host synchronisation."""
+    N, _, _, K = seg.shape
+    if K < 2:
+        raise ValueError("PointRend's uncertainty is the difference of the two largest logits: it needs at least 2 classes (got %d)" % K)
+    Kq = (K + 3) // 4 * 4
+    each = bool(head.get("coarse_in_each_layer", True))
+    srcs = list(feats[::-1])
+    Cf = sum(f.shape[-1] for f in srcs)
+    if any(f.shape[-1] % 4 for f in srcs):
+        raise ValueError("PointRend: the encoder stages' channel counts must be multiples of 4 (got %s)" % [f.shape[-1] for f in feats])
+    fcs = head["fc"]
+    widths = [w.shape[0] for w, _ in fcs]
+    if any(o % 4 for o in widths):
+        raise ValueError("PointRend: ph_fc_dim must be a multiple of 4 (got %s)" % widths)
+    mains = [Cf] + widths                      # width of each layer's input in front of its coarse block
+    cache = head.get("images")
+    imgs = [_pointrend_weight(w, m, K if (i == 0 or each) else 0, cache, i) for i, ((w, _), m) in enumerate(zip(list(fcs) + [head["predictor"]], mains))]
+    dev = seg.device
+    for _ in range(steps):
+        up, unc = pointrend_upsample2x(seg)
+        _, h, w, _ = up.shape
+        idx = pointrend_topk(unc, k0)
+        k = idx.shape[1]
+        rows = N * k
+        x = torch.empty((rows, Cf + Kq), dtype=torch.float32, device=dev)
+        bufs, extras = [], []
+        for li, o in enumerate(widths):
+            if each:                            # (two buffers in turn: layer i + 1 reads what layer i wrote beside the coarse block)
+                if li < 2:
+                    bufs.append(torch.empty((rows, o + Kq), dtype=torch.float32, device=dev))
+                    extras.append((bufs[-1], o))
+                elif widths[li] == widths[li - 2]:
+                    bufs.append(bufs[li - 2])
+                else:
+                    bufs.append(torch.empty((rows, o + Kq), dtype=torch.float32, device=dev))
+                    extras.append((bufs[-1], o))
+            else:
+                bufs.append(torch.empty((rows, o), dtype=torch.float32, device=dev))
+        pointrend_gather(srcs + [up], idx, h, w, out=x, extras=extras)
+        cur = x
+        for li, ((_, b), o) in enumerate(zip(fcs, widths)):
+            y = bufs[li]
+            conv_fwd_fused(cur.view(1, 1, rows, cur.shape[1]), imgs[li], b, None, True, o, 1, 1, out=y.view(1, 1, rows, y.shape[1])[..., :o])
+            cur = y
+        p = conv_fwd(cur.view(1, 1, rows, cur.shape[1]), imgs[-1], head["predictor"][1], K, 1, 1, zero_to=Kq)
+        pointrend_scatter(torch.as_strided(p, (rows, K), (Kq, 1)), idx, up)      # (the predictor's rows are Kq floats apart)
+        if record is not None:
+            record.append({"idx": idx, "uncertainty": unc})
+        seg = up
+    return seg
