@@ -798,6 +798,50 @@ int catseg_pointrend_gather(const catseg_pointrend_gather_desc* d, catseg_stream
 int catseg_pointrend_scatter(const float* rows, int ld_rows, const int* idx, int N, int k, long long hw, float* seg, int ld_seg, int K,
                              catseg_stream_t stream);
 
+/* ---- PointRend, train-mode forward and backward (models/PointRend.py:43-73, utils/pointrend_utils.py:65-116 and
+ * managers/EncDec_Manager.py:158-177 of the reference; csrc/pointrend_train.hip, catseg_pointrend_gather_at in csrc/pointrend.hip).  Points are
+ * (x, y) pairs in [0, 1]^2, [N, P, 2] fp32.  No entry point synchronises with the host, allocates or touches host memory: all are capturable.
+ *   draw:        out [N, M, 2] uniforms in [0, 1).  state: 16 bytes of device memory {seed lo, seed hi, layer | rank << 16, draw counter},
+ *                16-byte aligned.  Float i takes word i & 3 of philox4x32_10(counter = (i >> 2, draw, 1, layer | rank << 16), key = (seed lo,
+ *                seed hi)) -- counter word 2 is 1 where catseg_dropout2d_mask has 0 -- u = (word >> 8) 2^-24; the launch advances the draw
+ *                counter by one.  fixed != NULL (a test knob): out = fixed, the state is neither read nor written.
+ *   point_uncertainty: uncertainty[b, m] = second-largest - largest over the K real columns of F.grid_sample(coarse, 2 coords - 1; bilinear,
+ *                align_corners = False, ZERO padding); coarse NHWC [N, H, W] pixels of ld floats.  K >= 2.  No [N, K, M] intermediate.
+ *   gather_at:   catseg_pointrend_gather with the point read from coords [N, k, 2] instead of derived from a cell index (idx, h, w of the
+ *                descriptor are not read); the same sweep, the same bits for the same point.
+ *   compose:     coords [N, P, 2] = cand[b, sel[b, 0 .. kb)] (sel: int32 indices into the M candidates of image b, as catseg_pointrend_topk
+ *                writes them), then rest [N, P - kb, 2]; pix [N, P] (int32) = round(y (h - 1)) w + round(x (w - 1)), every operation rounded
+ *                to fp32, round half to even (models/PointRend.py:56-57; h w < 2^24; a result outside [0, h w) is stored as -1);
+ *                labels [N, P] (int64) = F.grid_sample(lbl [N, Hl, Wl] int64, mode = 'nearest', zero padding): a tap outside the map gives 0,
+ *                every stored value (the ignore class too) passes through.  lbl and labels may both be NULL.
+ *   gather_bwd:  the adjoint of gather_at: dst_s[b, tap pixel, 0:C_s] (+)= weight * dx[b P + p, block s] over the four bilinear taps of every
+ *                point; a tap outside the map is dropped.  accumulate[s] == 0: the WHOLE destination [N, H_s, W_s] x ld_s floats is zeroed
+ *                first, so pixels no tap touches are 0; != 0: they keep their values.  No floating-point atomics: a pixel's sum is formed by
+ *                one wave over its taps in ascending tap number 4 p + corner (nw, ne, sw, se); two launches give the same bits.
+ *                Destinations: 16-byte aligned, ld_s % 4 == 0, ld_s >= C_s rounded up to 4 (the pad columns receive 0).  P <= 3584.
+ *   scatter_last: seg[b, pix[b, p], 0:K] = rows[b P + p, 0:K]; among the points of one pixel the HIGHEST p writes (torch's scatter_ on
+ *                the CPU); pix outside [0, hw) writes nothing.  P <= 14336.
+ *   scatter_bwd: drows[b P + p, 0:K] (+)= dseg[b, pix[b, p], 0:K] for EVERY p (each duplicate receives its pixel's gradient), then
+ *                dseg[b, pix[b, p], 0:K] = 0 (the tensor the points were scattered into receives no gradient there). */
+typedef struct {
+  float* dst[5]; int ld[5], H[5], W[5], C[5], accumulate[5];
+  int n_sources;                 /* 1 .. 5 */
+  const float* coords;           /* [N, P, 2] */
+  int N, P;
+  const float* dx; int ld_dx;    /* [N P] rows: the sources' blocks side by side, each C_s rounded up to 4 columns wide */
+} catseg_pointrend_gather_bwd_desc;
+int catseg_pointrend_draw(void* state, const float* fixed, int N, int M, float* out, catseg_stream_t stream);
+int catseg_pointrend_point_uncertainty(const float* coarse, int ld, int N, int H, int W, int K, const float* coords, int M, float* uncertainty,
+                                       catseg_stream_t stream);
+int catseg_pointrend_gather_at(const catseg_pointrend_gather_desc* d, const float* coords, catseg_stream_t stream);
+int catseg_pointrend_compose(const float* cand, int M, const int* sel, int kb, const float* rest, int N, int P, int h, int w, const long long* lbl,
+                             int Hl, int Wl, float* coords, int* pix, long long* labels, catseg_stream_t stream);
+int catseg_pointrend_gather_bwd(const catseg_pointrend_gather_bwd_desc* d, catseg_stream_t stream);
+int catseg_pointrend_scatter_last(const float* rows, int ld_rows, const int* pix, int N, int P, long long hw, float* seg, int ld_seg, int K,
+                                  catseg_stream_t stream);
+int catseg_pointrend_scatter_bwd(float* dseg, int ld_seg, const int* pix, int N, int P, long long hw, float* drows, int ld_rows, int K, int accumulate,
+                                 catseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,11 @@ class PointrendGatherDesc(C.Structure):
                 ("w", I), ("out", P), ("ld_out", I), ("extra", P * 4), ("extra_ld", I * 4), ("extra_off", I * 4), ("n_extra", I)]
 
 
+class PointrendGatherBwdDesc(C.Structure):
+    _fields_ = [("dst", P * 5), ("ld", I * 5), ("H", I * 5), ("W", I * 5), ("C", I * 5), ("accumulate", I * 5), ("n_sources", I), ("coords", P),
+                ("N", I), ("P", I), ("dx", P), ("ld_dx", I)]
+
+
 _SIGS = {
     "catseg_last_error": (C.c_char_p, []),
     "catseg_version": (I, []),
@@ -235,6 +240,13 @@ _SIGS = {
     "catseg_pointrend_topk": (I, [P, I, L, I, P, P, SZ, P]),
     "catseg_pointrend_gather": (I, [P, P]),
     "catseg_pointrend_scatter": (I, [P, I, P, I, I, L, P, I, I, P]),
+    "catseg_pointrend_draw": (I, [P, P, I, I, P, P]),
+    "catseg_pointrend_point_uncertainty": (I, [P, I, I, I, I, I, P, I, P, P]),
+    "catseg_pointrend_gather_at": (I, [P, P, P]),
+    "catseg_pointrend_compose": (I, [P, I, P, I, P, I, I, I, I, P, I, I, P, P, P, P]),
+    "catseg_pointrend_gather_bwd": (I, [P, P]),
+    "catseg_pointrend_scatter_last": (I, [P, I, P, I, I, L, P, I, I, P]),
+    "catseg_pointrend_scatter_bwd": (I, [P, I, P, I, I, L, P, I, I, I, P]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header / library mismatch

@@ -9,22 +9,11 @@
 // The draw: element i = n C + c takes word i & 3 of philox4x32_10(counter = (i >> 2, draw, 0, layer | rank << 16), key = (seed lo, seed hi)),
 // u = (word >> 8) 2^-24, kept iff u >= p.
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
-typedef unsigned dr_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ dr_u32x4 philox4x32_10(dr_u32x4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-    c = dr_u32x4{hi1 ^ c[1] ^ k0, lo1, hi0 ^ c[3] ^ k1, lo0};
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
-}
+typedef ph_u32x4 dr_u32x4;
 
 // ONE block.  A thread owns spans of 32 consecutive elements (= one word of `bits` where C % 32 == 0: n C + c is then linear in the words).
 // fixed == nullptr: a draw; every thread reads the state in front of the barrier, thread 0 stores the advanced counter behind it.
@@ -49,7 +38,7 @@ __global__ __launch_bounds__(kMaskThreads) void dropout2d_mask_kernel(unsigned* 
       const int i0 = 32 * w + 4 * q;
       if (i0 >= total) break;
       dr_u32x4 r = {0u, 0u, 0u, 0u};
-      if (fixed == nullptr) r = philox4x32_10(dr_u32x4{(unsigned)(i0 >> 2), draw, 0u, s2}, s0, s1);
+      if (fixed == nullptr) r = philox4x32_10(dr_u32x4{(unsigned)(i0 >> 2), draw, PHILOX_STREAM_DROPOUT, s2}, s0, s1);
       f32x4 m;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {

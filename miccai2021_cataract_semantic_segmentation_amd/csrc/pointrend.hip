@@ -16,6 +16,7 @@
 //   catseg_pointrend_scatter     seg[b, idx[b, p], 0:K] = rows[b, p, 0:K]
 // One wave sweeps a point's channels with 16-byte loads (NHWC: a pixel's channels are contiguous).
 #include "lerp.h"
+#include "pointrend_taps.h"
 
 namespace {
 
@@ -23,8 +24,6 @@ constexpr int TK_THREADS = 256;
 constexpr int TK_ITEMS = 8;                           // candidates per thread and block
 constexpr int TK_CHUNK = TK_THREADS * TK_ITEMS;       // candidates per block
 constexpr int TK_PASSES = 4;                          // 8 bits of the value per pass
-constexpr int PR_MAXSRC = 5;
-constexpr int PR_MAXDST = 4;
 
 // ---------------------------------------------------------------------------------------------------------------- uncertainty
 // A block takes 256 consecutive pixels: their rows are one contiguous span of 256 ldy floats, read with consecutive lanes on consecutive
@@ -236,16 +235,7 @@ __global__ __launch_bounds__(TK_THREADS) void pr_topk_emit_kernel(const float* _
 }
 
 // ---------------------------------------------------------------------------------------------------------------- point gather
-struct PrGather {                 // by value in the kernel arguments: nothing to upload, capturable
-  const float* src[PR_MAXSRC];
-  int ld[PR_MAXSRC], H[PR_MAXSRC], W[PR_MAXSRC], C[PR_MAXSRC], off[PR_MAXSRC];     // off: first column of the source's block in the point row
-  int vec[PR_MAXSRC];             // the source's pixels are 16-byte aligned and hold C rounded up to 4 readable floats: 16-byte loads
-  int nsrc;
-  float* extra[PR_MAXDST];        // further destinations of the LAST source's block (the coarse logits)
-  int extra_ld[PR_MAXDST], extra_off[PR_MAXDST];
-  int nextra;
-};
-
+// (PrGather, the taps and the sweep of a point's channels: pointrend_taps.h, shared with the train-mode kernels)
 __global__ __launch_bounds__(256) void pr_gather_kernel(PrGather g, const int* __restrict__ idx, int k, long long npts, int h, int w, float hstep,
                                                         float hhalf, float wstep, float whalf, float* __restrict__ out, int ldo) {
   const int lane = threadIdx.x & 63;
@@ -256,53 +246,16 @@ __global__ __launch_bounds__(256) void pr_gather_kernel(PrGather g, const int* _
   const int row = pix / w, col = pix - row * w;
   // utils/pointrend_utils.py:146-147: step / 2 + index * step, every operation rounded to fp32; then point_sample's 2 p - 1
   const float px = __fadd_rn(whalf, __fmul_rn((float)col, wstep)), py = __fadd_rn(hhalf, __fmul_rn((float)row, hstep));
-  const float gx = __fsub_rn(__fmul_rn(2.f, px), 1.f), gy = __fsub_rn(__fmul_rn(2.f, py), 1.f);
-  float* orow = out + p * ldo;
-  for (int s = 0; s < g.nsrc; ++s) {
-    const int Hs = g.H[s], Ws = g.W[s], C = g.C[s], ld = g.ld[s];
-    // grid_sample, align_corners = False: ((g + 1) * size - 1) / 2 = (g + 1) * (size / 2) - 0.5
-    const float ix = __fsub_rn(__fmul_rn(__fadd_rn(gx, 1.f), 0.5f * (float)Ws), 0.5f);
-    const float iy = __fsub_rn(__fmul_rn(__fadd_rn(gy, 1.f), 0.5f * (float)Hs), 0.5f);
-    const float fx = floorf(ix), fy = floorf(iy);
-    const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-    const float tx1 = ix - fx, ty1 = iy - fy, tx0 = (fx + 1.f) - ix, ty0 = (fy + 1.f) - iy;
-    const float wnw = tx0 * ty0, wne = tx1 * ty0, wsw = tx0 * ty1, wse = tx1 * ty1;
-    const bool vx0 = x0 >= 0 && x0 < Ws, vx1 = x1 >= 0 && x1 < Ws, vy0 = y0 >= 0 && y0 < Hs, vy1 = y1 >= 0 && y1 < Hs;
-    const float* base = g.src[s] + (long long)b * Hs * Ws * ld;
-    const float* pnw = base + ((long long)y0 * Ws + x0) * ld;
-    const float* pne = pnw + ld;
-    const float* psw = pnw + (long long)Ws * ld;
-    const float* pse = psw + ld;
-    const bool last = s == g.nsrc - 1;
-    const int Cq = (C + 3) & ~3;
-    if (!g.vec[s]) {                                  // dense K-class logits (ld = K, K % 4 != 0): one channel per lane
-      for (int c = lane; c < Cq; c += 64) {
-        float v = 0.f;                                // pad columns of the block: zero
-        if (c < C) {
-          const float a = (vy0 && vx0) ? pnw[c] : 0.f, bq = (vy0 && vx1) ? pne[c] : 0.f;      // zero padding: a tap outside the map is 0
-          const float cq = (vy1 && vx0) ? psw[c] : 0.f, dq = (vy1 && vx1) ? pse[c] : 0.f;
-          v = a * wnw + bq * wne + cq * wsw + dq * wse;
-        }
-        orow[g.off[s] + c] = v;
-        if (last)
-          for (int q = 0; q < g.nextra; ++q) g.extra[q][p * g.extra_ld[q] + g.extra_off[q] + c] = v;
-      }
-      continue;
-    }
-    for (int c = lane * 4; c < Cq; c += 256) {
-      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-      const f32x4 a = (vy0 && vx0) ? *(const f32x4*)(pnw + c) : z;       // zero padding: a tap outside the map is 0
-      const f32x4 bq = (vy0 && vx1) ? *(const f32x4*)(pne + c) : z;
-      const f32x4 cq = (vy1 && vx0) ? *(const f32x4*)(psw + c) : z;
-      const f32x4 dq = (vy1 && vx1) ? *(const f32x4*)(pse + c) : z;
-      f32x4 v;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (c + e < C) ? (a[e] * wnw + bq[e] * wne + cq[e] * wsw + dq[e] * wse) : 0.f;      // pad columns of the block: zero
-      *(f32x4*)(orow + g.off[s] + c) = v;
-      if (last)
-        for (int q = 0; q < g.nextra; ++q) *(f32x4*)(g.extra[q] + p * g.extra_ld[q] + g.extra_off[q] + c) = v;
-    }
-  }
+  pr_gather_point(g, b, p, pr_grid(px), pr_grid(py), out, ldo, lane);
+}
+
+// the train-mode form: the point's (x, y) in [0, 1]^2 is read, not derived from a cell index
+__global__ __launch_bounds__(256) void pr_gather_at_kernel(PrGather g, const float* __restrict__ coords, int k, long long npts, float* __restrict__ out,
+                                                           int ldo) {
+  const int lane = threadIdx.x & 63;
+  const long long p = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);       // one wave per point
+  if (p >= npts) return;
+  pr_gather_point(g, (int)(p / k), p, pr_grid(coords[2 * p]), pr_grid(coords[2 * p + 1]), out, ldo, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- scatter
@@ -370,14 +323,12 @@ extern "C" int catseg_pointrend_topk(const float* uncertainty, int N, long long 
   return CATSEG_OK;
 }
 
-extern "C" int catseg_pointrend_gather(const catseg_pointrend_gather_desc* d, catseg_stream_t stream) {
-  CS_REQUIRE(d, "pointrend gather: null descriptor");
+namespace {
+// validates everything but the points of a gather descriptor and fills the kernel's argument
+int gather_args(const catseg_pointrend_gather_desc* d, PrGather& g) {
   CS_REQUIRE(d->n_sources >= 1 && d->n_sources <= PR_MAXSRC, "pointrend gather: 1 to %d sources (got %d)", PR_MAXSRC, d->n_sources);
   CS_REQUIRE(d->n_extra >= 0 && d->n_extra <= PR_MAXDST, "pointrend gather: at most %d further destinations of the last block (got %d)", PR_MAXDST, d->n_extra);
-  CS_REQUIRE(d->N > 0 && d->k > 0 && d->h > 0 && d->w > 0 && (long long)d->h * d->w < (1ll << 31) && d->k <= (long long)d->h * d->w,
-             "pointrend gather: bad point grid (N %d, k %d, grid %d x %d)", d->N, d->k, d->h, d->w);
-  CS_REQUIRE(d->idx && d->out && cs_aligned16(d->out) && d->ld_out % 4 == 0, "pointrend gather: idx and a 16-byte aligned point matrix with ld %% 4 == 0 are required");
-  PrGather g = {};
+  CS_REQUIRE(d->out && cs_aligned16(d->out) && d->ld_out % 4 == 0, "pointrend gather: a 16-byte aligned point matrix with ld %% 4 == 0 is required");
   int col = 0;
   for (int s = 0; s < d->n_sources; ++s) {
     const int Cq = (d->C[s] + 3) & ~3;
@@ -398,11 +349,34 @@ extern "C" int catseg_pointrend_gather(const catseg_pointrend_gather_desc* d, ca
   }
   g.nsrc = d->n_sources;
   g.nextra = d->n_extra;
+  return CATSEG_OK;
+}
+}  // namespace
+
+extern "C" int catseg_pointrend_gather(const catseg_pointrend_gather_desc* d, catseg_stream_t stream) {
+  CS_REQUIRE(d, "pointrend gather: null descriptor");
+  CS_REQUIRE(d->n_sources >= 1 && d->n_sources <= PR_MAXSRC, "pointrend gather: 1 to %d sources (got %d)", PR_MAXSRC, d->n_sources);
+  CS_REQUIRE(d->N > 0 && d->k > 0 && d->h > 0 && d->w > 0 && (long long)d->h * d->w < (1ll << 31) && d->k <= (long long)d->h * d->w,
+             "pointrend gather: bad point grid (N %d, k %d, grid %d x %d)", d->N, d->k, d->h, d->w);
+  CS_REQUIRE(d->idx, "pointrend gather: idx is required");
+  PrGather g = {};
+  if (const int rc = gather_args(d, g)) return rc;
   const long long npts = (long long)d->N * d->k;
   // 1 / float(h) is a Python float (double) in the reference; multiplied into / added to an fp32 tensor it is rounded to fp32 first
   const double hs = 1.0 / (double)d->h, wsd = 1.0 / (double)d->w;
   hipLaunchKernelGGL(pr_gather_kernel, dim3((unsigned)((npts + 3) / 4)), dim3(256), 0, (hipStream_t)stream, g, d->idx, d->k, npts, d->h, d->w, (float)hs,
                      (float)(hs / 2.0), (float)wsd, (float)(wsd / 2.0), d->out, d->ld_out);
+  CS_LAUNCH_CHECK();
+  return CATSEG_OK;
+}
+
+extern "C" int catseg_pointrend_gather_at(const catseg_pointrend_gather_desc* d, const float* coords, catseg_stream_t stream) {
+  CS_REQUIRE(d && coords, "pointrend gather at coordinates: the descriptor and the coordinates [N, k, 2] are required");
+  CS_REQUIRE(d->N > 0 && d->k > 0 && (long long)d->N * d->k < (1ll << 31), "pointrend gather at coordinates: N, k > 0 (N %d, k %d)", d->N, d->k);
+  PrGather g = {};
+  if (const int rc = gather_args(d, g)) return rc;
+  const long long npts = (long long)d->N * d->k;
+  hipLaunchKernelGGL(pr_gather_at_kernel, dim3((unsigned)((npts + 3) / 4)), dim3(256), 0, (hipStream_t)stream, g, coords, d->k, npts, d->out, d->ld_out);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
 }

@@ -212,10 +212,12 @@ def attach(model, bucket_bytes=None, force=None):
 
 
 def seed_dropout_by_rank(model, rank):
-    """every rank's Dropout2d layers draw with the rank in their Philox counter: independent masks on the shards of one batch (the seed itself
-    stays the shared one).  A layer that is already seeded is reseeded with its seed, its draw counter back to 0."""
+    """every module of the model that draws on the device (engine.rng_modules: the Dropout2d layers, PointRend's PointSampler) gets the rank
+    into its Philox counter: independent masks and independent training points on the shards of one batch (the seed itself stays the shared
+    one).  A module that is already seeded is reseeded with its seed, its draw counter back to 0.  (The name is the one dist.attach and the
+    tests have called since the Dropout2d layers were the only such modules.)"""
     from . import engine
-    for m in engine.dropout_layers(model):
+    for m in engine.rng_modules(model):
         m.rank = int(rank)
         if m._seeded:
             lo, hi = (int(v) & 0xFFFFFFFF for v in m.state[:2].tolist())
@@ -227,7 +229,7 @@ def broadcast_parameters(model, src=0):
     if not dist.is_initialized() or dist.get_world_size() == 1:
         return
     from . import engine
-    own = {id(m.state) for m in engine.dropout_layers(model)}
+    own = {id(m.state) for m in engine.rng_modules(model)}
     fp = model.flat()
     dist.broadcast(fp.flat, src)
     for b in model.buffers():

@@ -35,25 +35,17 @@ class BatchNorm2d(nn.BatchNorm2d):
         raise RuntimeError("engine BatchNorm2d is executed by the owning network, not called directly")
 
 
-class Dropout2d(nn.Dropout2d):
-    """nn.Dropout2d of a head (models/OCR.py:87, 311-316 of the reference), executed by conv_bn_act(drop=): no parameters, and its 16 bytes of
-    device state {seed lo, seed hi, layer | rank << 16, draw counter} are a NON-persistent buffer, so the state-dict keys stay the
-    reference's.  The mask is drawn on the device from that state and the same launch advances the counter (ops.dropout2d_mask): eager steps
-    and hipGraph replays run the same launches and draw the same masks.
-    The seed is torch.initial_seed() at the first training forward (the managers seed after construction) unless reseed() was called;
-    layer tells the dropout layers of one network apart, rank the data-parallel replicas (dist.attach).
-    fixed_mask: a test knob -- a [B, C] tensor of zeros and ones used instead of a draw (the state does not move)."""
+class _DeviceRng:
+    """What the modules that draw on the device share: 16 bytes of device state {seed lo, seed hi, layer | rank << 16, draw counter} as a
+    NON-persistent buffer (the state-dict keys stay the reference's).  A draw reads the state on the device and the same launch advances the
+    counter: eager steps and hipGraph replays run the same launches and draw the same numbers.  The seed is torch.initial_seed() at the
+    first training forward (the managers seed after construction) unless reseed() was called; layer tells the drawing modules of one
+    network apart, rank the data-parallel replicas (dist.attach)."""
 
-    def __init__(self, p=0.0, layer=0):
-        super().__init__(p)
+    def _init_rng(self, layer):
         self.layer, self.rank = int(layer), 0
         self.register_buffer("state", torch.zeros(4, dtype=torch.int32), persistent=False)
         self._seeded = False
-        self.fixed_mask = None
-        self.last = None            # the ops.DropMask of the last training forward
-
-    def forward(self, x):  # pragma: no cover
-        raise RuntimeError("engine Dropout2d is executed by the owning network, not called directly")
 
     def reseed(self, seed, rank=None):
         """(seed, rank) -> state, the draw counter back to 0"""
@@ -70,6 +62,25 @@ class Dropout2d(nn.Dropout2d):
         if not self._seeded:
             self.reseed(torch.initial_seed())
 
+
+class Dropout2d(nn.Dropout2d, _DeviceRng):
+    """nn.Dropout2d of a head (models/OCR.py:87, 311-316 of the reference), executed by conv_bn_act(drop=): no parameters; its draws come
+    from the device state of _DeviceRng (ops.dropout2d_mask).
+    fixed_mask: a test knob -- a [B, C] tensor of zeros and ones used instead of a draw (the state does not move)."""
+
+    def __init__(self, p=0.0, layer=0):
+        super().__init__(p)
+        self._init_rng(layer)
+        self.fixed_mask = None
+        self.last = None            # the ops.DropMask of the last training forward
+
+    def forward(self, x):  # pragma: no cover
+        raise RuntimeError("engine Dropout2d is executed by the owning network, not called directly")
+
+    def draws(self):
+        """a training forward of this module reads its device state"""
+        return self.p > 0.0 and self.fixed_mask is None
+
     def active(self, cx):
         return self.p > 0.0 and cx.train
 
@@ -83,6 +94,28 @@ class Dropout2d(nn.Dropout2d):
             self.ensure_seeded()
             self.last = ops.dropout2d_mask(self.state, self.p, B, C)
         return self.last
+
+
+class PointSampler(nn.Module, _DeviceRng):
+    """The random points of PointRend's training forward (utils/pointrend_utils.py:65-116 of the reference, whose torch.rand calls are the
+    device generator's draws here: ops.pointrend_draw, counter word 2 = 1 where the Dropout2d masks have 0).  No parameters.
+    fixed_points: a test knob -- a [N, P, 2] tensor of (x, y) in [0, 1]^2 used instead of the whole sampling (the state does not move)."""
+
+    def __init__(self, layer=0):
+        super().__init__()
+        self._init_rng(layer)
+        self.fixed_points = None
+
+    def forward(self, x):  # pragma: no cover
+        raise RuntimeError("engine PointSampler is executed by the owning network, not called directly")
+
+    def draws(self):
+        return self.fixed_points is None
+
+
+def rng_modules(module):
+    """the modules of a network that own a device generator state"""
+    return [m for m in module.modules() if isinstance(m, _DeviceRng)]
 
 
 def dropout_layers(module):
@@ -193,6 +226,7 @@ class Ctx:
         self.tape = []
         self.grads = {}
         self.shared = set()
+        self.nondiff = set()           # id(output) of the outputs that carry no gradient (PointRend's point coordinates)
         self.on_param_grad = on_param_grad
         self.on_quiet = None           # backward: called on the launch stream between two tape entries outside every parallel region
         self.claimed = set()
@@ -1030,6 +1064,112 @@ def pointrend_refine(cx, seg, feats, head, k0, steps):
     return ops.pointrend_refine(seg, feats, head, k0, steps)
 
 
+def pointrend_sample_points(coarse, sampler, P, ratio, beta, h, w):
+    """utils/pointrend_utils.py:86-116 and models/PointRend.py:54-57 of the reference on the device: M = int(P ratio) uniform candidates,
+    the uncertainty of the coarse logits sampled there, the int(beta P) most uncertain of them, P - int(beta P) fresh uniform points; per
+    point its pixel of the h x w map.  -> (coords [N, P, 2], pix int32 [N, P]).  Nothing differentiates through this."""
+    if not (ratio >= 1 and 0 <= beta <= 1):
+        raise ValueError("PointRend: pr_oversample_ratio >= 1 and 0 <= pr_importance_sample_ratio <= 1 (got %s, %s)" % (ratio, beta))
+    N = coarse.shape[0]
+    if sampler.fixed_points is not None:
+        pts = sampler.fixed_points.to(device=coarse.device, dtype=torch.float32).contiguous()
+        if tuple(pts.shape) != (N, P, 2):
+            raise ValueError("PointSampler.fixed_points must be [%d, %d, 2], got %s" % (N, P, tuple(pts.shape)))
+        coords, pix, _ = ops.pointrend_compose(None, None, ops.pointrend_draw(None, N, P, fixed=pts), h, w)
+        return coords, pix
+    sampler.ensure_seeded()
+    M, kb = int(P * ratio), int(beta * P)
+    cand = sel = rest = None
+    if kb > 0:
+        cand = ops.pointrend_draw(sampler.state, N, M)
+        sel = ops.pointrend_topk(ops.pointrend_point_uncertainty(coarse, cand), kb)
+    if P - kb > 0:
+        rest = ops.pointrend_draw(sampler.state, N, P - kb)
+    coords, pix, _ = ops.pointrend_compose(cand, sel, rest, h, w)
+    return coords, pix
+
+
+def pointrend_train(cx, coarse, feats, head, sampler, P, ratio, beta, scale):
+    """models/PointRend.py:43-73 of the reference, the train-mode forward.  coarse: UPerNet's logits NHWC [N, h, w, K] (padded rows); feats:
+    the encoder stages NHWC, shallow to deep; head: the StandardPointHead module; sampler: an engine.PointSampler.
+    -> (coords [N, P, 1, 2], point_logits [N, P, 1, K] (a view of rows K rounded up to 4 floats wide), pred [N, s h, s w, K]): pred IS the
+    interpolated coarse logits with the point logits scattered in place (seg_logits and pred of the reference are one memory; among points
+    on one pixel the last writes).
+    Backward (one tape entry): the scatter (every point, duplicates too, receives its pixel's gradient; the interpolation receives zero
+    there), the interpolation, the predictor and the fc layers with their ReLUs as GEMMs over the N P point rows (weight gradients straight
+    into p.grad [O, I, 1]: the zero pad columns of the weight images never leave this function; the coarse block's gradient summed over
+    every layer that concatenates it), and the deterministic adjoint of the point gather into the four stages and the coarse logits."""
+    N, hc, wc, K = coarse.shape
+    if K < 2:
+        raise ValueError("PointRend's uncertainty is the difference of the two largest logits: it needs at least 2 classes (got %d)" % K)
+    Kq = (K + 3) // 4 * 4
+    srcs = list(feats[::-1])
+    if any(f.shape[-1] % 4 for f in srcs):
+        raise ValueError("PointRend: the encoder stages' channel counts must be multiples of 4 (got %s)" % [f.shape[-1] for f in feats])
+    Cf = sum(f.shape[-1] for f in srcs)
+    layers = list(head.fc_layers) + [head.predictor]
+    widths = [m.out_channels for m in head.fc_layers]
+    if any(o % 4 for o in widths):
+        raise ValueError("PointRend: ph_fc_dim must be a multiple of 4 (got %s)" % widths)
+    each = bool(head.coarse_pred_each_layer)
+    for m in layers:
+        cx.claim(m.weight, m.bias)
+    h, w = hc * scale, wc * scale
+    dev = coarse.device
+    with torch.no_grad():
+        coords, pix = pointrend_sample_points(coarse, sampler, P, ratio, beta, h, w)
+    rows = N * P
+    # the inputs of the layers: [c5 | c4 | c3 | c2 | coarse] for fc1, [relu(fc_i) | coarse] (or relu(fc_i) alone) behind it
+    mains = [Cf] + widths                                  # width of each layer's input in front of its coarse block
+    blocks = [Kq] + [Kq if each else 0] * len(widths)      # ... and of the coarse block
+    xs = [torch.empty((rows, m + b), dtype=torch.float32, device=dev) for m, b in zip(mains, blocks)]
+    ops.pointrend_gather_at(srcs + [coarse], coords, out=xs[0], extras=[(x, m) for x, m, b in zip(xs[1:], mains[1:], blocks[1:]) if b])
+    # (weight images with the coarse block's columns padded to Kq, rebuilt every step: the optimiser writes the parameters in place)
+    imgs = [ops._pointrend_weight(m.weight.data, mn, K if b else 0) for m, mn, b in zip(layers, mains, blocks)]
+    for li, o in enumerate(widths):
+        ops.conv_fwd_fused(xs[li].view(1, 1, rows, -1), imgs[li], layers[li].bias.data, None, True, o, 1, 1, out=xs[li + 1].view(1, 1, rows, -1)[..., :o])
+    pl = ops.conv_fwd(xs[-1].view(1, 1, rows, -1), imgs[-1], head.predictor.bias.data, K, 1, 1, zero_to=Kq)      # (rows Kq floats apart)
+    prow = torch.as_strided(pl, (rows, K), (Kq, 1))
+    pl = torch.as_strided(pl, (N, P, 1, K), (P * Kq, Kq, Kq, 1))
+    pred = ops.bilinear_fwd(coarse, h, w, False)
+    ops.pointrend_scatter_last(prow, pix, pred)
+    coords4 = coords.view(N, P, 1, 2)
+    cx.nondiff.add(id(coords4))
+    if cx.record:
+        def bwd():
+            dpl, dpred = cx.take(pl), cx.take(pred)
+            cx.take(coords4)
+            if dpl is None and dpred is None:
+                return
+            dp = torch.zeros((rows, Kq), dtype=torch.float32, device=dev)      # (the pad columns stay zero: they meet the images' zero columns)
+            if dpl is not None:
+                dp[:, :K].copy_(dpl.reshape(rows, K))
+            if dpred is not None:
+                ops.pointrend_scatter_bwd(dpred, pix, dp, True)                # dpred is zero at the scattered pixels from here on
+                dc, acc = cx.dest(coarse)
+                ops.bilinear_bwd(dpred, tuple(coarse.shape), False, out=dc, zero_to=(ops.ld_of(dc) if ops.ld_of(dc) != K else 0), accumulate=acc)
+            dy, dx0, coarse_terms = dp, None, []
+            for li in range(len(layers) - 1, -1, -1):
+                m, x, mn, b = layers[li], xs[li], mains[li], blocks[li]
+                O, real = m.out_channels, mn + (K if b else 0)                 # the parameter's input width: no pad column
+                ops.gemm(ops.TN, 1, O, real, rows, dy, dy.stride(0), 0, x, x.stride(0), 0, cx.pgrad(m.weight).view(O, real), real, 0)
+                ops.bias_grad(dy, O, cx.pgrad(m.bias))
+                dx = torch.empty_like(x)
+                ops.gemm(ops.NN, 1, rows, mn + b, O, dy, dy.stride(0), 0, imgs[li], imgs[li].stride(0), 0, dx, dx.stride(0), 0)
+                cx.done(m.weight, m.bias)
+                if li == 0:
+                    dx0 = dx
+                else:
+                    if b:
+                        coarse_terms.append(dx[:, mn:])
+                    dy = ops.relu_bwd(dx[:, :mn], x[:, :mn])
+            for t in coarse_terms:
+                ops.axpy(t, dx0[:, Cf:], 1.0, True)
+            ops.pointrend_gather_bwd(dx0, coords, [cx.dest(t) for t in srcs + [coarse]])
+        cx.push(bwd)
+    return coords4, pl, pred
+
+
 def spatial_gather(cx, feats, logits, K):
     """models/OCR.py:158-170: proxy[b, k, :] = sum_n softmax_n(logits[b, n, k]) * feats[b, n, :]"""
     B, H, W, C = feats.shape
@@ -1103,7 +1243,7 @@ class NetFunction(torch.autograd.Function):
         if net._keep_pass:
             net._last_pass = (cx, outs)
         res = tuple(o.permute(0, 3, 1, 2) for o in outs)
-        ctx.mark_non_differentiable()
+        ctx.mark_non_differentiable(*[r for o, r in zip(outs, res) if id(o) in cx.nondiff])
         return res if len(res) > 1 else res[0]
 
     @staticmethod
@@ -1264,7 +1404,7 @@ class EngineNet(nn.Module):
     def _tape_backward(self, cx, outs_nhwc, gouts):
         """the backward pass of a recorded forward: hands the output gradients (NCHW, as autograd carries them) to the tape and pops it"""
         for o, g in zip(outs_nhwc, gouts):
-            if g is None:
+            if g is None or id(o) in cx.nondiff:
                 continue
             gn = g.permute(0, 2, 3, 1)
             if not gn.is_contiguous():

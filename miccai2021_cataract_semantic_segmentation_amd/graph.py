@@ -114,11 +114,11 @@ class GraphedTrainStep:
         optimiser.device_hyper()
         fp = model.flat()
         m, v = optimiser._moments(fp)
-        # Dropout2d: seeded here (the seeding is a host-to-device copy, which a capture cannot hold).  The warm-up steps draw masks: with
+        # Dropout2d, PointSampler: seeded here (the seeding is a host-to-device copy, which a capture cannot hold).  The warm-up steps draw masks: with
         # keep_state the 16-byte states -- non-persistent buffers of the model -- go back with the other buffers below, so that warm-up and
         # capture consume no draw (a capture launches nothing) and the first replay draws what the first eager step would have drawn
-        for mod in engine.dropout_layers(model):
-            if mod.p > 0.0 and mod.fixed_mask is None:
+        for mod in engine.rng_modules(model):
+            if mod.draws():
                 mod.ensure_seeded()
         saved = None
         if keep_state:

@@ -37,10 +37,11 @@ class LossWrapper(nn.Module):
         self.dc_off = "dc_off_at_epoch" in self.config
 
     def forward(self, deep_features, prediction, labels, loss_list=None, interm_prediction=None, epoch=None):
-        self.total_loss = torch.tensor(0.0, dtype=torch.float, device=self.device)
+        # (torch.zeros is a fill on the device; torch.tensor(0.0, device=...) would be a host-to-device copy, which a hipGraph capture refuses)
+        self.total_loss = torch.zeros((), dtype=torch.float, device=self.device)
         loss_list = list(self.loss_weightings.keys()) if loss_list is None else loss_list
         for name in self.loss_weightings:
-            zero = torch.tensor(0.0, dtype=torch.float, device=self.device)
+            zero = torch.zeros((), dtype=torch.float, device=self.device)
             if name not in loss_list:
                 loss = zero
             elif name == "LovaszSoftmax":

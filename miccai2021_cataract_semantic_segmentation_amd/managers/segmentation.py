@@ -55,9 +55,11 @@ class EncDecManager(BaseManager):
     ``deep_features, prediction = model(img); loss = LossWrapper(deep_features, prediction, lbl, epoch=epoch)`` (:158-185)."""
 
     def __init__(self, configuration, *args, **kwargs):
-        if configuration.get("mode") == "training" and configuration.get("decoder", {}).get("model") == "PointRend":
+        dec = configuration.get("decoder", {})
+        if configuration.get("mode") == "training" and dec.get("model") == "PointRend" and not dec.get("pr_train_on_device", False):
             from ..models.EncDec import POINTREND_TRAINING_REFUSAL
             raise NotImplementedError(POINTREND_TRAINING_REFUSAL)        # (before anything is built: validate / infer / demo_infer run)
+        self.loss_coarse = self.loss_points = None      # PointRend training: the two terms of the last step (device scalars), for logging
         super().__init__(configuration, *args, **kwargs)
 
     def load_model(self):
@@ -71,12 +73,26 @@ class EncDecManager(BaseManager):
             self.grad_scale = 1.0
 
     def load_loss(self):
+        from ..losses import CrossEntropyLoss
+        from ..utils import ce_ignore_index
         self.config["loss"]["experiment"] = self.experiment
         self.config["loss"]["device"] = str(self.device)
         self.loss = LossWrapper(self.config["loss"])
+        self.point_loss = CrossEntropyLoss(ignore_index=ce_ignore_index(self.experiment))      # (:165-169: the ignore class in experiments 2 / 3)
 
     def forward_loss(self, img, lbl):
-        deep_features, prediction = self.model(img.float())
+        out = self.model(img.float())
+        if len(out) == 5:
+            # PointRend in train mode (:160-171 of the reference's manager): seg_logits IS pred, the interpolated coarse logits that already
+            # hold the point predictions; the labels of the points are the nearest pixels' (a point outside the map: class 0)
+            from .. import ops
+            deep_features, point_coords, point_logits, seg_logits, prediction = out
+            lbl = lbl.long()
+            self.loss_coarse = self.loss(deep_features, seg_logits, lbl, epoch=self.epoch)
+            point_labels = ops.pointrend_point_labels(point_coords, lbl)
+            self.loss_points = self.point_loss(point_logits.unsqueeze(3), point_labels.unsqueeze(2))
+            return self.loss_coarse + self.loss_points, prediction
+        deep_features, prediction = out
         return self.loss(deep_features, prediction, lbl.long(), epoch=self.epoch), prediction
 
     def final_output(self, out):

@@ -1,15 +1,15 @@
 """Encoder-decoder segmentation nets on the HIP engine: the reference's EncDec (models/EncDec.py:7-53) with
 the ResNet / ResNeXt encoder wrappers (models/ResNet.py:5-94, models/ResNeXt.py:5-60: torchvision trunks
-returning the four stage outputs), the UPerNet decoder (models/UPerNet.py:7-145) and, for evaluation and inference, the PointRend
-decoder (models/PointRend.py:8-141).  State-dict keys as in the reference: ``enc_model.layer1.0.conv1.weight``,
+returning the four stage outputs), the UPerNet decoder (models/UPerNet.py:7-145) and the PointRend decoder (models/PointRend.py:8-141;
+its train-mode forward behind config['decoder']['pr_train_on_device']).  State-dict keys as in the reference: ``enc_model.layer1.0.conv1.weight``,
 ``dec_model.ppm_conv.0.0.weight``, ``dec_model.partial_upernet.ppm_conv.0.0.weight``, ``dec_model.point_head.fc1.weight`` ..."""
 import math
 
 import torch
 from torch import nn
 
-from ..engine import (BatchNorm2d, Conv2d, EngineNet, adaptive_avgpool, add_n, bilinear, concat_views, conv_bias,
-                      conv_bn_act, copy_into, maxpool, pointrend_refine)
+from ..engine import (BatchNorm2d, Conv2d, EngineNet, PointSampler, adaptive_avgpool, add_n, bilinear, concat_views, conv_bias,
+                      conv_bn_act, copy_into, maxpool, pointrend_refine, pointrend_train)
 from ..utils import num_classes
 from .backbone import BasicBlock, Bottleneck, _c1, load_pretrained_trunk
 
@@ -161,9 +161,12 @@ class UPerNet(nn.Module):
         return x
 
 
-POINTREND_TRAINING_REFUSAL = ("PointRend's train-mode forward is not on the accelerated path: the random point sampling "
-                              "(get_uncertain_point_coords_with_randomness), the point cross-entropy loss and the backward of the point gather "
-                              "are missing; the eval-mode forward (model.eval(): validation, inference, Ensemble member, TTA, demo_infer) is there")
+POINTREND_TRAINING_REFUSAL = ("PointRend's train-mode forward runs on the accelerated path only where the configuration asks for it with "
+                              "config['decoder']['pr_train_on_device'] = True: the random point sampling "
+                              "(get_uncertain_point_coords_with_randomness) then draws from the device generator (engine.PointSampler), not "
+                              "from torch.rand, so a run does not reproduce the reference's points; the point cross-entropy loss and the "
+                              "backward of the point gather are HIP kernels.  Without the key only the eval-mode forward (model.eval(): "
+                              "validation, inference, Ensemble member, TTA, demo_infer) runs")
 
 
 class StandardPointHead(nn.Module):
@@ -198,30 +201,44 @@ class StandardPointHead(nn.Module):
 
 
 class PointRend(nn.Module):
-    """models/PointRend.py:8-90 of the reference, the eval-mode forward: UPerNet's logits at 1/s resolution, then log2(s) times upsample x 2,
-    pick the pr_subdivision_num_pts most uncertain pixels, re-predict them from point features of the four encoder stages and the coarse
-    logits, write them back.  The train-mode forward (random points, point loss) is refused: POINTREND_TRAINING_REFUSAL."""
+    """models/PointRend.py:8-90 of the reference.  Eval mode: UPerNet's logits at 1/s resolution, then log2(s) times upsample x 2, pick the
+    pr_subdivision_num_pts most uncertain pixels, re-predict them from point features of the four encoder stages and the coarse logits,
+    write them back.  Train mode (config['pr_train_on_device'] = True, a build-side key; refused without it: POINTREND_TRAINING_REFUSAL):
+    pr_train_num_pts points per image, int(pr_importance_sample_ratio P) of them the most uncertain of P pr_oversample_ratio uniform
+    candidates, the rest uniform; the point head's predictions there, and the x s interpolation of the coarse logits with those
+    predictions scattered in (engine.pointrend_train).  The points are the draws of `sampler` (an engine.PointSampler: device-resident
+    state, a non-persistent buffer; reseed(); sampler.fixed_points replaces the sampling in tests)."""
 
     def __init__(self, config, experiment):
         super().__init__()
         self.num_classes = num_classes(experiment)
         if self.num_classes < 2:
             raise ValueError("PointRend's uncertainty is the difference of the two largest logits: it needs at least 2 classes (got %d)" % self.num_classes)
-        self.train_num_pts = config["pr_train_num_pts"]                                 # (train-only: read and kept, unused)
-        self.oversample_ratio = config.get("pr_oversample_ratio", 3)                    # (train-only)
-        self.importance_sample_ratio = config.get("pr_importance_sample_ratio", .75)    # (train-only)
+        self.train_num_pts = config["pr_train_num_pts"]
+        self.oversample_ratio = config.get("pr_oversample_ratio", 3)
+        self.importance_sample_ratio = config.get("pr_importance_sample_ratio", .75)
         self.subdivision_num_pts = config["pr_subdivision_num_pts"]
+        self.train_on_device = bool(config.get("pr_train_on_device", False))
         self.in_channels = config["input_channels"]
         self.in_scales = config["input_scales"]
         self.fpn_num_lvl = min(max(config.get("fpn_num_lvl", len(self.in_scales)), 1), len(self.in_scales))
         config["interpolate_result_up"] = False     # the coarse prediction stays at 1/s resolution
         self.partial_upernet = UPerNet(config, experiment)
         self.point_head = StandardPointHead(config, self.num_classes)
+        self.sampler = PointSampler()
+
+    def reseed(self, seed, rank=None):
+        self.sampler.reseed(seed, rank)
 
     def run(self, cx, conv_out):
         coarse = self.partial_upernet.run(cx, conv_out)
-        steps = int(math.log2(self.in_scales[-self.fpn_num_lvl]))
-        return pointrend_refine(cx, coarse, conv_out, self.point_head.tensors(), self.subdivision_num_pts, steps)
+        scale = self.in_scales[-self.fpn_num_lvl]
+        if cx.train:
+            if not self.train_on_device:
+                raise NotImplementedError(POINTREND_TRAINING_REFUSAL)
+            return pointrend_train(cx, coarse, conv_out, self.point_head, self.sampler, self.train_num_pts, self.oversample_ratio,
+                                   self.importance_sample_ratio, scale)
+        return pointrend_refine(cx, coarse, conv_out, self.point_head.tensors(), self.subdivision_num_pts, int(math.log2(scale)))
 
 
 _DECODERS = {"UPerNet": UPerNet, "PointRend": PointRend}
@@ -246,11 +263,19 @@ class EncDec(EngineNet):
         self.out_stride = 32
 
     def forward(self, x):
-        if self.training and isinstance(self.dec_model, PointRend):
+        if not (self.training and isinstance(self.dec_model, PointRend)):
+            return super().forward(x)
+        if not self.dec_model.train_on_device:
             raise NotImplementedError(POINTREND_TRAINING_REFUSAL)
-        return super().forward(x)
+        # models/PointRend.py:73 with the encoder's features in front (models/EncDec.py of the reference): (deep_features, point_coords
+        # [N, P, 2], point_logits [N, K, P], seg_logits, pred) -- the last two are ONE tensor, as the reference's in-place scatter leaves them
+        outs = super().forward(x)
+        coords, logits, pred = outs[-3:]
+        res = (coords.squeeze(3).permute(0, 2, 1), logits.squeeze(3), pred, pred)
+        return (outs[0],) + res if self.get_features else res
 
     def _body(self, cx, x):
         feats = self.enc_model.run(cx, x)
         pred = self.dec_model.run(cx, feats)
-        return [feats[-1], pred] if self.get_features else [pred]
+        pred = list(pred) if isinstance(pred, tuple) else [pred]
+        return [feats[-1]] + pred if self.get_features else pred

@@ -1681,6 +1681,13 @@ def scale_by_device_scalar(x, s):
     return x
 
 
+def bias_grad(dy, C, dbias):
+    """dbias[c] = sum over the rows of dy[:, c], c < C (dy: 2-D rows or NHWC)"""
+    ws = workspace(256 * C * 4 + 1024, dy.device)
+    check(lib.catseg_bias_grad(ptr(dy), ld_of(dy), rows_of(dy), C, ptr(dbias), ptr(ws), ws.numel(), stream()))
+    return dbias
+
+
 def maxpool_fwd(x):
     B, H, W, C = x.shape
     Ho, Wo = (H + 1) // 2, (W + 1) // 2
@@ -2575,6 +2582,114 @@ def pointrend_scatter(rows, idx, seg):
     _, h, w, K = seg.shape
     check(lib.catseg_pointrend_scatter(ptr(rows), rows.stride(0), ptr(idx), N, k, h * w, ptr(seg), ld_of(seg), K, stream()))
     return seg
+
+
+# ---------------------------------------------------------------------------------------------- PointRend training (csrc/pointrend_train.hip)
+def pointrend_draw(state, N, M, fixed=None):
+    """[N, M, 2] uniforms in [0, 1): the next draw of the sampler whose 16-byte device state is `state` (int32 [4]: seed lo, seed hi,
+    layer | rank << 16, draw counter); the launch advances the counter.  fixed (a test knob): the given [N, M, 2] coordinates instead of a
+    draw, the state does not move."""
+    dev = fixed.device if fixed is not None else state.device
+    out = torch.empty((N, M, 2), dtype=torch.float32, device=dev)
+    if fixed is not None:
+        assert tuple(fixed.shape) == (N, M, 2) and fixed.dtype == torch.float32 and fixed.is_contiguous()
+    check(lib.catseg_pointrend_draw(None if fixed is not None else ptr(state), ptr(fixed) if fixed is not None else None, N, M, ptr(out), stream()))
+    return out
+
+
+def pointrend_point_uncertainty(coarse, coords):
+    """[N, M]: second-largest - largest of the K logits of coarse (NHWC [N, H, W, K], any pixel stride) point-sampled at coords [N, M, 2]"""
+    N, H, W, K = coarse.shape
+    if K < 2:
+        raise ValueError("PointRend's uncertainty is the difference of the two largest logits: it needs at least 2 classes (got %d)" % K)
+    M = coords.shape[1]
+    assert coords.shape[0] == N and coords.dtype == torch.float32 and coords.is_contiguous()
+    unc = torch.empty((N, M), dtype=torch.float32, device=coarse.device)
+    with _Timed("pointrend_point_uncertainty", 0.0):
+        check(lib.catseg_pointrend_point_uncertainty(ptr(coarse), ld_of(coarse), N, H, W, K, ptr(coords), M, ptr(unc), stream()))
+    return unc
+
+
+def pointrend_compose(cand, sel, rest, h, w, lbl=None):
+    """(coords [N, P, 2], pix int32 [N, P], labels int64 [N, P] or None): the selected candidates cand[b, sel[b]] followed by rest; per
+    point its pixel of the h x w map (models/PointRend.py:56-57 of the reference) and, with lbl (int64 [N, Hl, Wl]), its nearest label."""
+    N = (cand if cand is not None else rest).shape[0]
+    kb = 0 if sel is None else sel.shape[1]
+    R = 0 if rest is None else rest.shape[1]
+    P = kb + R
+    dev = (cand if cand is not None else rest).device
+    coords = torch.empty((N, P, 2), dtype=torch.float32, device=dev)
+    pix = torch.empty((N, P), dtype=torch.int32, device=dev)
+    labels = None
+    Hl = Wl = 0
+    if lbl is not None:
+        assert lbl.dtype == torch.int64 and lbl.is_contiguous() and lbl.dim() == 3 and lbl.shape[0] == N
+        Hl, Wl = lbl.shape[1:]
+        labels = torch.empty((N, P), dtype=torch.int64, device=dev)
+    check(lib.catseg_pointrend_compose(ptr(cand) if kb else None, cand.shape[1] if kb else 0, ptr(sel) if kb else None, kb, ptr(rest) if R else None, N, P,
+                                       h, w, ptr(lbl) if lbl is not None else None, Hl, Wl, ptr(coords), ptr(pix),
+                                       ptr(labels) if labels is not None else None, stream()))
+    return coords, pix, labels
+
+
+def pointrend_point_labels(coords, lbl):
+    """int64 [N, P]: F.grid_sample(lbl.float(), mode='nearest') at coords [N, P, 2] (managers/EncDec_Manager.py:164 of the reference)"""
+    coords = coords.detach()
+    if not coords.is_contiguous():
+        coords = coords.contiguous()
+    return pointrend_compose(None, None, coords, lbl.shape[1], lbl.shape[2], lbl.contiguous())[2]
+
+
+def pointrend_gather_at(sources, coords, out=None, extras=()):
+    """pointrend_gather at given points: coords [N, P, 2] (x, y) in [0, 1]^2"""
+    N, k, _ = coords.shape
+    assert coords.dtype == torch.float32 and coords.is_contiguous()
+    cols = sum((s.shape[-1] + 3) // 4 * 4 for s in sources)
+    if out is None:
+        out = torch.empty((N * k, cols), dtype=torch.float32, device=coords.device)
+    d = _lib.PointrendGatherDesc()
+    for i, s in enumerate(sources):
+        assert s.shape[0] == N and s.dtype == torch.float32
+        d.src[i], d.ld[i], d.H[i], d.W[i], d.C[i] = ptr(s), ld_of(s), s.shape[1], s.shape[2], s.shape[3]
+    d.n_sources, d.N, d.k, d.out, d.ld_out = len(sources), N, k, ptr(out), out.stride(0)
+    for i, (buf, c0) in enumerate(extras):
+        d.extra[i], d.extra_ld[i], d.extra_off[i] = ptr(buf), buf.stride(0), c0
+    d.n_extra = len(extras)
+    with _Timed("hbm:pointrend_gather_at", 4.0 * (4 + 1) * N * k * cols):
+        check(lib.catseg_pointrend_gather_at(ctypes.byref(d), ptr(coords), stream()))
+    return out
+
+
+def pointrend_gather_bwd(dx, coords, dests):
+    """the adjoint of pointrend_gather_at: dx [N P, >= cols] -> dests = [(NHWC gradient buffer [N, H, W, C], accumulate?)] in the order of
+    the gather's sources.  accumulate False: the whole buffer is written (pixels no tap touches: zero).  Deterministic, no atomics."""
+    N, P, _ = coords.shape
+    d = _lib.PointrendGatherBwdDesc()
+    nbytes = 0.0
+    for i, (g, acc) in enumerate(dests):
+        assert g.shape[0] == N and g.dtype == torch.float32
+        d.dst[i], d.ld[i], d.H[i], d.W[i], d.C[i], d.accumulate[i] = ptr(g), ld_of(g), g.shape[1], g.shape[2], g.shape[3], 1 if acc else 0
+        nbytes += 4.0 * ((0 if acc else g.numel()) + (4 + 4) * N * P * g.shape[3])
+    d.n_sources, d.coords, d.N, d.P, d.dx, d.ld_dx = len(dests), ptr(coords), N, P, ptr(dx), dx.stride(0)
+    with _Timed("hbm:pointrend_gather_bwd", nbytes):
+        check(lib.catseg_pointrend_gather_bwd(ctypes.byref(d), stream()))
+    return [g for g, _ in dests]
+
+
+def pointrend_scatter_last(rows, pix, seg):
+    """seg[b, pix[b, p], :] = rows[b P + p, :K] in place (seg NHWC [N, h, w, K]); among the points of one pixel the last one writes"""
+    N, P = pix.shape
+    _, h, w, K = seg.shape
+    check(lib.catseg_pointrend_scatter_last(ptr(rows), rows.stride(0), ptr(pix), N, P, h * w, ptr(seg), ld_of(seg), K, stream()))
+    return seg
+
+
+def pointrend_scatter_bwd(dseg, pix, drows, accumulate):
+    """drows[b P + p, :K] (+)= dseg[b, pix[b, p], :] for every point, then dseg = 0 at every scattered pixel (in place)"""
+    N, P = pix.shape
+    _, h, w, K = dseg.shape
+    check(lib.catseg_pointrend_scatter_bwd(ptr(dseg), ld_of(dseg), ptr(pix), N, P, h * w, ptr(drows), drows.stride(0), K, 1 if accumulate else 0, stream()))
+    return drows
 
 
 def _pointrend_weight(w, main, K, cache=None, slot=None):
