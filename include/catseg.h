@@ -34,7 +34,7 @@ extern "C" {
 typedef void* catseg_stream_t; /* hipStream_t */
 
 const char* catseg_last_error(void);
-int catseg_version(void);   /* 2: catseg_bn_apply / catseg_bn_backward take a descriptor, catseg_add_n_act its records */
+int catseg_version(void);   /* 3: catseg_conv2d_* take a descriptor (2: catseg_bn_apply / catseg_bn_backward do, catseg_add_n_act takes its records) */
 
 /* ---- convolution as implicit GEMM on v_mfma_f32_32x32x2_f32 ------------------------------
  * replaces F.conv2d behind nn.Conv2d at models/OCR.py:72-97,200-235,308-313 and
@@ -50,34 +50,75 @@ typedef struct {
                               weights [Cout][kh][kw][Cin/g], Cin/g a multiple of 4 */
 } catseg_conv_desc;
 
-/* y[p, o] = sum_{ky,kx,c} x[pix(p,ky,kx), c] * w[o,ky,kx,c] (+ bias[o]); columns
- * [Cout, zero_to) of y are written as zeros (zero_to <= ldy, 0 = none). */
-int catseg_conv2d_fwd(const catseg_conv_desc* d, const float* x, const float* w, const float* bias,
-                      float* y, int zero_to, catseg_stream_t stream);
-/* training forward of conv -> BatchNorm (models/OCR.py:72-76 etc.): catseg_conv2d_fwd whose epilogue also writes per-(M-tile,
- * channel) BatchNorm partials [n_tiles][3][Cout] (K, s1, s2) for catseg_bn_finalize -- no separate statistics pass over y.
- * *tile_rows == 0 on return: this layer's tile form has no fused statistics; use catseg_bn_train_stats. */
-int catseg_conv2d_fwd_bnstats(const catseg_conv_desc* d, const float* x, const float* w, const float* bias, float* y,
-                              int zero_to, float* bn_part, size_t bn_part_floats, int* tile_rows, int* n_tiles,
-                              catseg_stream_t stream);
-/* inference: y = act(conv(x, w) + bias (+ residual)), act = relu if relu != 0, in one kernel.  With
- * catseg_fold_bn this is Conv2d + eval-mode BatchNorm2d + residual add + ReLU of a ResNet / UPerNet block. */
-int catseg_conv2d_fwd_fused(const catseg_conv_desc* d, const float* x, const float* w, const float* bias,
-                            const float* residual, int ldr, int relu, float* y, catseg_stream_t stream);
+/* ---- the four convolution entry points: one per direction + the backward-weight workspace query.  `operands` says how BOTH GEMM operands
+ * of a call are stored; the descriptors are flat, a field left NULL / 0 is "not used".
+ *
+ *  CATSEG_OPERANDS_  activation (x / dy) and weight operand                                         directions and extras accepted
+ *  F32               NHWC fp32 activations; OHWI fp32 weights (forward and backward-data read the   all three; groups, stem4, any stride, residual / relu,
+ *                    same tensor)                                                                   dbias
+ *  BF16X3            catseg_split3 [3][rows][roundup(C, 8)]; weights: catseg_split3 of the          all three; Cin % 8 == 0; no residual / relu
+ *                    [Cout][kh kw Cin] view (forward), catseg_split3_weight_t (backward-data)
+ *  BF16X3_BLOCKED    catseg_split3_blocked [3][ceil(C/16)][rows][16]; catseg_split3_weight_blocked  forward (Cin % 16 == 0; residual / relu), backward-data
+ *                    (forward), catseg_split3_weight_t_blocked (backward-data)
+ *  F16X2             catseg_split2h planar [2][rows][roundup(C, 8)] + both 8-byte scale records     backward-weight; Cin % 8 == 0
+ *  F16X2_BLOCKED     catseg_split2h blocked [2][ceil(C/16)][rows][16] + both scale records;         all three (forward: Cin % 16 == 0, residual / relu;
+ *                    catseg_split2h_weight_blocked (forward), _weight_t_blocked (backward-data)     backward-weight: Cin % 8 == 0)
+ *
+ *  geo.ldx / geo.ldy.  F32: floats per pixel of the x (dx) and y (dy) buffers.  Plane operands: a plane has its own pitch (above), so only
+ *  the fp32 side of a call is a row stride -- forward: ldx = Cin, ldy = row stride of y; backward-data: ldx = row stride of dx,
+ *  ldy = roundup(Cout, 8); backward-weight: ldx = Cin, ldy = roundup(Cout, 8).
+ *
+ *  Plane operands: dense only (groups <= 1, no stem4); at most 32 taps in forward / backward-data; backward-data for stride 1 only; planes
+ *  16-byte aligned; no dbias (catseg_bias_grad computes it); a scale record per operand with f16x2, none with any other form.  residual /
+ *  relu (the inference epilogue) exclude zero_to and bn_part.  Anything else returns CATSEG_EINVAL before any launch, with a message that
+ *  starts with the function's name. */
+#define CATSEG_OPERANDS_F32 0
+#define CATSEG_OPERANDS_BF16X3 1
+#define CATSEG_OPERANDS_BF16X3_BLOCKED 2
+#define CATSEG_OPERANDS_F16X2 3
+#define CATSEG_OPERANDS_F16X2_BLOCKED 4
+/* y[p, o] = act(sum_{ky,kx,c} x[pix(p,ky,kx), c] * w[o,ky,kx,c] (+ bias[o]) (+ residual[p, o])), act = relu if relu != 0; columns
+ * [Cout, zero_to) of y are written as zeros (zero_to <= ldy, 0 = none).
+ * bn_part != NULL: the training forward of conv -> BatchNorm (models/OCR.py:72-76 etc.): the epilogue also writes per-(M-tile, channel)
+ * BatchNorm partials [n_tiles][3][Cout] (K, s1, s2) for catseg_bn_finalize -- no separate statistics pass over y.  tile_rows / n_tiles are
+ * then required and always written; *tile_rows == 0: this layer's tile form has no fused statistics (or bn_part_floats is too small for
+ * them), use catseg_bn_train_stats.
+ * residual / relu: inference, with catseg_fold_bn this is Conv2d + eval-mode BatchNorm2d + residual add + ReLU of a ResNet / UPerNet block
+ * in one kernel. */
+typedef struct {
+  catseg_conv_desc geo; int operands;
+  const void* x; const void* x_scale;
+  const void* w; const void* w_scale;
+  const float* bias;
+  float* y; int zero_to;
+  float* bn_part; size_t bn_part_floats; int* tile_rows; int* n_tiles;
+  const float* residual; int ldr; int relu;
+} catseg_conv_fwd_desc;
+int catseg_conv2d_fwd(const catseg_conv_fwd_desc* d, catseg_stream_t stream);
+/* dx[q, c] (+)= sum_{ky,kx,o} dy[opix(q,ky,kx), o] * w[o,ky,kx,c]  (autograd of the above; w: see the table) */
+typedef struct {
+  catseg_conv_desc geo; int operands;
+  const void* dy; const void* dy_scale;
+  const void* w; const void* w_scale;
+  float* dx; int accumulate;
+} catseg_conv_bwd_data_desc;
+int catseg_conv2d_bwd_data(const catseg_conv_bwd_data_desc* d, catseg_stream_t stream);
+/* dw[o,ky,kx,c] = sum_p dy[p, o] * x[pix(p,ky,kx), c]; dbias[o] = sum_p dy[p,o] (may be NULL).
+ * workspace: catseg_conv2d_bwd_weight_workspace() bytes (split-reduction slabs); too small: CATSEG_EWORKSPACE. */
+typedef struct {
+  catseg_conv_desc geo; int operands;
+  const void* x; const void* x_scale;
+  const void* dy; const void* dy_scale;
+  float* dw; float* dbias;
+  void* workspace; size_t workspace_bytes;
+} catseg_conv_bwd_weight_desc;
+size_t catseg_conv2d_bwd_weight_workspace(const catseg_conv_desc* geo, int operands);
+int catseg_conv2d_bwd_weight(const catseg_conv_bwd_weight_desc* d, catseg_stream_t stream);
 /* w'[o,:] = w[o,:] * gamma[o]/sqrt(rv[o]+eps), b'[o] = beta[o] + (b[o] - rm[o]) * gamma[o]/sqrt(rv[o]+eps);
  * per_out = floats per output channel of w (kh*kw*Cin, or 7*32 for the packed stem) */
 int catseg_fold_bn(const float* w, const float* bias, const float* gamma, const float* beta, const float* running_mean,
                    const float* running_var, float eps, int O, int per_out, float* w_folded, float* bias_folded,
                    catseg_stream_t stream);
-/* dx[q, c] (+)= sum_{ky,kx,o} dy[opix(q,ky,kx), o] * w[o,ky,kx,c]  (autograd of the above) */
-int catseg_conv2d_bwd_data(const catseg_conv_desc* d, const float* dy, const float* w, float* dx,
-                           int accumulate, catseg_stream_t stream);
-/* dw[o,ky,kx,c] = sum_p dy[p, o] * x[pix(p,ky,kx), c]; dbias[o] = sum_p dy[p,o] (may be NULL).
- * workspace: catseg_conv2d_bwd_weight_workspace() bytes (split-reduction slabs). */
-size_t catseg_conv2d_bwd_weight_workspace(const catseg_conv_desc* d);
-int catseg_conv2d_bwd_weight(const catseg_conv_desc* d, const float* x, const float* dy, float* dw,
-                             float* dbias, void* workspace, size_t workspace_bytes,
-                             catseg_stream_t stream);
 
 /* ---- batched GEMM for the OCR gather / object attention (torch.matmul at
  * models/OCR.py:167,266,274).  C[z] (M x N, ldc) = op(A[z]) * op(B[z]):
@@ -123,17 +164,6 @@ int catseg_gemm_batched(int layout, int batch, int M, int N, int K, const float*
 size_t catseg_split3_elems(long long rows, int C);   /* 16-bit elements per plane: rows * roundup(C, 8) */
 int catseg_split3(const float* x, int ld, long long rows, int C, void* planes, catseg_stream_t stream);
 int catseg_split3_weight_t(const float* w, int O, int taps, int Cin, void* planes, catseg_stream_t stream);
-int catseg_conv2d_fwd_bf16x3(const catseg_conv_desc* d, const void* x_planes, const void* w_planes, const float* bias,
-                             float* y, int zero_to, catseg_stream_t stream);
-int catseg_conv2d_fwd_bf16x3_bnstats(const catseg_conv_desc* d, const void* x_planes, const void* w_planes, const float* bias,
-                                     float* y, int zero_to, float* bn_part, size_t bn_part_floats, int* tile_rows, int* n_tiles,
-                                     catseg_stream_t stream);
-int catseg_conv2d_bwd_data_bf16x3(const catseg_conv_desc* d, const void* dy_planes, const void* wt_planes, float* dx,
-                                  int accumulate, catseg_stream_t stream);
-/* dw = backward-weight from pre-split planes (x: C = Cin, dy: C = Cout); workspace = split-reduction slabs */
-size_t catseg_conv2d_bwd_weight_bf16x3_workspace(const catseg_conv_desc* d);
-int catseg_conv2d_bwd_weight_bf16x3(const catseg_conv_desc* d, const void* x_planes, const void* dy_planes, float* dw,
-                                    void* workspace, size_t workspace_bytes, catseg_stream_t stream);
 /* BLOCKED operand planes for the large layers (>= 193 output columns): activations [3][ceil(C/16)][rows][16], weights
  * [3][K/16][N][16] -- the 256 rows of one K-step form one contiguous run, so that every LDS-DMA instruction of the 256 x 256
  * kernel reads whole cache lines (the [rows][C] planes above gave each lane pair its own line and bounded that kernel by the
@@ -144,15 +174,6 @@ int catseg_split3_blocked(const float* x, long long rows, int C, int ld, void* b
                           catseg_stream_t stream);
 int catseg_split3_weight_blocked(const float* w, int O, int taps, int Cin, void* planes, catseg_stream_t stream);    /* Cin % 16 == 0 */
 int catseg_split3_weight_t_blocked(const float* w, int O, int taps, int Cin, void* planes, catseg_stream_t stream);  /* [taps*roundup(O,16)/16][Cin][16] */
-/* forward (Cin % 16 == 0; bn_part may be NULL: no BatchNorm partials) and stride-1 backward-data from blocked planes */
-int catseg_conv2d_fwd_bf16x3_blocked(const catseg_conv_desc* d, const void* x_planes, const void* w_planes, const float* bias,
-                                     float* y, int zero_to, float* bn_part, size_t bn_part_floats, int* tile_rows, int* n_tiles,
-                                     catseg_stream_t stream);
-/* inference: y = act(conv + bias (+ residual)) in one kernel, the bf16x3 counterpart of catseg_conv2d_fwd_fused */
-int catseg_conv2d_fwd_fused_bf16x3_blocked(const catseg_conv_desc* d, const void* x_planes, const void* w_planes, const float* bias,
-                                           const float* residual, int ldr, int relu, float* y, catseg_stream_t stream);
-int catseg_conv2d_bwd_data_bf16x3_blocked(const catseg_conv_desc* d, const void* dy_planes, const void* wt_planes, float* dx,
-                                          int accumulate, catseg_stream_t stream);
 /* dbias[o] = sum_p dy[p, o] (the bias-gradient part of catseg_conv2d_bwd_weight on its own); workspace >= 256 * C floats */
 int catseg_bias_grad(const float* dy, int ld, long long rows, int C, float* dbias, void* workspace, size_t workspace_bytes,
                      catseg_stream_t stream);
@@ -178,21 +199,7 @@ int catseg_split2h_weight_blocked(const float* w, int O, int taps, int Cin, void
 int catseg_concat_bilinear_split2h(int nsrc, const float* const* xs, const int* lds, const int* Hs, const int* Ws, const int* Cs,
                                    const void* const* records, int B, int Ho, int Wo, void* blocked_planes, void* scale, catseg_stream_t stream);
 int catseg_split2h_weight_t_blocked(const float* w, int O, int taps, int Cin, void* planes, void* scale, catseg_stream_t stream);
-int catseg_conv2d_fwd_f16x2_blocked(const catseg_conv_desc* d, const void* x_planes, const void* x_scale, const void* w_planes,
-                                    const void* w_scale, const float* bias, float* y, int zero_to, float* bn_part, size_t bn_part_floats,
-                                    int* tile_rows, int* n_tiles, catseg_stream_t stream);
-int catseg_conv2d_fwd_fused_f16x2_blocked(const catseg_conv_desc* d, const void* x_planes, const void* x_scale, const void* w_planes,
-                                          const void* w_scale, const float* bias, const float* residual, int ldr, int relu, float* y,
-                                          catseg_stream_t stream);
-int catseg_conv2d_bwd_data_f16x2_blocked(const catseg_conv_desc* d, const void* dy_planes, const void* dy_scale, const void* wt_planes,
-                                         const void* wt_scale, float* dx, int accumulate, catseg_stream_t stream);
-size_t catseg_conv2d_bwd_weight_f16x2_workspace(const catseg_conv_desc* d);
-int catseg_conv2d_bwd_weight_f16x2(const catseg_conv_desc* d, const void* x_planes, const void* x_scale, const void* dy_planes,
-                                   const void* dy_scale, float* dw, void* workspace, size_t workspace_bytes, catseg_stream_t stream);
-/* the same from the BLOCKED planes of catseg_split2h (the operand layout of the forward / backward-data kernels): one plane set per tensor
- * serves all three directions of a layer (the backward of F.conv2d at models/OCR.py:72-89, 326-333). */
-int catseg_conv2d_bwd_weight_f16x2_blocked(const catseg_conv_desc* d, const void* x_planes, const void* x_scale, const void* dy_planes,
-                                           const void* dy_scale, float* dw, void* workspace, size_t workspace_bytes, catseg_stream_t stream);
+/* (one blocked plane set per tensor serves all three directions of a layer: the backward of F.conv2d at models/OCR.py:72-89, 326-333) */
 
 /* ---- the first stem convolution of HRNet: nn.Conv2d(3, 64, 3, stride 2, padding 1) on the image (models/HRNetv2.py:281-283), exact fp32, HBM-bound
  * direct kernels (csrc/stem3.hip).  x is addressed through element strides (sb, sc, sy, sx) for (batch, channel, row, column): NCHW or NHWC-4,
@@ -219,7 +226,7 @@ int catseg_stem7_fwd(const float* x, long long sb, long long sc, long long sy, l
 
 /* ---- direct 3x3 / stride 1 / pad 1 convolution in split precision (csrc/dconv3_b3.hip) for the HRNet trunk: the BasicBlock
  * convolutions conv3x3(planes, planes) at models/HRNetv2.py:22-25,41-44 (Cin = Cout = C in {48, 96}; catseg_dconv3_supported).
- * Same F.conv2d call sites and same arithmetic as catseg_conv2d_fwd_bf16x3 (three exact bf16 planes per fp32 operand, six bf16
+ * Same F.conv2d call sites and same arithmetic as catseg_conv2d_fwd on bf16x3 operands (three exact bf16 planes per fp32 operand, six bf16
  * MFMA products, fp32 accumulation), but the activation is read as fp32 and split inside the kernel: a block loads the halo
  * tile of its pixel tile once and forms all nine taps from it.
  *   catseg_dconv3_prep: OHWI fp32 weights [C][3][3][C] -> the kernel's pre-split weight image (catseg_dconv3_wimg_bytes bytes);
@@ -246,7 +253,7 @@ int catseg_dconv3_bnbwd(int B, int H, int W, int C, const float* dy, int lddy, c
                         int ldq, const float* stats, const float* gamma, const float* beta, float* part, size_t part_floats,
                         catseg_stream_t stream);
 /* The same direct kernels on TWO fp16 planes and THREE products (csrc/dconv3_f16x2.hip = dconv3_b3.hip compiled with DC_H2; the
- * arithmetic of catseg_conv2d_fwd_f16x2_blocked).  The activation is split inside the kernel, so its power-of-two prescale comes from a
+ * arithmetic of catseg_conv2d_fwd on f16x2 operands).  The activation is split inside the kernel, so its power-of-two prescale comes from a
  * DEVICE amax record of CATSEG_AMAX_RECORD_BYTES = 2048 bytes (16 uint32 slots 128 bytes apart; max over the slots = bits of max|x|
  * over the whole tensor) that the PRODUCER of x accumulated (catseg_bn_apply, catseg_add_n_act, catseg_bn_backward given a record:
  * one fire-and-forget atomicMax per block into slot blockIdx % 16; the caller zeroes the record before the producer runs).  A record value above the true maximum is safe, one below it overflows fp16.
@@ -444,7 +451,7 @@ int catseg_bn_apply(const catseg_bn_apply_desc* d, catseg_stream_t stream);
  *                          dy_record: zeroed, receives the bound the exponent comes from, and the exponent
  *   dy_h2_planes           ONLY the blocked fp16 x 2 planes of catseg_split2h (catseg_split2h_blocked_elems(rows, C) halves) with
  *                          dy_h2_scale, their 8-byte record {bits of the bound, e} -- for a layer whose backward-weight / backward-data run
- *                          catseg_conv2d_bwd_weight_f16x2_blocked / catseg_conv2d_bwd_data_f16x2_blocked (the BatchNorm behind the head
+ *                          catseg_conv2d_bwd_weight / catseg_conv2d_bwd_data on CATSEG_OPERANDS_F16X2_BLOCKED (the BatchNorm behind the head
  *                          convolutions, models/OCR.py:72-89, 326-333).  dbias (may be NULL) = column sums of dy (gradient of a convolution
  *                          bias in front of the BatchNorm).  No residual branch, no mask; C % 64 == 0; the planes below 4 GB; g_record /
  *                          y_record / dy_record: three zeroed amax records, they receive max|g|, max|y| and the bound;
@@ -732,7 +739,7 @@ int catseg_adam_step_dev(float* p, const float* g, float* m, float* v, long long
    (bytes, relative to wimg_base), int32 O, I, kh, kw, transposed, ky0, kys, nky, kx0, kxs, nkx, pad} (a 1 x 1 layer: kh = kw = nky = nkx =
    kys = kxs = 1, ky0 = kx0 = 0); records = n x {uint32 bits of max|w|, int32 exponent} (DEVICE).
    catseg_pconv1: y[M][N] (+)= x[M][K] . B^T (+ bias); B = image of (N, K) = the layer's [O][I] weights (forward: N = O, K = I) or, with
-   transposed != 0 at preparation, their transpose (backward-data: N = I, K = O).  bn_part as catseg_conv2d_fwd_bnstats.
+   transposed != 0 at preparation, their transpose (backward-data: N = I, K = O).  bn_part as in catseg_conv2d_fwd.
    catseg_pconv1_wgrad: dw[Cout][Cin] = dy^T . x over P pixels (slabs + fixed-order sum: deterministic). */
 int catseg_pconv1_supported(int N, int K);
 size_t catseg_pconv1_wimg_bytes(int N, int K);
@@ -765,7 +772,7 @@ int catseg_gconv_bwd_weight(const catseg_conv_desc* d, const float* dy, const vo
 
 /* ---- PointRend, eval-mode refinement (models/PointRend.py:74-90 of the reference: F.interpolate x 2, calculate_uncertainty, torch.topk,
  * five point_sample = F.grid_sample calls, torch.cat, scatter_; csrc/pointrend.hip).  The point head's layers are 1 x 1 convolutions over
- * the N k points and run through catseg_conv2d_fwd / catseg_conv2d_fwd_fused; the upsampling is the catseg_bilinear_fwd launch.  Nothing here synchronises with the host or allocates: a
+ * the N k points and run through catseg_conv2d_fwd; the upsampling is the catseg_bilinear_fwd launch.  Nothing here synchronises with the host or allocates: a
  * refinement step can be captured in a hipGraph.
  *   uncertainty: uncertainty[p] = second-largest - largest of y[p ldy + 0 .. K) (<= 0; equal logits give 0), p < pixels: the rows the resize
  *               launch (catseg_bilinear_fwd, align_corners = 0, x 2) stored.  Columns K .. ldy are never read.  K >= 2 (one class has no

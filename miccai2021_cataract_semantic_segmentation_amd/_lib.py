@@ -27,6 +27,25 @@ class ConvDesc(C.Structure):
                                  "ldx", "ldy", "stem4", "groups")]
 
 
+# catseg_conv_fwd_desc / _bwd_data_desc / _bwd_weight_desc, filled by keyword: a field left out is NULL / 0.  operands: how both GEMM operands
+# of the call are stored (CATSEG_OPERANDS_*)
+OPERANDS_F32, OPERANDS_BF16X3, OPERANDS_BF16X3_BLOCKED, OPERANDS_F16X2, OPERANDS_F16X2_BLOCKED = range(5)
+
+
+class ConvFwdDesc(C.Structure):
+    _fields_ = [("geo", ConvDesc), ("operands", I), ("x", P), ("x_scale", P), ("w", P), ("w_scale", P), ("bias", P), ("y", P), ("zero_to", I),
+                ("bn_part", P), ("bn_part_floats", SZ), ("tile_rows", P), ("n_tiles", P), ("residual", P), ("ldr", I), ("relu", I)]
+
+
+class ConvBwdDataDesc(C.Structure):
+    _fields_ = [("geo", ConvDesc), ("operands", I), ("dy", P), ("dy_scale", P), ("w", P), ("w_scale", P), ("dx", P), ("accumulate", I)]
+
+
+class ConvBwdWeightDesc(C.Structure):
+    _fields_ = [("geo", ConvDesc), ("operands", I), ("x", P), ("x_scale", P), ("dy", P), ("dy_scale", P), ("dw", P), ("dbias", P),
+                ("workspace", P), ("workspace_bytes", SZ)]
+
+
 # catseg_bn_apply_desc / catseg_bn_backward_desc, filled by keyword: a field left out is NULL / 0
 class BnApplyDesc(C.Structure):
     _fields_ = [("y", P), ("ldy", I), ("mean", P), ("scale", P), ("beta", P), ("residual", P), ("ldr", I), ("residual_record", P), ("z", P), ("ldz", I),
@@ -53,9 +72,7 @@ class PointrendGatherBwdDesc(C.Structure):
 _SIGS = {
     "catseg_last_error": (C.c_char_p, []),
     "catseg_version": (I, []),
-    "catseg_conv2d_fwd": (I, [P, P, P, P, P, I, P]),
-    "catseg_conv2d_fwd_bnstats": (I, [P, P, P, P, P, I, P, SZ, P, P, P]),
-    "catseg_conv2d_fwd_bf16x3_bnstats": (I, [P, P, P, P, P, I, P, SZ, P, P, P]),
+    "catseg_conv2d_fwd": (I, [P, P]),
     "catseg_bn_finalize": (I, [P, I, L, L, I, P, F, F, P, P, P, P, P]),
     "catseg_bn_finalize_counts": (I, [P, I, P, L, I, P, F, F, P, P, P, P, P]),
     "catseg_dconv3_supported": (I, [I]),
@@ -102,11 +119,10 @@ _SIGS = {
     "catseg_upcat2x_fwd": (I, [P, I, P, I, P, I, I, I, I, I, I, P, P]),
     "catseg_relu_bwd_rec": (I, [P, I, P, I, P, P, I, P, I, I, I, I, I, P, P]),
     "catseg_bn_mask_bytes": (SZ, [L, I]),
-    "catseg_conv2d_fwd_fused": (I, [P, P, P, P, P, I, I, P, P]),
     "catseg_fold_bn": (I, [P, P, P, P, P, P, F, I, I, P, P, P]),
-    "catseg_conv2d_bwd_data": (I, [P, P, P, P, I, P]),
-    "catseg_conv2d_bwd_weight_workspace": (SZ, [P]),
-    "catseg_conv2d_bwd_weight": (I, [P, P, P, P, P, P, SZ, P]),
+    "catseg_conv2d_bwd_data": (I, [P, P]),
+    "catseg_conv2d_bwd_weight_workspace": (SZ, [P, I]),
+    "catseg_conv2d_bwd_weight": (I, [P, P]),
     "catseg_gemm_batched": (I, [I, I, I, I, I, P, I, L, P, I, L, P, I, L, I, I, P]),
     "catseg_sum_slabs": (I, [P, P, L, I, I, I, P]),
     "catseg_debug_set_tile": (I, [I, I]),
@@ -135,16 +151,10 @@ _SIGS = {
     "catseg_split3_blocked": (I, [P, L, I, I, P, P, P]),
     "catseg_split3_weight_blocked": (I, [P, I, I, I, P, P]),
     "catseg_split3_weight_t_blocked": (I, [P, I, I, I, P, P]),
-    "catseg_conv2d_fwd_bf16x3_blocked": (I, [P, P, P, P, P, I, P, SZ, P, P, P]),
-    "catseg_conv2d_bwd_data_bf16x3_blocked": (I, [P, P, P, P, I, P]),
-    "catseg_conv2d_fwd_fused_bf16x3_blocked": (I, [P, P, P, P, P, I, I, P, P]),
     "catseg_split2h_blocked_elems": (SZ, [L, I]),
     "catseg_split2h_planar_elems": (SZ, [L, I]),
     "catseg_split2h": (I, [P, L, I, I, P, P, P, P]),
     "catseg_split2h_bound": (I, [P, L, I, I, P, P, P, P, P, P, P, P]),
-    "catseg_conv2d_bwd_weight_f16x2_workspace": (SZ, [P]),
-    "catseg_conv2d_bwd_weight_f16x2": (I, [P, P, P, P, P, P, P, SZ, P]),
-    "catseg_conv2d_bwd_weight_f16x2_blocked": (I, [P, P, P, P, P, P, P, SZ, P]),
     "catseg_concat_bilinear_split2h": (I, [I, P, P, P, P, P, P, I, I, I, P, P, P]),
     "catseg_stem3_supported": (I, [I, I, I]),
     "catseg_stem3_partial_rows": (I, [I, I, I]),
@@ -156,13 +166,6 @@ _SIGS = {
     "catseg_stem7_fwd": (I, [P, L, L, L, L, I, I, I, P, P, P, I, P, P, P]),
     "catseg_split2h_weight_blocked": (I, [P, I, I, I, P, P, P]),
     "catseg_split2h_weight_t_blocked": (I, [P, I, I, I, P, P, P]),
-    "catseg_conv2d_fwd_f16x2_blocked": (I, [P, P, P, P, P, P, P, I, P, SZ, P, P, P]),
-    "catseg_conv2d_fwd_fused_f16x2_blocked": (I, [P, P, P, P, P, P, P, I, I, P, P]),
-    "catseg_conv2d_bwd_data_f16x2_blocked": (I, [P, P, P, P, P, P, I, P]),
-    "catseg_conv2d_fwd_bf16x3": (I, [P, P, P, P, P, I, P]),
-    "catseg_conv2d_bwd_data_bf16x3": (I, [P, P, P, P, I, P]),
-    "catseg_conv2d_bwd_weight_bf16x3_workspace": (SZ, [P]),
-    "catseg_conv2d_bwd_weight_bf16x3": (I, [P, P, P, P, P, SZ, P]),
     "catseg_bias_grad": (I, [P, I, L, I, P, P, SZ, P]),
     "catseg_bn_workspace": (SZ, [L, I]),
     "catseg_bn_train_stats": (I, [P, L, I, I, P, F, F, P, P, P, P, P, SZ, P]),
@@ -265,8 +268,11 @@ if os.environ.get("CATSEG_SYNC"):  # debugging aid: synchronise after every entr
             if name in ("catseg_last_error", "catseg_version") or name.endswith("_workspace"):
                 return fn
 
+            def fields(st):     # (a descriptor's geometry is a nested structure)
+                return {f: fields(v) if isinstance(v, C.Structure) else v for f, v in ((f, getattr(st, f)) for f, _ in st._fields_)}
+
             def call(*a):
-                desc = [{f: getattr(x._obj, f) for f, _ in x._obj._fields_} for x in a if isinstance(getattr(x, "_obj", None), C.Structure)]
+                desc = [fields(x._obj) for x in a if isinstance(getattr(x, "_obj", None), C.Structure)]
                 print("[catseg]", name, desc, [x for x in a if isinstance(x, (int, float))], flush=True)
                 rc = fn(*a)
                 torch.cuda.synchronize()

@@ -13,4 +13,4 @@ void catseg_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* catseg_last_error(void) { return g_err; }
-extern "C" int catseg_version(void) { return 2; }
+extern "C" int catseg_version(void) { return 3; }

@@ -11,6 +11,19 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 void catseg_set_error(const char* fmt, ...);
 
+// The per-arithmetic halves of catseg_conv2d_fwd / _bwd_data / _bwd_weight (csrc/conv.hip checks what the operand forms share and dispatches):
+// fp32 in igemm.hip, three bf16 planes in igemm_bf16x3.hip, two fp16 planes in igemm_f16x2.hip.  Each keeps its form's own checks and messages.
+int cs_conv_fwd_f32(const catseg_conv_fwd_desc* q, hipStream_t st);
+int cs_conv_fwd_b3(const catseg_conv_fwd_desc* q, hipStream_t st);
+int cs_conv_fwd_h2(const catseg_conv_fwd_desc* q, hipStream_t st);
+int cs_conv_bwd_data_f32(const catseg_conv_bwd_data_desc* q, hipStream_t st);
+int cs_conv_bwd_data_b3(const catseg_conv_bwd_data_desc* q, hipStream_t st);
+int cs_conv_bwd_data_h2(const catseg_conv_bwd_data_desc* q, hipStream_t st);
+size_t cs_conv_bwd_weight_workspace_f32(const catseg_conv_desc* d);
+int cs_conv_bwd_weight_f32(const catseg_conv_bwd_weight_desc* q, hipStream_t st);
+int cs_conv_bwd_weight_b3(const catseg_conv_bwd_weight_desc* q, hipStream_t st);
+int cs_conv_bwd_weight_h2(const catseg_conv_bwd_weight_desc* q, hipStream_t st);
+
 #define CS_REQUIRE(cond, ...)                 \
   do {                                        \
     if (!(cond)) {                            \

@@ -1125,62 +1125,42 @@ extern "C" int catseg_debug_set_splits(int splits) {
 
 extern "C" int catseg_debug_plan_conv(const catseg_conv_desc* d, int op, int* out);
 
-extern "C" int catseg_conv2d_fwd(const catseg_conv_desc* d, const float* x, const float* w, const float* bias,
-                                 float* y, int zero_to, catseg_stream_t stream) {
+// fp32 operands of catseg_conv2d_fwd.  bn_part: the kernel's epilogue also writes the per-(M-tile, channel) BatchNorm partials for
+// catseg_bn_finalize (no separate statistics pass over y); *tile_rows == 0 means this layer's tile form has no fused statistics (grouped /
+// 16-32 wide forms): the convolution has run, the caller uses catseg_bn_train_stats instead.  residual / relu: y = act(conv(x, w) + bias
+// (+ residual)) in ONE kernel -- Conv2d + eval-mode BatchNorm2d (folded into w / bias by catseg_fold_bn) + residual add + ReLU of a ResNet /
+// ResNeXt / UPerNet block.
+int cs_conv_fwd_f32(const catseg_conv_fwd_desc* q, hipStream_t st) {
+  const catseg_conv_desc* d = &q->geo;
   if (int e = check_desc(d)) return e;
-  CS_REQUIRE(cs_aligned16(x) && cs_aligned16(w) && cs_aligned16(y), "conv fwd: pointers must be 16-byte aligned");
-  CS_REQUIRE(zero_to <= d->ldy, "conv fwd: zero_to > ldy");
-  IgemmArgs a = fwd_args(d, x, w, bias, y);
-  a.zero_to = zero_to;
+  CS_REQUIRE(cs_aligned16(q->x) && cs_aligned16(q->w) && cs_aligned16(q->y), "conv fwd%s: pointers must be 16-byte aligned",
+             q->residual || q->relu ? " fused" : "");
+  if (q->bn_part) CS_REQUIRE(q->zero_to <= d->ldy && q->tile_rows && q->n_tiles, "conv fwd bnstats: bad args");
+  else CS_REQUIRE(q->zero_to <= d->ldy, "conv fwd: zero_to > ldy");
+  if (q->bn_part) { *q->tile_rows = 0; *q->n_tiles = 0; }
+  IgemmArgs a = fwd_args(d, (const float*)q->x, (const float*)q->w, q->bias, q->y);
+  a.zero_to = q->zero_to;
+  a.residual = q->residual; a.ldr = q->ldr; a.relu = q->relu;
   if (d->groups > 1) {
-    CS_REQUIRE(zero_to == 0, "conv fwd: zero_to is not supported with groups");
-    group_args(a, d);
-    if (bias) { catseg_set_error("conv fwd: bias is not supported with groups"); return CATSEG_EINVAL; }
-    return launch_igemm<L_NT>(a, d->groups, 1, (hipStream_t)stream);
-  }
-  return launch_igemm<L_NT>(a, 1, 1, (hipStream_t)stream);
-}
-
-// Training forward of conv -> BatchNorm: as catseg_conv2d_fwd, and the kernel's epilogue also writes the per-(M-tile, channel)
-// BatchNorm partials for catseg_bn_finalize (no separate statistics pass over y).  *tile_rows / *n_tiles describe the
-// partials ([n_tiles][3][Cout] floats in bn_part); *tile_rows == 0 means this layer's tile form has no fused statistics
-// (grouped / 16-32 wide forms): the convolution has run, the caller uses catseg_bn_train_stats instead.
-extern "C" int catseg_conv2d_fwd_bnstats(const catseg_conv_desc* d, const float* x, const float* w, const float* bias, float* y,
-                                         int zero_to, float* bn_part, size_t bn_part_floats, int* tile_rows, int* n_tiles,
-                                         catseg_stream_t stream) {
-  if (int e = check_desc(d)) return e;
-  CS_REQUIRE(cs_aligned16(x) && cs_aligned16(w) && cs_aligned16(y), "conv fwd: pointers must be 16-byte aligned");
-  CS_REQUIRE(zero_to <= d->ldy && tile_rows && n_tiles, "conv fwd bnstats: bad args");
-  *tile_rows = 0; *n_tiles = 0;
-  if (d->groups > 1) return catseg_conv2d_fwd(d, x, w, bias, y, zero_to, stream);
-  IgemmArgs a = fwd_args(d, x, w, bias, y);
-  a.zero_to = zero_to;
-  const int ncols = zero_to > a.N ? zero_to : a.N;
-  const TilePlan pl = plan_tiles(L_NT, a.M, ncols, 1, a.g.rows, true, (long long)a.taps * a.Cred);
-  if ((pl.narrow == 0 || pl.narrow == 1) && cs_claim_bn_partials(a.M, 64 * pl.mi, d->Cout, bn_part, bn_part_floats, tile_rows, n_tiles))
-    a.bn_part = bn_part;
-  return launch_igemm<L_NT>(a, 1, 1, (hipStream_t)stream, &pl);
-}
-
-// Inference: y = act(conv(x, w) + bias (+ residual)) in ONE kernel — Conv2d + eval-mode BatchNorm2d (folded into
-// w / bias by catseg_fold_bn) + residual add + ReLU of a ResNet / ResNeXt / UPerNet block.
-extern "C" int catseg_conv2d_fwd_fused(const catseg_conv_desc* d, const float* x, const float* w, const float* bias,
-                                       const float* residual, int ldr, int relu, float* y, catseg_stream_t stream) {
-  if (int e = check_desc(d)) return e;
-  CS_REQUIRE(cs_aligned16(x) && cs_aligned16(w) && cs_aligned16(y), "conv fwd fused: pointers must be 16-byte aligned");
-  IgemmArgs a = fwd_args(d, x, w, bias, y);
-  a.residual = residual; a.ldr = ldr; a.relu = relu;
-  if (d->groups > 1) {
-    CS_REQUIRE(residual == nullptr, "conv fwd fused: residual is not supported with groups");
+    CS_REQUIRE(q->zero_to == 0, "conv fwd: zero_to is not supported with groups");
+    CS_REQUIRE(q->residual == nullptr, "conv fwd fused: residual is not supported with groups");
     group_args(a, d);
     a.bias_bs = d->Cout / d->groups;
-    return launch_igemm<L_NT>(a, d->groups, 1, (hipStream_t)stream);
+    return launch_igemm<L_NT>(a, d->groups, 1, st);
   }
-  return launch_igemm<L_NT>(a, 1, 1, (hipStream_t)stream);
+  if (!q->bn_part) return launch_igemm<L_NT>(a, 1, 1, st);
+  const int ncols = q->zero_to > a.N ? q->zero_to : a.N;
+  const TilePlan pl = plan_tiles(L_NT, a.M, ncols, 1, a.g.rows, true, (long long)a.taps * a.Cred);
+  if ((pl.narrow == 0 || pl.narrow == 1) && cs_claim_bn_partials(a.M, 64 * pl.mi, d->Cout, q->bn_part, q->bn_part_floats, q->tile_rows, q->n_tiles))
+    a.bn_part = q->bn_part;
+  return launch_igemm<L_NT>(a, 1, 1, st, &pl);
 }
 
-extern "C" int catseg_conv2d_bwd_data(const catseg_conv_desc* d, const float* dy, const float* w, float* dx,
-                                      int accumulate, catseg_stream_t stream) {
+int cs_conv_bwd_data_f32(const catseg_conv_bwd_data_desc* q, hipStream_t stream) {
+  const catseg_conv_desc* d = &q->geo;
+  const float *dy = (const float*)q->dy, *w = (const float*)q->w;
+  float* dx = q->dx;
+  const int accumulate = q->accumulate;
   if (int e = check_desc(d)) return e;
   CS_REQUIRE(!d->stem4, "conv bwd_data: not defined for the stem (the image needs no gradient)");
   CS_REQUIRE(cs_aligned16(dy) && cs_aligned16(w) && cs_aligned16(dx), "conv bwd_data: pointers must be 16-byte aligned");
@@ -1190,12 +1170,13 @@ extern "C" int catseg_conv2d_bwd_data(const catseg_conv_desc* d, const float* dy
     const int cig = d->Cin / d->groups, cog = d->Cout / d->groups;
     CS_REQUIRE(d->stride == 1 || d->kh * d->kw <= 32, "conv bwd_data: grouped strided convolution needs <= 32 taps");
     CS_REQUIRE(cog % 4 == 0, "conv bwd_data: Cout/groups must be a multiple of 4");
-    catseg_conv_desc g1 = *d;
-    g1.groups = 1; g1.Cin = cig; g1.Cout = cog;          // per-group geometry; ldx / ldy stay the full pixel strides
+    catseg_conv_bwd_data_desc g1 = *q;
+    g1.geo.groups = 1; g1.geo.Cin = cig; g1.geo.Cout = cog;          // per-group geometry; ldx / ldy stay the full pixel strides
     // run the dense path once per group with shifted base pointers (stride > 1 launches several kernels per call)
-    for (int g = 0; g < d->groups; ++g)
-      if (int e = catseg_conv2d_bwd_data(&g1, dy + (size_t)g * cog, w + (size_t)g * cog * d->kh * d->kw * cig, dx + (size_t)g * cig, accumulate, stream))
-        return e;
+    for (int g = 0; g < d->groups; ++g) {
+      g1.dy = dy + (size_t)g * cog; g1.w = w + (size_t)g * cog * d->kh * d->kw * cig; g1.dx = dx + (size_t)g * cig;
+      if (int e = cs_conv_bwd_data_f32(&g1, stream)) return e;
+    }
     return CATSEG_OK;
   }
   IgemmArgs a = {};
@@ -1291,12 +1272,12 @@ extern "C" int catseg_debug_plan_conv(const catseg_conv_desc* d, int op, int* ou
   return CATSEG_OK;
 }
 
-extern "C" size_t catseg_conv2d_bwd_weight_workspace(const catseg_conv_desc* d) {
+size_t cs_conv_bwd_weight_workspace_f32(const catseg_conv_desc* d) {
   if (check_desc(d)) return 0;
   if (d->groups > 1) {
     catseg_conv_desc g1 = *d;
     g1.groups = 1; g1.Cin = d->Cin / d->groups; g1.Cout = d->Cout / d->groups;
-    return catseg_conv2d_bwd_weight_workspace(&g1);
+    return cs_conv_bwd_weight_workspace_f32(&g1);
   }
   const int splits = wgrad_plan(d).splits;
   const size_t wel = (size_t)d->Cout * (d->stem4 ? d->kh * 32 : d->kh * d->kw * d->Cin);
@@ -1307,28 +1288,31 @@ extern "C" size_t catseg_conv2d_bwd_weight_workspace(const catseg_conv_desc* d) 
   return cs_align_up(bytes, 256);
 }
 
-extern "C" int catseg_conv2d_bwd_weight(const catseg_conv_desc* d, const float* x, const float* dy, float* dw,
-                                        float* dbias, void* workspace, size_t workspace_bytes,
-                                        catseg_stream_t stream) {
+int cs_conv_bwd_weight_f32(const catseg_conv_bwd_weight_desc* q, hipStream_t st) {
+  const catseg_conv_desc* d = &q->geo;
+  const float *x = (const float*)q->x, *dy = (const float*)q->dy;
+  float *dw = q->dw, *dbias = q->dbias;
+  void* workspace = q->workspace;
+  const size_t workspace_bytes = q->workspace_bytes;
   if (int e = check_desc(d)) return e;
   CS_REQUIRE(cs_aligned16(dy) && cs_aligned16(x) && cs_aligned16(dw), "conv bwd_weight: pointers must be 16-byte aligned");
   if (d->groups > 1) {   // grouped: one dense backward-weight per group (shifted bases; the per-group filter banks are contiguous in dw)
     const int cig = d->Cin / d->groups, cog = d->Cout / d->groups;
     CS_REQUIRE(cog % 4 == 0 && cig % 4 == 0, "conv bwd_weight: channels per group must be multiples of 4");
-    catseg_conv_desc g1 = *d;
-    g1.groups = 1; g1.Cin = cig; g1.Cout = cog;
-    for (int g = 0; g < d->groups; ++g)
-      if (int e = catseg_conv2d_bwd_weight(&g1, x + (size_t)g * cig, dy + (size_t)g * cog, dw + (size_t)g * cog * d->kh * d->kw * cig,
-                                           dbias ? dbias + (size_t)g * cog : nullptr, workspace, workspace_bytes, stream))
-        return e;
+    catseg_conv_bwd_weight_desc g1 = *q;
+    g1.geo.groups = 1; g1.geo.Cin = cig; g1.geo.Cout = cog;
+    for (int g = 0; g < d->groups; ++g) {
+      g1.x = x + (size_t)g * cig; g1.dy = dy + (size_t)g * cog; g1.dw = dw + (size_t)g * cog * d->kh * d->kw * cig;
+      g1.dbias = dbias ? dbias + (size_t)g * cog : nullptr;
+      if (int e = cs_conv_bwd_weight_f32(&g1, st)) return e;
+    }
     return CATSEG_OK;
   }
-  const size_t need = catseg_conv2d_bwd_weight_workspace(d);
+  const size_t need = cs_conv_bwd_weight_workspace_f32(d);
   if (workspace_bytes < need || (need && !workspace)) {
     catseg_set_error("conv bwd_weight: workspace %zu < %zu", workspace_bytes, need);
     return CATSEG_EWORKSPACE;
   }
-  hipStream_t st = (hipStream_t)stream;
   const TilePlan pl = wgrad_plan(d);
   int splits = pl.splits;
   const int rps = pl.rps;

@@ -1281,43 +1281,46 @@ extern "C" int catseg_split3_weight_t(const float* w, int O, int taps, int Cin, 
   return CATSEG_OK;
 }
 
-// y = conv(x, w) (+ bias) from pre-split planes: x_planes = catseg_split3 of x (rows = B*H*W, C = Cin),
-// w_planes = catseg_split3 of the OHWI weights viewed as [Cout][kh*kw*Cin]
-extern "C" int catseg_conv2d_fwd_bf16x3(const catseg_conv_desc* d, const void* x_planes, const void* w_planes, const float* bias,
-                                        float* y, int zero_to, catseg_stream_t stream) {
-  CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->Cin % 8 == 0 && d->kh * d->kw <= 32, "conv fwd bf16x3: needs Cin % 8 == 0, <= 32 taps, dense");
-  CS_REQUIRE(cs_aligned16(x_planes) && cs_aligned16(w_planes) && cs_aligned16(y) && zero_to <= d->ldy, "conv fwd bf16x3: alignment");
-  CS_REQUIRE((long long)d->B * d->H * d->W * d->Cin < (1ll << 31) && (long long)d->Cout * d->kh * d->kw * d->Cin < (1ll << 31), "conv fwd bf16x3: 32-bit offsets");
-  B3Args a = b3_fwd_args(d, x_planes, w_planes, bias, y, false);
-  a.zero_to = zero_to;
-  return run_b3(a, (hipStream_t)stream);
+// y = act(conv(x, w) (+ bias) (+ residual)) from pre-split planes.  Planar: x = catseg_split3 of x (rows = B*H*W, C = Cin), w = catseg_split3 of
+// the OHWI weights viewed as [Cout][kh*kw*Cin].  Blocked: x = catseg_split3_blocked of x (Cin % 16 == 0), w = catseg_split3_weight_blocked (for
+// the residual / relu epilogue: of the BatchNorm-folded weights).  bn_part: per-(M-tile, channel) BatchNorm partials from the epilogue.
+// (The three forms keep the names and messages they had as separate entry points.)
+int cs_conv_fwd_b3(const catseg_conv_fwd_desc* q, hipStream_t st) {
+  const catseg_conv_desc* d = &q->geo;
+  const bool blocked = q->operands == CATSEG_OPERANDS_BF16X3_BLOCKED, fused = q->residual || q->relu;
+  const char* who = fused ? "conv fwd fused bf16x3" : blocked ? "conv fwd bf16x3 blocked" : "conv fwd bf16x3";
+  const int cmul = blocked ? 16 : 8;
+  CS_REQUIRE(!d->stem4 && d->groups <= 1 && d->Cin % cmul == 0 && d->kh * d->kw <= 32, "%s: needs Cin %% %d == 0, <= 32 taps, dense", who, cmul);
+  CS_REQUIRE(cs_aligned16(q->x) && cs_aligned16(q->w) && cs_aligned16(q->y) && q->zero_to <= d->ldy && (q->residual == nullptr || q->ldr >= d->Cout) &&
+                 (blocked || !q->bn_part || (q->tile_rows && q->n_tiles)),
+             "%s: %s", who, fused || (!blocked && q->bn_part) ? "bad args" : "alignment");
+  if (!blocked)
+    CS_REQUIRE((long long)d->B * d->H * d->W * d->Cin < (1ll << 31) && (long long)d->Cout * d->kh * d->kw * d->Cin < (1ll << 31), "%s: 32-bit offsets", who);
+  B3Args a = b3_fwd_args(d, q->x, q->w, q->bias, q->y, blocked);
+  a.zero_to = q->zero_to;
+  a.residual = q->residual; a.ldr = q->ldr; a.relu = q->relu;
+  if (q->bn_part != nullptr) {
+    CS_REQUIRE(q->tile_rows && q->n_tiles, "%s: tile_rows / n_tiles", who);
+    // every bf16x3 tile form is 256 rows tall (128 x 256 excepted: never picked by the heuristic, and then nothing is claimed)
+    const bool tall = blocked || pick_b3_tile(q->zero_to > a.N ? q->zero_to : a.N) != 3;
+    if (cs_claim_bn_partials(a.M, 256, d->Cout, tall ? q->bn_part : nullptr, q->bn_part_floats, q->tile_rows, q->n_tiles)) a.bn_part = q->bn_part;
+  }
+  return run_b3(a, st);
 }
 
-// as catseg_conv2d_fwd_bf16x3, plus per-(M-tile, channel) BatchNorm partials from the epilogue (see catseg_conv2d_fwd_bnstats)
-extern "C" int catseg_conv2d_fwd_bf16x3_bnstats(const catseg_conv_desc* d, const void* x_planes, const void* w_planes, const float* bias,
-                                                float* y, int zero_to, float* bn_part, size_t bn_part_floats, int* tile_rows, int* n_tiles,
-                                                catseg_stream_t stream) {
-  CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->Cin % 8 == 0 && d->kh * d->kw <= 32, "conv fwd bf16x3: needs Cin % 8 == 0, <= 32 taps, dense");
-  CS_REQUIRE(cs_aligned16(x_planes) && cs_aligned16(w_planes) && cs_aligned16(y) && zero_to <= d->ldy && tile_rows && n_tiles, "conv fwd bf16x3: bad args");
-  CS_REQUIRE((long long)d->B * d->H * d->W * d->Cin < (1ll << 31) && (long long)d->Cout * d->kh * d->kw * d->Cin < (1ll << 31), "conv fwd bf16x3: 32-bit offsets");
-  B3Args a = b3_fwd_args(d, x_planes, w_planes, bias, y, false);
-  a.zero_to = zero_to;
-  // every bf16x3 tile form is 256 rows tall (128 x 256 excepted: never picked by the heuristic, and then nothing is claimed)
-  if (pick_b3_tile(zero_to > a.N ? zero_to : a.N) == 3) bn_part = nullptr;
-  if (cs_claim_bn_partials(a.M, 256, d->Cout, bn_part, bn_part_floats, tile_rows, n_tiles)) a.bn_part = bn_part;
-  return run_b3(a, (hipStream_t)stream);
-}
-
-// dx (+)= backward-data of a STRIDE-1 convolution from pre-split planes: dy_planes = catseg_split3 of dy (C = Cout rounded up
-// to 8 with zero pad), wt_planes = catseg_split3_weight_t of the weights
-extern "C" int catseg_conv2d_bwd_data_bf16x3(const catseg_conv_desc* d, const void* dy_planes, const void* wt_planes, float* dx,
-                                             int accumulate, catseg_stream_t stream) {
-  CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->stride == 1 && d->kh * d->kw <= 32, "conv bwd_data bf16x3: stride 1, <= 32 taps, dense");
-  CS_REQUIRE(cs_aligned16(dy_planes) && cs_aligned16(wt_planes) && cs_aligned16(dx), "conv bwd_data bf16x3: alignment");
-  const int cop = (d->Cout + 7) & ~7;
-  CS_REQUIRE((long long)d->B * d->Ho * d->Wo * cop < (1ll << 31) && (long long)d->Cin * d->kh * d->kw * cop < (1ll << 31),
-             "conv bwd_data bf16x3: 32-bit offsets");
-  return run_b3(b3_bwd_data_args(d, dy_planes, wt_planes, dx, accumulate, cop, false), (hipStream_t)stream);
+// dx (+)= backward-data of a STRIDE-1 convolution from pre-split planes.  Planar: dy = catseg_split3 of dy (C = Cout rounded up to 8 with zero
+// pad), w = catseg_split3_weight_t of the weights.  Blocked: dy = catseg_split3_blocked of dy (C = Cout; the channel tail up to roundup(Cout, 16)
+// is zero), w = catseg_split3_weight_t_blocked.
+int cs_conv_bwd_data_b3(const catseg_conv_bwd_data_desc* q, hipStream_t st) {
+  const catseg_conv_desc* d = &q->geo;
+  const bool blocked = q->operands == CATSEG_OPERANDS_BF16X3_BLOCKED;
+  const char* who = blocked ? "conv bwd_data bf16x3 blocked" : "conv bwd_data bf16x3";
+  CS_REQUIRE(!d->stem4 && d->groups <= 1 && d->stride == 1 && d->kh * d->kw <= 32, "%s: stride 1, <= 32 taps, dense", who);
+  CS_REQUIRE(cs_aligned16(q->dy) && cs_aligned16(q->w) && cs_aligned16(q->dx), "%s: alignment", who);
+  const int cop = blocked ? (d->Cout + 15) & ~15 : (d->Cout + 7) & ~7;
+  if (!blocked)
+    CS_REQUIRE((long long)d->B * d->Ho * d->Wo * cop < (1ll << 31) && (long long)d->Cin * d->kh * d->kw * cop < (1ll << 31), "%s: 32-bit offsets", who);
+  return run_b3(b3_bwd_data_args(d, q->dy, q->w, q->dx, q->accumulate, cop, blocked), st);
 }
 
 // ---- blocked operand planes (the 256 x 256 register-pipelined kernel reads whole cache lines per LDS-DMA instruction) ----------
@@ -1360,69 +1363,27 @@ extern "C" int catseg_split3_weight_t_blocked(const float* w, int O, int taps, i
   return CATSEG_OK;
 }
 
-// as catseg_conv2d_fwd_bf16x3 / _bnstats with BLOCKED planes: x_planes = catseg_split3_blocked of x (C = Cin, Cin % 16 == 0),
-// w_planes = catseg_split3_weight_blocked.  bn_part may be null (then tile_rows / n_tiles are not touched).
-extern "C" int catseg_conv2d_fwd_bf16x3_blocked(const catseg_conv_desc* d, const void* x_planes, const void* w_planes, const float* bias,
-                                                float* y, int zero_to, float* bn_part, size_t bn_part_floats, int* tile_rows, int* n_tiles,
-                                                catseg_stream_t stream) {
-  CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->Cin % 16 == 0 && d->kh * d->kw <= 32, "conv fwd bf16x3 blocked: needs Cin % 16 == 0, <= 32 taps, dense");
-  CS_REQUIRE(cs_aligned16(x_planes) && cs_aligned16(w_planes) && cs_aligned16(y) && zero_to <= d->ldy, "conv fwd bf16x3 blocked: alignment");
-  B3Args a = b3_fwd_args(d, x_planes, w_planes, bias, y, true);
-  a.zero_to = zero_to;
-  if (bn_part != nullptr) {
-    CS_REQUIRE(tile_rows && n_tiles, "conv fwd bf16x3 blocked: tile_rows / n_tiles");
-    if (cs_claim_bn_partials(a.M, 256, d->Cout, bn_part, bn_part_floats, tile_rows, n_tiles)) a.bn_part = bn_part;
-  }
-  return run_b3(a, (hipStream_t)stream);
-}
-
-// inference: y = act(conv(x, w) + bias (+ residual)) from BLOCKED planes in one kernel (the bf16x3 counterpart of
-// catseg_conv2d_fwd_fused; w_planes = catseg_split3_weight_blocked of the BatchNorm-folded weights)
-extern "C" int catseg_conv2d_fwd_fused_bf16x3_blocked(const catseg_conv_desc* d, const void* x_planes, const void* w_planes, const float* bias,
-                                                      const float* residual, int ldr, int relu, float* y, catseg_stream_t stream) {
-  CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->Cin % 16 == 0 && d->kh * d->kw <= 32, "conv fwd fused bf16x3: needs Cin % 16 == 0, <= 32 taps, dense");
-  CS_REQUIRE(cs_aligned16(x_planes) && cs_aligned16(w_planes) && cs_aligned16(y) && (residual == nullptr || ldr >= d->Cout), "conv fwd fused bf16x3: bad args");
-  B3Args a = b3_fwd_args(d, x_planes, w_planes, bias, y, true);
-  a.residual = residual; a.ldr = ldr; a.relu = relu;
-  return run_b3(a, (hipStream_t)stream);
-}
-
-// as catseg_conv2d_bwd_data_bf16x3 with BLOCKED planes: dy_planes = catseg_split3_blocked of dy (C = Cout; the channel tail up to
-// roundup(Cout, 16) is zero), wt_planes = catseg_split3_weight_t_blocked
-extern "C" int catseg_conv2d_bwd_data_bf16x3_blocked(const catseg_conv_desc* d, const void* dy_planes, const void* wt_planes, float* dx,
-                                                     int accumulate, catseg_stream_t stream) {
-  CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->stride == 1 && d->kh * d->kw <= 32, "conv bwd_data bf16x3 blocked: stride 1, <= 32 taps, dense");
-  CS_REQUIRE(cs_aligned16(dy_planes) && cs_aligned16(wt_planes) && cs_aligned16(dx), "conv bwd_data bf16x3 blocked: alignment");
-  return run_b3(b3_bwd_data_args(d, dy_planes, wt_planes, dx, accumulate, (d->Cout + 15) & ~15, true), (hipStream_t)stream);
-}
-
-// workspace: split-reduction slabs (only when more than one split is planned)
-extern "C" size_t catseg_conv2d_bwd_weight_bf16x3_workspace(const catseg_conv_desc* d) {
-  return d ? cs_wgrad_plan(d).workspace_bytes : 0;
-}
-
 // dw[o][ky][kx][c] = sum_p dy[p][o] x[pix(p,ky,kx)][c] from pre-split planes: dy_planes = catseg_split3 of dy (C = Cout),
 // x_planes = catseg_split3 of x (C = Cin, Cin % 8 == 0)
-extern "C" int catseg_conv2d_bwd_weight_bf16x3(const catseg_conv_desc* d, const void* x_planes, const void* dy_planes, float* dw,
-                                               void* workspace, size_t workspace_bytes, catseg_stream_t stream) {
-  CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->Cin % 8 == 0, "conv bwd_weight bf16x3: dense, Cin % 8 == 0");
-  CS_REQUIRE(cs_aligned16(x_planes) && cs_aligned16(dy_planes) && cs_aligned16(dw), "conv bwd_weight bf16x3: alignment");
+int cs_conv_bwd_weight_b3(const catseg_conv_bwd_weight_desc* q, hipStream_t st) {
+  const catseg_conv_desc* d = &q->geo;
+  CS_REQUIRE(!d->stem4 && d->groups <= 1 && d->Cin % 8 == 0, "conv bwd_weight bf16x3: dense, Cin %% 8 == 0");
+  CS_REQUIRE(cs_aligned16(q->x) && cs_aligned16(q->dy) && cs_aligned16(q->dw), "conv bwd_weight bf16x3: alignment");
   CS_REQUIRE((long long)d->B * d->H * d->W * d->Cin < (1ll << 31), "conv bwd_weight bf16x3: 32-bit offsets");
   const CsWgradPlan pl = cs_wgrad_plan(d);
-  if (workspace_bytes < pl.workspace_bytes || (pl.workspace_bytes && !workspace)) {
-    catseg_set_error("conv bwd_weight bf16x3: workspace %zu < %zu", workspace_bytes, pl.workspace_bytes);
+  if (q->workspace_bytes < pl.workspace_bytes || (pl.workspace_bytes && !q->workspace)) {
+    catseg_set_error("conv bwd_weight bf16x3: workspace %zu < %zu", q->workspace_bytes, pl.workspace_bytes);
     return CATSEG_EWORKSPACE;
   }
-  hipStream_t st = (hipStream_t)stream;
   B3TArgs a = {};
-  const int sp = cs_wgrad_fill(a, d, pl, dw, workspace);
-  a.dy = (const u16*)dy_planes; a.dy_plane = (long long)a.P * a.ldo;
-  a.x = (const u16*)x_planes; a.x_plane = (long long)d->B * d->H * d->W * d->Cin;
+  const int sp = cs_wgrad_fill(a, d, pl, q->dw, q->workspace);
+  a.dy = (const u16*)q->dy; a.dy_plane = (long long)a.P * a.ldo;
+  a.x = (const u16*)q->x; a.x_plane = (long long)d->B * d->H * d->W * d->Cin;
   a.zero = zero_page_b3();
   hipLaunchKernelGGL(igemm_b3t_kernel, dim3(a.tilesM * a.tilesN * sp), dim3(256), 0, st, a);
   CS_LAUNCH_CHECK();
   if (sp > 1) {
-    cs_launch_reduce_slabs((const float*)workspace, dw, (long long)a.M * a.N / 4, sp, 4096, st);
+    cs_launch_reduce_slabs((const float*)q->workspace, q->dw, (long long)a.M * a.N / 4, sp, 4096, st);
     CS_LAUNCH_CHECK();
   }
   return CATSEG_OK;

@@ -1288,88 +1288,62 @@ H2Args h2_bwd_data_args(const catseg_conv_desc* d, const void* dy_planes, const 
 }
 }  // namespace
 
-// y = conv(x, w) (+ bias) from two-plane fp16 operands: x_planes / x_scale = the blocked planes of catseg_split2h of x (C = Cin, Cin % 16 == 0),
-// w_planes / w_scale = catseg_split2h_weight_blocked.  bn_part may be null (then tile_rows / n_tiles are not touched).
-extern "C" int catseg_conv2d_fwd_f16x2_blocked(const catseg_conv_desc* d, const void* x_planes, const void* x_scale, const void* w_planes,
-                                               const void* w_scale, const float* bias, float* y, int zero_to, float* bn_part,
-                                               size_t bn_part_floats, int* tile_rows, int* n_tiles, catseg_stream_t stream) {
-  CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->Cin % 16 == 0 && d->kh * d->kw <= 32, "conv fwd f16x2: needs Cin % 16 == 0, <= 32 taps, dense");
-  CS_REQUIRE(cs_aligned16(x_planes) && cs_aligned16(w_planes) && cs_aligned16(y) && zero_to <= d->ldy && x_scale && w_scale, "conv fwd f16x2: alignment");
-  H2Args a = h2_fwd_args(d, x_planes, x_scale, w_planes, w_scale, bias, y);
-  a.zero_to = zero_to;
-  if (bn_part != nullptr) {
-    CS_REQUIRE(tile_rows && n_tiles, "conv fwd f16x2: tile_rows / n_tiles");
-    if (cs_claim_bn_partials(a.M, 256, d->Cout, bn_part, bn_part_floats, tile_rows, n_tiles)) a.bn_part = bn_part;
+// y = act(conv(x, w) (+ bias) (+ residual)) from two-plane fp16 operands: x / x_scale = the blocked planes of catseg_split2h of x (C = Cin,
+// Cin % 16 == 0), w / w_scale = catseg_split2h_weight_blocked.  bn_part: per-(M-tile, channel) BatchNorm partials from the epilogue.
+int cs_conv_fwd_h2(const catseg_conv_fwd_desc* q, hipStream_t st) {
+  const catseg_conv_desc* d = &q->geo;
+  const bool fused = q->residual || q->relu;
+  const char* who = fused ? "conv fwd fused f16x2" : "conv fwd f16x2";
+  CS_REQUIRE(!d->stem4 && d->groups <= 1 && d->Cin % 16 == 0 && d->kh * d->kw <= 32, "%s: needs Cin %% 16 == 0, <= 32 taps, dense", who);
+  CS_REQUIRE(cs_aligned16(q->x) && cs_aligned16(q->w) && cs_aligned16(q->y) && q->zero_to <= d->ldy && (q->residual == nullptr || q->ldr >= d->Cout) &&
+                 q->x_scale && q->w_scale,
+             "%s: %s", who, fused ? "bad args" : "alignment");
+  H2Args a = h2_fwd_args(d, q->x, q->x_scale, q->w, q->w_scale, q->bias, q->y);
+  a.zero_to = q->zero_to;
+  a.residual = q->residual; a.ldr = q->ldr; a.relu = q->relu;
+  if (q->bn_part != nullptr) {
+    CS_REQUIRE(q->tile_rows && q->n_tiles, "%s: tile_rows / n_tiles", who);
+    if (cs_claim_bn_partials(a.M, 256, d->Cout, q->bn_part, q->bn_part_floats, q->tile_rows, q->n_tiles)) a.bn_part = q->bn_part;
   }
-  return run_h2(a, (hipStream_t)stream);
+  return run_h2(a, st);
 }
 
-// inference: y = act(conv(x, w) + bias (+ residual)) in one kernel (the counterpart of catseg_conv2d_fwd_fused_bf16x3_blocked)
-extern "C" int catseg_conv2d_fwd_fused_f16x2_blocked(const catseg_conv_desc* d, const void* x_planes, const void* x_scale, const void* w_planes,
-                                                     const void* w_scale, const float* bias, const float* residual, int ldr, int relu, float* y,
-                                                     catseg_stream_t stream) {
-  CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->Cin % 16 == 0 && d->kh * d->kw <= 32, "conv fwd fused f16x2: needs Cin % 16 == 0, <= 32 taps, dense");
-  CS_REQUIRE(cs_aligned16(x_planes) && cs_aligned16(w_planes) && cs_aligned16(y) && (residual == nullptr || ldr >= d->Cout) && x_scale && w_scale,
-             "conv fwd fused f16x2: bad args");
-  H2Args a = h2_fwd_args(d, x_planes, x_scale, w_planes, w_scale, bias, y);
-  a.residual = residual; a.ldr = ldr; a.relu = relu;
-  return run_h2(a, (hipStream_t)stream);
+// dx (+)= conv_transpose(dy, w), stride 1: dy / dy_scale = the blocked planes of catseg_split2h of dy (C = Cout; the channel tail up to
+// roundup(Cout, 16) is zero), w / w_scale = catseg_split2h_weight_t_blocked
+int cs_conv_bwd_data_h2(const catseg_conv_bwd_data_desc* q, hipStream_t st) {
+  const catseg_conv_desc* d = &q->geo;
+  CS_REQUIRE(!d->stem4 && d->groups <= 1 && d->stride == 1 && d->kh * d->kw <= 32, "conv bwd_data f16x2: stride 1, <= 32 taps, dense");
+  CS_REQUIRE(cs_aligned16(q->dy) && cs_aligned16(q->w) && cs_aligned16(q->dx) && q->dy_scale && q->w_scale, "conv bwd_data f16x2: alignment");
+  return run_h2(h2_bwd_data_args(d, q->dy, q->dy_scale, q->w, q->w_scale, q->dx, q->accumulate), st);
 }
 
-// dx (+)= conv_transpose(dy, w), stride 1: dy_planes / dy_scale = the blocked planes of catseg_split2h of dy (C = Cout; the channel tail up to
-// roundup(Cout, 16) is zero), wt_planes / wt_scale = catseg_split2h_weight_t_blocked
-extern "C" int catseg_conv2d_bwd_data_f16x2_blocked(const catseg_conv_desc* d, const void* dy_planes, const void* dy_scale, const void* wt_planes,
-                                                    const void* wt_scale, float* dx, int accumulate, catseg_stream_t stream) {
-  CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->stride == 1 && d->kh * d->kw <= 32, "conv bwd_data f16x2: stride 1, <= 32 taps, dense");
-  CS_REQUIRE(cs_aligned16(dy_planes) && cs_aligned16(wt_planes) && cs_aligned16(dx) && dy_scale && wt_scale, "conv bwd_data f16x2: alignment");
-  return run_h2(h2_bwd_data_args(d, dy_planes, dy_scale, wt_planes, wt_scale, dx, accumulate), (hipStream_t)stream);
-}
-
-// workspace: split-reduction slabs (only when more than one split is planned)
-extern "C" size_t catseg_conv2d_bwd_weight_f16x2_workspace(const catseg_conv_desc* d) {
-  return d ? cs_wgrad_plan(d).workspace_bytes : 0;
-}
-
-// dw[o][ky][kx][c] = sum_p dy[p][o] x[pix(p,ky,kx)][c] from two-plane fp16 operands in the PLANAR layout of catseg_split2h:
-// dy_planes / dy_scale of dy (C = Cout), x_planes / x_scale of x (C = Cin, Cin % 8 == 0)
-namespace {
-int run_h2t(const catseg_conv_desc* d, const void* x_planes, const void* x_scale, const void* dy_planes, const void* dy_scale, float* dw,
-            void* workspace, size_t workspace_bytes, int blocked, hipStream_t st) {
-  CS_REQUIRE(d && !d->stem4 && d->groups <= 1 && d->Cin % 8 == 0, "conv bwd_weight f16x2: dense, Cin % 8 == 0");
-  CS_REQUIRE(cs_aligned16(x_planes) && cs_aligned16(dy_planes) && cs_aligned16(dw) && x_scale && dy_scale, "conv bwd_weight f16x2: alignment");
+// dw[o][ky][kx][c] = sum_p dy[p][o] x[pix(p,ky,kx)][c] from two-plane fp16 operands: dy / dy_scale of dy (C = Cout), x / x_scale of x (C = Cin,
+// Cin % 8 == 0), both in the PLANAR layout of catseg_split2h or both in the BLOCKED one ([2][ceil(C / 16)][rows][16], channel tails zero) -- the
+// planes the forward and the backward-data kernel read: one plane set per tensor serves all three directions
+int cs_conv_bwd_weight_h2(const catseg_conv_bwd_weight_desc* q, hipStream_t st) {
+  const catseg_conv_desc* d = &q->geo;
+  const int blocked = q->operands == CATSEG_OPERANDS_F16X2_BLOCKED;
+  CS_REQUIRE(!d->stem4 && d->groups <= 1 && d->Cin % 8 == 0, "conv bwd_weight f16x2: dense, Cin %% 8 == 0");
+  CS_REQUIRE(cs_aligned16(q->x) && cs_aligned16(q->dy) && cs_aligned16(q->dw) && q->x_scale && q->dy_scale, "conv bwd_weight f16x2: alignment");
   const int cpad_x = blocked ? (d->Cin + 15) & ~15 : d->Cin, cpad_o = blocked ? (d->Cout + 15) & ~15 : (d->Cout + 7) & ~7;
   CS_REQUIRE((long long)d->B * d->H * d->W * cpad_x * 4 < (1ll << 32) - 64 && (long long)d->B * d->Ho * d->Wo * cpad_o * 4 < (1ll << 32) - 64,
              "conv bwd_weight f16x2: an operand's two planes must stay below 4 GB");
   const CsWgradPlan pl = cs_wgrad_plan(d);
-  if (workspace_bytes < pl.workspace_bytes || (pl.workspace_bytes && !workspace)) {
-    catseg_set_error("conv bwd_weight f16x2: workspace %zu < %zu", workspace_bytes, pl.workspace_bytes);
+  if (q->workspace_bytes < pl.workspace_bytes || (pl.workspace_bytes && !q->workspace)) {
+    catseg_set_error("conv bwd_weight f16x2: workspace %zu < %zu", q->workspace_bytes, pl.workspace_bytes);
     return CATSEG_EWORKSPACE;
   }
   H2TArgs a = {};
-  const int sp = cs_wgrad_fill(a, d, pl, dw, workspace);
-  a.dy = (const u16*)dy_planes; a.dy_plane = (long long)a.P * cpad_o;
-  a.x = (const u16*)x_planes; a.x_rows = (long long)d->B * d->H * d->W; a.x_plane = a.x_rows * cpad_x;
+  const int sp = cs_wgrad_fill(a, d, pl, q->dw, q->workspace);
+  a.dy = (const u16*)q->dy; a.dy_plane = (long long)a.P * cpad_o;
+  a.x = (const u16*)q->x; a.x_rows = (long long)d->B * d->H * d->W; a.x_plane = a.x_rows * cpad_x;
   a.blocked = blocked;
-  a.edy = (const int*)dy_scale + 1; a.ex = (const int*)x_scale + 1;
+  a.edy = (const int*)q->dy_scale + 1; a.ex = (const int*)q->x_scale + 1;
   hipLaunchKernelGGL(igemm_h2t_kernel, dim3(a.tilesM * a.tilesN * sp), dim3(256), 0, st, a);
   CS_LAUNCH_CHECK();
   if (sp > 1) {
-    cs_launch_reduce_slabs((const float*)workspace, dw, (long long)a.M * a.N / 4, sp, 4096, st);
+    cs_launch_reduce_slabs((const float*)q->workspace, q->dw, (long long)a.M * a.N / 4, sp, 4096, st);
     CS_LAUNCH_CHECK();
   }
   return CATSEG_OK;
-}
-}  // namespace
-
-extern "C" int catseg_conv2d_bwd_weight_f16x2(const catseg_conv_desc* d, const void* x_planes, const void* x_scale, const void* dy_planes,
-                                              const void* dy_scale, float* dw, void* workspace, size_t workspace_bytes, catseg_stream_t stream) {
-  return run_h2t(d, x_planes, x_scale, dy_planes, dy_scale, dw, workspace, workspace_bytes, 0, (hipStream_t)stream);
-}
-
-// the same from the BLOCKED planes of catseg_split2h ([2][ceil(C / 16)][rows][16], channel tails zero) -- the planes the forward and the
-// backward-data kernel read: one plane set per tensor serves all three directions
-extern "C" int catseg_conv2d_bwd_weight_f16x2_blocked(const catseg_conv_desc* d, const void* x_planes, const void* x_scale, const void* dy_planes,
-                                                      const void* dy_scale, float* dw, void* workspace, size_t workspace_bytes,
-                                                      catseg_stream_t stream) {
-  return run_h2t(d, x_planes, x_scale, dy_planes, dy_scale, dw, workspace, workspace_bytes, 1, (hipStream_t)stream);
 }

@@ -753,7 +753,7 @@ extern "C" int catseg_bn_train_stats(const float* y, long long rows, int C, int 
 }
 
 // the second half of catseg_bn_train_stats on its own: merges [n_blocks][3][C] partials (K, s1, s2) over row blocks of
-// rows_per_block rows (the last one shorter) -- written by catseg_conv2d_fwd_bnstats / _bf16x3_bnstats
+// rows_per_block rows (the last one shorter) -- written by catseg_conv2d_fwd given bn_part
 extern "C" int catseg_bn_finalize(const float* partials, int n_blocks, long long rows_per_block, long long rows, int C, const float* gamma,
                                   float eps, float momentum, float* running_mean, float* running_var, float* stats_out, float* scale,
                                   catseg_stream_t stream) {

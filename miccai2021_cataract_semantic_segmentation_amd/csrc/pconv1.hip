@@ -923,7 +923,7 @@ extern "C" int catseg_pconv1_prep_batch(const float* flat, int n, const void* en
 }
 
 // y[M][N] (+)= x[M][K] . B^T (+ bias) with B = the weight image of (N, K); x_rec: the amax record of x (its producer's); w_rec: the
-// image's {amax bits, exponent}.  bn_part may be null; otherwise per-(256-row tile, channel) BatchNorm partials as catseg_conv2d_fwd_bnstats.
+// image's {amax bits, exponent}.  bn_part may be null; otherwise per-(256-row tile, channel) BatchNorm partials as catseg_conv2d_fwd given bn_part.
 extern "C" int catseg_pconv1(long long M, int N, int K, const float* x, int ldx, const void* x_rec, const void* wimg, const void* w_rec,
                              const float* bias, float* y, int ldy, int accumulate, float* bn_part, size_t bn_part_floats, int* tile_rows,
                              int* n_tiles, catseg_stream_t stream) {
@@ -1083,7 +1083,7 @@ extern "C" int catseg_gconv_entries(const catseg_conv_desc* d, int backward_data
   return s * s;
 }
 
-// y = conv(x, w) (+ bias) -- forward gather launch; wimg = forward image, BatchNorm partials as catseg_conv2d_fwd_bnstats
+// y = conv(x, w) (+ bias) -- forward gather launch; wimg = forward image, BatchNorm partials as catseg_conv2d_fwd given bn_part
 extern "C" int catseg_gconv_fwd(const catseg_conv_desc* d, const float* x, const void* x_rec, const void* wimg, const void* w_rec,
                                 const float* bias, float* y, float* bn_part, size_t bn_part_floats, int* tile_rows, int* n_tiles,
                                 catseg_stream_t stream) {

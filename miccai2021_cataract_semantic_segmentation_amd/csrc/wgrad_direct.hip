@@ -194,7 +194,7 @@ extern "C" int catseg_debug_set_wgrad_direct(int on) {
   return CATSEG_OK;
 }
 
-// used by catseg_conv2d_bwd_weight(_workspace) in igemm.hip
+// used by cs_conv_bwd_weight_f32 / cs_conv_bwd_weight_workspace_f32 in igemm.hip
 size_t wgrad_direct_workspace(const catseg_conv_desc* d) {
   const DirectPlan p = direct_plan(d);
   return p.kind ? (size_t)p.splits * d->Cout * 9 * d->Cin * 4 : 0;

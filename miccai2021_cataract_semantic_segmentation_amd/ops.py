@@ -13,7 +13,8 @@ import torch
 
 from . import _lib
 from . import plan as _plan
-from ._lib import BnApplyDesc, BnBackwardDesc, ConvDesc, check, lib, ptr, stream
+from ._lib import (BnApplyDesc, BnBackwardDesc, ConvBwdDataDesc, ConvBwdWeightDesc, ConvDesc, ConvFwdDesc, OPERANDS_BF16X3, OPERANDS_BF16X3_BLOCKED,
+                   OPERANDS_F16X2, OPERANDS_F16X2_BLOCKED, OPERANDS_F32, check, lib, ptr, stream)
 
 _ws = {}
 
@@ -1035,39 +1036,27 @@ def conv_fwd(x, w_ptr_tensor, bias, Cout, kh, kw, stride=1, pad=0, dil=1, out=No
                                        part.numel() if part is not None else 0, ctypes.byref(tr) if bn_stats else None,
                                        ctypes.byref(nt) if bn_stats else None, stream()))
         drop_amax(out)
-    elif route.kind == "h2":
-        d = make_desc(x.shape, Cin, Cout, ld_of(out), kh, kw, stride, pad, dil)
-        with _Timed("split3", 0.0):
-            xp, xsc = _split3_cached(x, "h2", both=train and not H2T_BLOCKED, keep=train)
-            wp, wsc = split2h_weight_blocked(w_ptr_tensor)
-        with _Timed("fwd_h2", flops):
-            check(lib.catseg_conv2d_fwd_f16x2_blocked(ctypes.byref(d), ptr(xp), ptr(xsc), ptr(wp), ptr(wsc), ptr(bias), ptr(out), zero_to,
-                                                      ptr(part), part.numel() if part is not None else 0,
-                                                      ctypes.byref(tr) if bn_stats else None, ctypes.byref(nt) if bn_stats else None, stream()))
-    elif route.kind == "b3":
-        d = make_desc(x.shape, Cin, Cout, ld_of(out), kh, kw, stride, pad, dil)
-        blk = route.blocked
-        with _Timed("split3", 0.0):
-            xp = _split3_cached(x, "blk" if blk else "planar", both=blk and train, keep=train)
-            wp = split3_weight_blocked(w_ptr_tensor) if blk else split3_weight(w_ptr_tensor)
-        with _Timed("fwd_b3", flops):
-            if blk:
-                check(lib.catseg_conv2d_fwd_bf16x3_blocked(ctypes.byref(d), ptr(xp), ptr(wp), ptr(bias), ptr(out), zero_to, ptr(part),
-                                                           part.numel() if part is not None else 0,
-                                                           ctypes.byref(tr) if bn_stats else None, ctypes.byref(nt) if bn_stats else None, stream()))
-            elif bn_stats:
-                check(lib.catseg_conv2d_fwd_bf16x3_bnstats(ctypes.byref(d), ptr(xp), ptr(wp), ptr(bias), ptr(out), zero_to, ptr(part),
-                                                           part.numel(), ctypes.byref(tr), ctypes.byref(nt), stream()))
-            else:
-                check(lib.catseg_conv2d_fwd_bf16x3(ctypes.byref(d), ptr(xp), ptr(wp), ptr(bias), ptr(out), zero_to, stream()))
     else:
-        d = make_desc(x.shape, ld_of(x), Cout, ld_of(out), kh, kw, stride, pad, dil, stem4, groups)
-        with _Timed("fwd", flops):
-            if bn_stats:
-                check(lib.catseg_conv2d_fwd_bnstats(ctypes.byref(d), ptr(x), ptr(w_ptr_tensor), ptr(bias), ptr(out), zero_to, ptr(part),
-                                                    part.numel(), ctypes.byref(tr), ctypes.byref(nt), stream()))
-            else:
-                check(lib.catseg_conv2d_fwd(ctypes.byref(d), ptr(x), ptr(w_ptr_tensor), ptr(bias), ptr(out), zero_to, stream()))
+        if route.kind == "h2":
+            kind, operands = "fwd_h2", OPERANDS_F16X2_BLOCKED
+            with _Timed("split3", 0.0):
+                xp, xsc = _split3_cached(x, "h2", both=train and not H2T_BLOCKED, keep=train)
+                wp, wsc = split2h_weight_blocked(w_ptr_tensor)
+        elif route.kind == "b3":
+            blk = route.blocked
+            kind, operands, xsc, wsc = "fwd_b3", OPERANDS_BF16X3_BLOCKED if blk else OPERANDS_BF16X3, None, None
+            with _Timed("split3", 0.0):
+                xp = _split3_cached(x, "blk" if blk else "planar", both=blk and train, keep=train)
+                wp = split3_weight_blocked(w_ptr_tensor) if blk else split3_weight(w_ptr_tensor)
+        else:
+            kind, operands, xp, xsc, wp, wsc = "fwd", OPERANDS_F32, x, None, w_ptr_tensor, None
+        if operands == OPERANDS_F32:
+            d = make_desc(x.shape, ld_of(x), Cout, ld_of(out), kh, kw, stride, pad, dil, stem4, groups)
+        else:
+            d = make_desc(x.shape, Cin, Cout, ld_of(out), kh, kw, stride, pad, dil)
+        stats = dict(bn_part=part, bn_part_floats=part.numel(), tile_rows=ctypes.addressof(tr), n_tiles=ctypes.addressof(nt)) if bn_stats else {}
+        with _Timed(kind, flops):
+            _conv_call(ConvFwdDesc, d, operands, x=xp, x_scale=xsc, w=wp, w_scale=wsc, bias=bias, y=out, zero_to=zero_to, **stats)
     res = (out, (part, nt.value, tr.value) if tr.value > 0 else None) if bn_stats else out
     return (res, None) if with_yrec else res
 
@@ -1137,27 +1126,26 @@ def conv_bwd_data(dy, w, xshape, kh, kw, stride=1, pad=0, dil=1, out=None, accum
         with _Timed("dgrad_s2p", flops):
             check(lib.catseg_gconv_bwd_data(ctypes.byref(d), ptr(dy), ptr(amax_of(dy)), ptr(wimg[0]), ptr(wimg[1]), ptr(out),
                                             1 if accumulate else 0, stream()))
-    elif route.kind == "h2":
-        d = make_desc(xshape, ld_of(out), Cout, (Cout + 7) // 8 * 8, kh, kw, stride, pad, dil)
-        with _Timed("split3", 0.0):
-            dyp, dysc = _split3_cached_dy(dy, "h2")
-            wtp, wtsc = split2h_weight_t_blocked(w)
-        with _Timed("dgrad_h2", flops):
-            check(lib.catseg_conv2d_bwd_data_f16x2_blocked(ctypes.byref(d), ptr(dyp), ptr(dysc), ptr(wtp), ptr(wtsc), ptr(out),
-                                                           1 if accumulate else 0, stream()))
-    elif route.kind == "b3":
-        d = make_desc(xshape, ld_of(out), Cout, (Cout + 7) // 8 * 8, kh, kw, stride, pad, dil)
-        blk = route.blocked
-        with _Timed("split3", 0.0):
-            dyp = _split3_cached_dy(dy, "blk" if blk else "planar")
-            wtp = split3_weight_t_blocked(w) if blk else split3_weight_t(w)
-        with _Timed("dgrad_b3", flops):
-            fn = lib.catseg_conv2d_bwd_data_bf16x3_blocked if blk else lib.catseg_conv2d_bwd_data_bf16x3
-            check(fn(ctypes.byref(d), ptr(dyp), ptr(wtp), ptr(out), 1 if accumulate else 0, stream()))
     else:
-        d = make_desc(xshape, ld_of(out), Cout, ld_of(dy), kh, kw, stride, pad, dil, False, groups)
-        with _Timed("dgrad", flops):
-            check(lib.catseg_conv2d_bwd_data(ctypes.byref(d), ptr(dy), ptr(w), ptr(out), 1 if accumulate else 0, stream()))
+        if route.kind == "h2":
+            kind, operands = "dgrad_h2", OPERANDS_F16X2_BLOCKED
+            with _Timed("split3", 0.0):
+                dyp, dysc = _split3_cached_dy(dy, "h2")
+                wtp, wtsc = split2h_weight_t_blocked(w)
+        elif route.kind == "b3":
+            blk = route.blocked
+            kind, operands, dysc, wtsc = "dgrad_b3", OPERANDS_BF16X3_BLOCKED if blk else OPERANDS_BF16X3, None, None
+            with _Timed("split3", 0.0):
+                dyp = _split3_cached_dy(dy, "blk" if blk else "planar")
+                wtp = split3_weight_t_blocked(w) if blk else split3_weight_t(w)
+        else:
+            kind, operands, dyp, dysc, wtp, wtsc = "dgrad", OPERANDS_F32, dy, None, w, None
+        if operands == OPERANDS_F32:
+            d = make_desc(xshape, ld_of(out), Cout, ld_of(dy), kh, kw, stride, pad, dil, False, groups)
+        else:
+            d = make_desc(xshape, ld_of(out), Cout, (Cout + 7) // 8 * 8, kh, kw, stride, pad, dil)
+        with _Timed(kind, flops):
+            _conv_call(ConvBwdDataDesc, d, operands, dy=dyp, dy_scale=dysc, w=wtp, w_scale=wtsc, dx=out, accumulate=1 if accumulate else 0)
     return (out, None) if with_pre else out
 
 
@@ -1199,29 +1187,27 @@ def conv_bwd_weight(x, dy, dw, dbias, kh, kw, stride=1, pad=0, dil=1, stem4=Fals
             check(lib.catseg_gconv_bwd_weight(ctypes.byref(d), ptr(dy), ptr(amax_of(dy)), ptr(x), ptr(amax_of(x)), ptr(dw), ptr(ws), need, stream()))
     elif route.kind in ("h2", "b3"):
         d = make_desc(x.shape, Cin, Cout, (Cout + 7) // 8 * 8, kh, kw, stride, pad, dil)
-        ws = workspace(lib.catseg_conv2d_bwd_weight_bf16x3_workspace(ctypes.byref(d)) + 256 * Cout * 4, x.device)
         dgrad_blk = dgrad_route(L).blocked     # the layer's backward-data will read BLOCKED planes of dy: this split pass writes them as well
         if route.kind == "h2":
             # two fp16 planes per operand (csrc/igemm_f16x2.hip; each operand's planes behind one 32-bit-offset buffer resource); dy's
             # blocked planes for this layer's backward-data from the same pass
-            ws = workspace(lib.catseg_conv2d_bwd_weight_f16x2_workspace(ctypes.byref(d)) + 256 * Cout * 4, x.device)
+            kind, operands = "wgrad_h2", OPERANDS_F16X2_BLOCKED if H2T_BLOCKED else OPERANDS_F16X2
+            ws = _wgrad_workspace(d, operands, 256 * Cout * 4, x.device)
             with _Timed("split3", 0.0):
                 xp, xsc, dyp, dysc = _wgrad_h2_planes(x, dy, dgrad_blk)
-            with _Timed("wgrad_h2", flops):
-                fn = lib.catseg_conv2d_bwd_weight_f16x2_blocked if H2T_BLOCKED else lib.catseg_conv2d_bwd_weight_f16x2
-                check(fn(ctypes.byref(d), ptr(xp), ptr(xsc), ptr(dyp), ptr(dysc), ptr(dw), ptr(ws), ws.numel(), stream()))
         else:
+            kind, operands, xsc, dysc = "wgrad_b3", OPERANDS_BF16X3, None, None
+            ws = _wgrad_workspace(d, operands, 256 * Cout * 4, x.device)
             with _Timed("split3", 0.0):
                 xp = _split3_cached(x, "planar")
                 dyp = _split3_cached_dy(dy, "planar", both=dgrad_blk)
-            with _Timed("wgrad_b3", flops):
-                check(lib.catseg_conv2d_bwd_weight_bf16x3(ctypes.byref(d), ptr(xp), ptr(dyp), ptr(dw), ptr(ws), ws.numel(), stream()))
+        with _Timed(kind, flops):
+            _conv_call(ConvBwdWeightDesc, d, operands, x=xp, x_scale=xsc, dy=dyp, dy_scale=dysc, dw=dw, workspace=ws, workspace_bytes=ws.numel())
     else:
         d = make_desc(x.shape, ld_of(x), Cout, ld_of(dy), kh, kw, stride, pad, dil, stem4, groups)
-        need = lib.catseg_conv2d_bwd_weight_workspace(ctypes.byref(d))
-        ws = workspace(need, x.device)
+        ws = _wgrad_workspace(d, OPERANDS_F32, 0, x.device)
         with _Timed("wgrad", flops):
-            check(lib.catseg_conv2d_bwd_weight(ctypes.byref(d), ptr(x), ptr(dy), ptr(dw), ptr(dbias), ptr(ws), ws.numel(), stream()))
+            _conv_call(ConvBwdWeightDesc, d, OPERANDS_F32, x=x, dy=dy, dw=dw, dbias=dbias, workspace=ws, workspace_bytes=ws.numel())
         return dw
     if dbias is not None:
         check(lib.catseg_bias_grad(ptr(dy), ld_of(dy), rows_of(dy), Cout, ptr(dbias), ptr(ws), ws.numel(), stream()))
@@ -1349,6 +1335,21 @@ def _relu_source(z, relu, beta):
     if mask is not None:
         return dict(relu=1, mask=ptr(mask))
     return dict(relu=1 if relu else 0, z=ptr(z), ldz=_ld(z), beta=ptr(beta))
+
+
+_CONV_ENTRY = {ConvFwdDesc: "catseg_conv2d_fwd", ConvBwdDataDesc: "catseg_conv2d_bwd_data", ConvBwdWeightDesc: "catseg_conv2d_bwd_weight"}
+
+
+def _conv_call(Desc, geo, operands, **fields):
+    """one catseg_conv2d_fwd / _bwd_data / _bwd_weight call (by the descriptor type): tensors in `fields` go in as their pointers, a field left
+    out is NULL / 0"""
+    d = Desc(geo=geo, operands=operands, **{k: v if isinstance(v, int) else ptr(v) for k, v in fields.items()})
+    check(getattr(lib, _CONV_ENTRY[Desc])(ctypes.byref(d), stream()))
+
+
+def _wgrad_workspace(geo, operands, extra, device):
+    """the workspace of a backward-weight call + `extra` bytes (the bias-gradient partials of catseg_bias_grad behind a plane kernel)"""
+    return workspace(lib.catseg_conv2d_bwd_weight_workspace(ctypes.byref(geo), operands) + extra, device)
 
 
 def _bn_backward_call(dz, y, stats, gamma, dgamma, dbeta, passes, ws_bytes=None, **fields):
@@ -1600,12 +1601,12 @@ def conv_bwd_weight_h2(x, dyp, dysc, Cout, dw, kh, kw, stride, pad, dil):
     """backward-weight from the blocked planes of dy (bn_backward_h2) and of x (kept from the forward pass, or split now)"""
     Cin = x.shape[-1]
     d = make_desc(x.shape, Cin, Cout, (Cout + 7) // 8 * 8, kh, kw, stride, pad, dil)
-    wsb = workspace(lib.catseg_conv2d_bwd_weight_f16x2_workspace(ctypes.byref(d)) + 256 * Cout * 4, x.device)
+    wsb = _wgrad_workspace(d, OPERANDS_F16X2_BLOCKED, 256 * Cout * 4, x.device)
     with _Timed("split3", 0.0):
         xp, xsc = _split3_cached(x, "h2")
     with _Timed("wgrad_h2", 2.0 * d.B * d.Ho * d.Wo * Cout * Cin * kh * kw):
-        check(lib.catseg_conv2d_bwd_weight_f16x2_blocked(ctypes.byref(d), ptr(xp), ptr(xsc), ptr(dyp), ptr(dysc), ptr(dw), ptr(wsb), wsb.numel(),
-                                                         stream()))
+        _conv_call(ConvBwdWeightDesc, d, OPERANDS_F16X2_BLOCKED, x=xp, x_scale=xsc, dy=dyp, dy_scale=dysc, dw=dw, workspace=wsb,
+                   workspace_bytes=wsb.numel())
     return dw
 
 
@@ -1617,8 +1618,7 @@ def conv_bwd_data_h2(dyp, dysc, w, xshape, Cout, kh, kw, pad, dil, out, accumula
     with _Timed("split3", 0.0):
         wtp, wtsc = split2h_weight_t_blocked(w)
     with _Timed("dgrad_h2", 2.0 * d.B * d.Ho * d.Wo * Cout * Cin * kh * kw):
-        check(lib.catseg_conv2d_bwd_data_f16x2_blocked(ctypes.byref(d), ptr(dyp), ptr(dysc), ptr(wtp), ptr(wtsc), ptr(out),
-                                                       1 if accumulate else 0, stream()))
+        _conv_call(ConvBwdDataDesc, d, OPERANDS_F16X2_BLOCKED, dy=dyp, dy_scale=dysc, w=wtp, w_scale=wtsc, dx=out, accumulate=1 if accumulate else 0)
     return out
 
 
@@ -2272,6 +2272,7 @@ def conv_fwd_fused(x, w, bias, residual, relu, Cout, kh, kw, stride=1, pad=0, di
     if out is None:
         out = new_act(B, Ho, Wo, Cout, x.device)
     flops = 2.0 * B * Ho * Wo * Cout * (3 if stem4 else Cin // groups) * kh * kw
+    epilogue = dict(bias=bias, ldr=ld_of(residual) if residual is not None else 0, relu=1 if relu else 0)
     if (_fwd_gemm_ok(Layer(x.shape, Cout, kh, kw, stride, pad, dil, groups, stem4=stem4, w4d=w.numel() == Cout * kh * kw * Cin))
             and _b3_blocked_shape(Cout, Cin) and 6 * Cout * kh * kw * Cin < (1 << 32) - 64):
         # the bf16x3 kernel with the fused epilogue; the batch is cut so that the three blocked planes of a piece stay below 4 GB
@@ -2284,31 +2285,26 @@ def conv_fwd_fused(x, w, bias, residual, relu, Cout, kh, kw, stride=1, pad=0, di
                 xs, os_ = (x, out) if nb == B else (x[b0:b0 + nb], out[b0:b0 + nb])    # (x itself: the split-plane cache is keyed by identity)
                 rs = residual[b0:b0 + nb] if residual is not None else None
                 d = make_desc(xs.shape, Cin, Cout, ld_of(out), kh, kw, stride, pad, dil)
-                if _h2():
-                    with _Timed("split3", 0.0):
+                with _Timed("split3", 0.0):      # (w: OHWI weights, 4-D or the flat buffer catseg_fold_bn writes)
+                    if _h2():
+                        kind, operands = "fwd_h2", OPERANDS_F16X2_BLOCKED
                         xp, xsc = _split3_cached(xs, "h2") if nb == B else split2h_blocked(xs)
-                        if wp is None:      # (w: OHWI weights, 4-D or the flat buffer catseg_fold_bn writes)
+                        if wp is None:
                             wp = torch.empty((2, kh * kw * Cin // 16, Cout, 16), dtype=torch.int16, device=w.device)
                             wsc = torch.empty(2, dtype=torch.int32, device=w.device)
                             check(lib.catseg_split2h_weight_blocked(ptr(w), Cout, kh * kw, Cin, ptr(wp), ptr(wsc), stream()))
-                    with _Timed("fwd_h2", flops * xs.shape[0] / B):
-                        check(lib.catseg_conv2d_fwd_fused_f16x2_blocked(ctypes.byref(d), ptr(xp), ptr(xsc), ptr(wp), ptr(wsc), ptr(bias), ptr(rs),
-                                                                        ld_of(residual) if residual is not None else 0, 1 if relu else 0,
-                                                                        ptr(os_), stream()))
-                    continue
-                with _Timed("split3", 0.0):
-                    xp = _split3_cached(xs, "blk") if nb == B else split3_blocked(xs)[0]
-                    if wp is None:      # (w: OHWI weights, 4-D or the flat buffer catseg_fold_bn writes)
-                        wp = torch.empty((3, kh * kw * Cin // 16, Cout, 16), dtype=torch.int16, device=w.device)
-                        check(lib.catseg_split3_weight_blocked(ptr(w), Cout, kh * kw, Cin, ptr(wp), stream()))
-                with _Timed("fwd_b3", flops * xs.shape[0] / B):
-                    check(lib.catseg_conv2d_fwd_fused_bf16x3_blocked(ctypes.byref(d), ptr(xp), ptr(wp), ptr(bias), ptr(rs),
-                                                                     ld_of(residual) if residual is not None else 0, 1 if relu else 0, ptr(os_), stream()))
+                    else:
+                        kind, operands, xsc, wsc = "fwd_b3", OPERANDS_BF16X3_BLOCKED, None, None
+                        xp = _split3_cached(xs, "blk") if nb == B else split3_blocked(xs)[0]
+                        if wp is None:
+                            wp = torch.empty((3, kh * kw * Cin // 16, Cout, 16), dtype=torch.int16, device=w.device)
+                            check(lib.catseg_split3_weight_blocked(ptr(w), Cout, kh * kw, Cin, ptr(wp), stream()))
+                with _Timed(kind, flops * xs.shape[0] / B):
+                    _conv_call(ConvFwdDesc, d, operands, x=xp, x_scale=xsc, w=wp, w_scale=wsc, residual=rs, y=os_, **epilogue)
             return out
     d = make_desc(x.shape, ld_of(x), Cout, ld_of(out), kh, kw, stride, pad, dil, stem4, groups)
     with _Timed("fwd", flops):
-        check(lib.catseg_conv2d_fwd_fused(ctypes.byref(d), ptr(x), ptr(w), ptr(bias), ptr(residual),
-                                          ld_of(residual) if residual is not None else 0, 1 if relu else 0, ptr(out), stream()))
+        _conv_call(ConvFwdDesc, d, OPERANDS_F32, x=x, w=w, residual=residual, y=out, **epilogue)
     return out
 
 
@@ -2451,48 +2447,29 @@ def split3_weight_t(w):
     return planes
 
 
-def conv_fwd_b3(xshape, xp, wp, bias, Cout, kh, kw, stride=1, pad=0, dil=1, out=None, zero_to=0):
+def conv_fwd_b3(xshape, xp, wp, bias, Cout, kh, kw, stride=1, pad=0, dil=1, out=None, zero_to=0, blocked=False):
+    """forward from pre-split bf16x3 planes (tests and tools): split3 / split3_weight, or with blocked=True split3_blocked /
+    split3_weight_blocked (always the 256 x 256 register-pipelined kernel)"""
     B, H, W, Cin = xshape
     Ho, Wo = conv_out_size(H, kh, stride, pad, dil), conv_out_size(W, kw, stride, pad, dil)
     if out is None:
         out = new_act(B, Ho, Wo, Cout, xp.device, ld=max(zero_to, (Cout + 3) // 4 * 4))
     d = make_desc(xshape, Cin, Cout, ld_of(out), kh, kw, stride, pad, dil)
     with _Timed("fwd", 2.0 * B * Ho * Wo * Cout * Cin * kh * kw):
-        check(lib.catseg_conv2d_fwd_bf16x3(ctypes.byref(d), ptr(xp), ptr(wp), ptr(bias), ptr(out), zero_to, stream()))
+        _conv_call(ConvFwdDesc, d, OPERANDS_BF16X3_BLOCKED if blocked else OPERANDS_BF16X3, x=xp, w=wp, bias=bias, y=out, zero_to=zero_to)
     return out
 
 
-def conv_bwd_data_b3(dyp, wtp, xshape, Cout, kh, kw, stride=1, pad=0, dil=1, out=None, accumulate=False):
+def conv_bwd_data_b3(dyp, wtp, xshape, Cout, kh, kw, stride=1, pad=0, dil=1, out=None, accumulate=False, blocked=False):
+    """backward-data from pre-split bf16x3 planes (tests and tools): split3 / split3_weight_t, or their blocked twins"""
     B, H, W, Cin = xshape
     if out is None:
         out = new_act(B, H, W, Cin, dyp.device)
         accumulate = False
     d = make_desc(xshape, ld_of(out), Cout, (Cout + 7) // 8 * 8, kh, kw, stride, pad, dil)
     with _Timed("dgrad", 2.0 * B * d.Ho * d.Wo * Cout * Cin * kh * kw):
-        check(lib.catseg_conv2d_bwd_data_bf16x3(ctypes.byref(d), ptr(dyp), ptr(wtp), ptr(out), 1 if accumulate else 0, stream()))
-    return out
-
-
-def conv_fwd_b3_blocked(xshape, xblk, wblk, bias, Cout, kh, kw, stride=1, pad=0, dil=1, out=None, zero_to=0):
-    """forward from BLOCKED planes (split3_blocked / split3_weight_blocked): always the 256 x 256 register-pipelined kernel"""
-    B, H, W, Cin = xshape
-    Ho, Wo = conv_out_size(H, kh, stride, pad, dil), conv_out_size(W, kw, stride, pad, dil)
-    if out is None:
-        out = new_act(B, Ho, Wo, Cout, xblk.device, ld=max(zero_to, (Cout + 3) // 4 * 4))
-    d = make_desc(xshape, Cin, Cout, ld_of(out), kh, kw, stride, pad, dil)
-    with _Timed("fwd", 2.0 * B * Ho * Wo * Cout * Cin * kh * kw):
-        check(lib.catseg_conv2d_fwd_bf16x3_blocked(ctypes.byref(d), ptr(xblk), ptr(wblk), ptr(bias), ptr(out), zero_to, None, 0, None, None, stream()))
-    return out
-
-
-def conv_bwd_data_b3_blocked(dyblk, wtblk, xshape, Cout, kh, kw, stride=1, pad=0, dil=1, out=None, accumulate=False):
-    B, H, W, Cin = xshape
-    if out is None:
-        out = new_act(B, H, W, Cin, dyblk.device)
-        accumulate = False
-    d = make_desc(xshape, ld_of(out), Cout, (Cout + 7) // 8 * 8, kh, kw, stride, pad, dil)
-    with _Timed("dgrad", 2.0 * B * d.Ho * d.Wo * Cout * Cin * kh * kw):
-        check(lib.catseg_conv2d_bwd_data_bf16x3_blocked(ctypes.byref(d), ptr(dyblk), ptr(wtblk), ptr(out), 1 if accumulate else 0, stream()))
+        _conv_call(ConvBwdDataDesc, d, OPERANDS_BF16X3_BLOCKED if blocked else OPERANDS_BF16X3, dy=dyp, w=wtp, dx=out,
+                   accumulate=1 if accumulate else 0)
     return out
 
 

@@ -40,8 +40,27 @@ static catseg_conv_desc desc(int B, int H, int W, int Cin, int Cout, int k, int 
   return c;
 }
 
+// the convolution entry points take descriptors: one call per line below through these (a field not named is NULL / 0)
+enum { F32 = CATSEG_OPERANDS_F32, B3 = CATSEG_OPERANDS_BF16X3, B3B = CATSEG_OPERANDS_BF16X3_BLOCKED, H2P = CATSEG_OPERANDS_F16X2,
+       H2B = CATSEG_OPERANDS_F16X2_BLOCKED };
+static int fwd(int form, const catseg_conv_desc& g, const void* x, const void* x_scale, const void* w, const void* w_scale, const float* bias, float* y,
+               int zero_to, float* bn_part = nullptr, size_t bn_part_floats = 0, int* tile_rows = nullptr, int* n_tiles = nullptr,
+               const float* residual = nullptr, int ldr = 0, int relu = 0) {
+  const catseg_conv_fwd_desc q = {g, form, x, x_scale, w, w_scale, bias, y, zero_to, bn_part, bn_part_floats, tile_rows, n_tiles, residual, ldr, relu};
+  return catseg_conv2d_fwd(&q, nullptr);
+}
+static int dgrad(int form, const catseg_conv_desc& g, const void* dy, const void* dy_scale, const void* w, const void* w_scale, float* dx, int accumulate) {
+  const catseg_conv_bwd_data_desc q = {g, form, dy, dy_scale, w, w_scale, dx, accumulate};
+  return catseg_conv2d_bwd_data(&q, nullptr);
+}
+static int wgrad(int form, const catseg_conv_desc& g, const void* x, const void* x_scale, const void* dy, const void* dy_scale, float* dw, void* workspace,
+                 size_t workspace_bytes, float* dbias = nullptr) {
+  const catseg_conv_bwd_weight_desc q = {g, form, x, x_scale, dy, dy_scale, dw, dbias, workspace, workspace_bytes};
+  return catseg_conv2d_bwd_weight(&q, nullptr);
+}
+
 int main() {
-  EXPECT(catseg_version() >= 1);
+  EXPECT(catseg_version() >= 3);
   alignas(16) static float buf[64];
   float* p16 = buf;
 
@@ -91,12 +110,12 @@ int main() {
       EXPECT(rc == CATSEG_OK);
       EXPECT(out[0] >= 0);
     }
-    EXPECT(catseg_conv2d_bwd_weight_workspace(&d) > 0);
+    EXPECT(catseg_conv2d_bwd_weight_workspace(&d, F32) > 0);
     if (q.Cin % 8 == 0) {       // (0 = this layer is not one the split-precision backward-weight kernels take)
       catseg_conv_desc e = d;
       e.ldx = q.Cin; e.ldy = (q.Cout + 7) / 8 * 8;
-      (void)catseg_conv2d_bwd_weight_bf16x3_workspace(&e);
-      (void)catseg_conv2d_bwd_weight_f16x2_workspace(&e);
+      (void)catseg_conv2d_bwd_weight_workspace(&e, B3);
+      (void)catseg_conv2d_bwd_weight_workspace(&e, H2P);
     }
   }
   {
@@ -124,8 +143,8 @@ int main() {
     for (const Pin& q : pins) {
       const Shape& s = q.s;
       catseg_conv_desc d = desc(s.B, s.H, s.W, s.Cin, s.Cout, s.k, s.s, s.p, s.d);
-      const size_t b3 = catseg_conv2d_bwd_weight_bf16x3_workspace(&d), h2 = catseg_conv2d_bwd_weight_f16x2_workspace(&d);
-      const size_t f32 = catseg_conv2d_bwd_weight_workspace(&d);
+      const size_t b3 = catseg_conv2d_bwd_weight_workspace(&d, B3), h2 = catseg_conv2d_bwd_weight_workspace(&d, H2P);
+      const size_t f32 = catseg_conv2d_bwd_weight_workspace(&d, F32);
       int plan[3][5];
       bool same = b3 == q.ws_b3 && h2 == q.ws_h2 && f32 == q.ws_f32;
       for (int op = 0; op < 3; ++op) {
@@ -144,28 +163,28 @@ int main() {
   // ---- argument validation: every call below must fail ON THE HOST, with a message, before any HIP call (there is no GPU here)
   {
     catseg_conv_desc d = desc(1, 8, 8, 6, 16, 1, 1, 0);        // Cin not a multiple of 4
-    EXPECT(catseg_conv2d_fwd(&d, p16, p16, nullptr, p16, 0, nullptr) != CATSEG_OK);
+    EXPECT(fwd(F32, d, p16, nullptr, p16, nullptr, nullptr, p16, 0) != CATSEG_OK);
     EXPECT(std::strstr(catseg_last_error(), "multiple of 4") != nullptr);
     d = desc(1, 8, 8, 8, 16, 3, 1, 1);
     d.Ho = 9;                                                   // inconsistent geometry
-    EXPECT(catseg_conv2d_fwd(&d, p16, p16, nullptr, p16, 0, nullptr) != CATSEG_OK);
-    EXPECT(catseg_conv2d_bwd_data(&d, p16, p16, p16, 0, nullptr) != CATSEG_OK);
+    EXPECT(fwd(F32, d, p16, nullptr, p16, nullptr, nullptr, p16, 0) != CATSEG_OK);
+    EXPECT(dgrad(F32, d, p16, nullptr, p16, nullptr, p16, 0) != CATSEG_OK);
     d = desc(1, 8, 8, 8, 16, 3, 1, 1);
     d.ldx = 6;                                                  // row stride below the channel count
-    EXPECT(catseg_conv2d_fwd(&d, p16, p16, nullptr, p16, 0, nullptr) != CATSEG_OK);
+    EXPECT(fwd(F32, d, p16, nullptr, p16, nullptr, nullptr, p16, 0) != CATSEG_OK);
     d = desc(1, 8, 8, 8, 16, 3, 1, 1);
-    EXPECT(catseg_conv2d_fwd(&d, p16 + 1, p16, nullptr, p16, 0, nullptr) != CATSEG_OK);      // misaligned pointer
-    EXPECT(catseg_conv2d_fwd(&d, p16, p16, nullptr, p16, 64, nullptr) != CATSEG_OK);         // zero_to beyond the row
+    EXPECT(fwd(F32, d, p16 + 1, nullptr, p16, nullptr, nullptr, p16, 0) != CATSEG_OK);      // misaligned pointer
+    EXPECT(fwd(F32, d, p16, nullptr, p16, nullptr, nullptr, p16, 64) != CATSEG_OK);         // zero_to beyond the row
     d = desc(INT_MAX / 2, 8, 8, 8, 16, 3, 1, 1);                                            // extents whose products overflow 32 bits
-    (void)catseg_conv2d_bwd_weight_workspace(&d);
+    (void)catseg_conv2d_bwd_weight_workspace(&d, F32);
     int out[8];
     (void)catseg_debug_plan_conv(&d, 0, out);
     d = desc(1, 8, 8, 8, 16, 3, 1, 1);
     d.stride = 0;                                                                           // stride 0: no division by it on the host
-    EXPECT(catseg_conv2d_fwd(&d, p16, p16, nullptr, p16, 0, nullptr) != CATSEG_OK);
+    EXPECT(fwd(F32, d, p16, nullptr, p16, nullptr, nullptr, p16, 0) != CATSEG_OK);
     d = desc(1, 8, 8, 8, 16, 3, 1, 1);
     d.groups = 3;                                                                           // channels not divisible by the groups
-    EXPECT(catseg_conv2d_fwd(&d, p16, p16, nullptr, p16, 0, nullptr) != CATSEG_OK);
+    EXPECT(fwd(F32, d, p16, nullptr, p16, nullptr, nullptr, p16, 0) != CATSEG_OK);
   }
   // ---- the split-precision convolution entry points (bf16x3: three bf16 planes; f16x2: two fp16 planes): each refuses with its own code and
   // message -- misaligned planes, a channel count its layout cannot hold, a strided backward-data, operands past the index limits, a workspace
@@ -183,83 +202,83 @@ int main() {
     const catseg_conv_desc big = desc(8, 1024, 1024, 96, 96, 1, 1, 0);      // < 2^31 elements, but the planes of one operand pass 4 GB
     const catseg_conv_desc head = desc(8, 136, 240, 720, 512, 3, 1, 1);     // a layer whose backward-weight plans several splits
 
-    EXPECT_ERR(catseg_conv2d_fwd_bf16x3(&ok, off, pl, nullptr, p16, 0, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: alignment");
-    EXPECT_ERR(catseg_conv2d_fwd_bf16x3(&ok, pl, pl, nullptr, p16, 64, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: alignment");     // zero_to > ldy
-    EXPECT_ERR(catseg_conv2d_fwd_bf16x3(&c12, pl, pl, nullptr, p16, 0, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: needs Cin % 8 == 0");
-    EXPECT_ERR(catseg_conv2d_fwd_bf16x3(&grp, pl, pl, nullptr, p16, 0, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: needs Cin % 8 == 0");
-    EXPECT_ERR(catseg_conv2d_fwd_bf16x3(&huge, pl, pl, nullptr, p16, 0, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: 32-bit offsets");
-    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_bnstats(&ok, pl, off, nullptr, p16, 0, p16, 64, &tr, &ntl, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: bad args");
-    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_bnstats(&ok, pl, pl, nullptr, p16, 0, p16, 64, nullptr, &ntl, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: bad args");
-    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_bnstats(&c12, pl, pl, nullptr, p16, 0, p16, 64, &tr, &ntl, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: needs Cin % 8 == 0");
-    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_bnstats(&huge, pl, pl, nullptr, p16, 0, p16, 64, &tr, &ntl, nullptr), CATSEG_EINVAL, "conv fwd bf16x3: 32-bit offsets");
+    EXPECT_ERR(fwd(B3, ok, off, nullptr, pl, nullptr, nullptr, p16, 0), CATSEG_EINVAL, "conv fwd bf16x3: alignment");
+    EXPECT_ERR(fwd(B3, ok, pl, nullptr, pl, nullptr, nullptr, p16, 64), CATSEG_EINVAL, "conv fwd bf16x3: alignment");     // zero_to > ldy
+    EXPECT_ERR(fwd(B3, c12, pl, nullptr, pl, nullptr, nullptr, p16, 0), CATSEG_EINVAL, "conv fwd bf16x3: needs Cin % 8 == 0");
+    EXPECT_ERR(fwd(B3, grp, pl, nullptr, pl, nullptr, nullptr, p16, 0), CATSEG_EINVAL, "conv fwd bf16x3: needs Cin % 8 == 0");
+    EXPECT_ERR(fwd(B3, huge, pl, nullptr, pl, nullptr, nullptr, p16, 0), CATSEG_EINVAL, "conv fwd bf16x3: 32-bit offsets");
+    EXPECT_ERR(fwd(B3, ok, pl, nullptr, off, nullptr, nullptr, p16, 0, p16, 64, &tr, &ntl), CATSEG_EINVAL, "conv fwd bf16x3: bad args");
+    EXPECT_ERR(fwd(B3, ok, pl, nullptr, pl, nullptr, nullptr, p16, 0, p16, 64, nullptr, &ntl), CATSEG_EINVAL, "conv fwd bf16x3: bad args");
+    EXPECT_ERR(fwd(B3, c12, pl, nullptr, pl, nullptr, nullptr, p16, 0, p16, 64, &tr, &ntl), CATSEG_EINVAL, "conv fwd bf16x3: needs Cin % 8 == 0");
+    EXPECT_ERR(fwd(B3, huge, pl, nullptr, pl, nullptr, nullptr, p16, 0, p16, 64, &tr, &ntl), CATSEG_EINVAL, "conv fwd bf16x3: 32-bit offsets");
     EXPECT(tr == -1 && ntl == -1);                                          // a refused call leaves the tile contract untouched
-    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_blocked(&c24, pl, pl, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(fwd(B3B, c24, pl, nullptr, pl, nullptr, nullptr, p16, 0), CATSEG_EINVAL,
                "conv fwd bf16x3 blocked: needs Cin % 16 == 0");
-    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_blocked(&ok, off, pl, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(fwd(B3B, ok, off, nullptr, pl, nullptr, nullptr, p16, 0), CATSEG_EINVAL,
                "conv fwd bf16x3 blocked: alignment");
-    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_blocked(&ok, pl, pl, nullptr, p16, 0, p16, 64, nullptr, nullptr, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(fwd(B3B, ok, pl, nullptr, pl, nullptr, nullptr, p16, 0, p16, 64, nullptr, nullptr), CATSEG_EINVAL,
                "conv fwd bf16x3 blocked: tile_rows / n_tiles");
-    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_blocked(&big, pl, pl, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(fwd(B3B, big, pl, nullptr, pl, nullptr, nullptr, p16, 0), CATSEG_EINVAL,
                "bf16x3 blocked planes: an operand's three planes must stay below 4 GB");
-    EXPECT_ERR(catseg_conv2d_fwd_bf16x3_blocked(&big, pl, pl, nullptr, p16, 0, p16, 0, &tr, &ntl, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(fwd(B3B, big, pl, nullptr, pl, nullptr, nullptr, p16, 0, p16, 0, &tr, &ntl), CATSEG_EINVAL,
                "bf16x3 blocked planes: an operand's three planes must stay below 4 GB");
     EXPECT(tr == 0 && ntl == 0);                                            // (the partials did not fit: claimed nothing, then refused by the launcher)
-    EXPECT_ERR(catseg_conv2d_fwd_fused_bf16x3_blocked(&c24, pl, pl, nullptr, nullptr, 0, 1, p16, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(fwd(B3B, c24, pl, nullptr, pl, nullptr, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, 1), CATSEG_EINVAL,
                "conv fwd fused bf16x3: needs Cin % 16 == 0");
-    EXPECT_ERR(catseg_conv2d_fwd_fused_bf16x3_blocked(&ok, pl, pl, nullptr, p16, 8, 1, p16, nullptr), CATSEG_EINVAL, "conv fwd fused bf16x3: bad args");
-    EXPECT_ERR(catseg_conv2d_fwd_fused_bf16x3_blocked(&ok, pl, pl, nullptr, nullptr, 0, 1, (float*)off, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(fwd(B3B, ok, pl, nullptr, pl, nullptr, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, p16, 8, 1), CATSEG_EINVAL, "conv fwd fused bf16x3: bad args");
+    EXPECT_ERR(fwd(B3B, ok, pl, nullptr, pl, nullptr, nullptr, (float*)off, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, 1), CATSEG_EINVAL,
                "conv fwd fused bf16x3: bad args");
-    EXPECT_ERR(catseg_conv2d_fwd_fused_bf16x3_blocked(&big, pl, pl, nullptr, nullptr, 0, 1, p16, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(fwd(B3B, big, pl, nullptr, pl, nullptr, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, 1), CATSEG_EINVAL,
                "bf16x3 blocked planes: an operand's three planes must stay below 4 GB");
-    EXPECT_ERR(catseg_conv2d_bwd_data_bf16x3(&s2, pl, pl, p16, 0, nullptr), CATSEG_EINVAL, "conv bwd_data bf16x3: stride 1");
-    EXPECT_ERR(catseg_conv2d_bwd_data_bf16x3(&ok, pl, off, p16, 0, nullptr), CATSEG_EINVAL, "conv bwd_data bf16x3: alignment");
-    EXPECT_ERR(catseg_conv2d_bwd_data_bf16x3(&huge, pl, pl, p16, 0, nullptr), CATSEG_EINVAL, "conv bwd_data bf16x3: 32-bit offsets");
-    EXPECT_ERR(catseg_conv2d_bwd_data_bf16x3_blocked(&s2, pl, pl, p16, 0, nullptr), CATSEG_EINVAL, "conv bwd_data bf16x3 blocked: stride 1");
-    EXPECT_ERR(catseg_conv2d_bwd_data_bf16x3_blocked(&ok, off, pl, p16, 1, nullptr), CATSEG_EINVAL, "conv bwd_data bf16x3 blocked: alignment");
-    EXPECT_ERR(catseg_conv2d_bwd_data_bf16x3_blocked(&big, pl, pl, p16, 0, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(dgrad(B3, s2, pl, nullptr, pl, nullptr, p16, 0), CATSEG_EINVAL, "conv bwd_data bf16x3: stride 1");
+    EXPECT_ERR(dgrad(B3, ok, pl, nullptr, off, nullptr, p16, 0), CATSEG_EINVAL, "conv bwd_data bf16x3: alignment");
+    EXPECT_ERR(dgrad(B3, huge, pl, nullptr, pl, nullptr, p16, 0), CATSEG_EINVAL, "conv bwd_data bf16x3: 32-bit offsets");
+    EXPECT_ERR(dgrad(B3B, s2, pl, nullptr, pl, nullptr, p16, 0), CATSEG_EINVAL, "conv bwd_data bf16x3 blocked: stride 1");
+    EXPECT_ERR(dgrad(B3B, ok, off, nullptr, pl, nullptr, p16, 1), CATSEG_EINVAL, "conv bwd_data bf16x3 blocked: alignment");
+    EXPECT_ERR(dgrad(B3B, big, pl, nullptr, pl, nullptr, p16, 0), CATSEG_EINVAL,
                "bf16x3 blocked planes: an operand's three planes must stay below 4 GB");
-    EXPECT_ERR(catseg_conv2d_bwd_weight_bf16x3(&c12, pl, pl, p16, nullptr, 0, nullptr), CATSEG_EINVAL, "conv bwd_weight bf16x3: dense, Cin % 8 == 0");
-    EXPECT_ERR(catseg_conv2d_bwd_weight_bf16x3(&ok, off, pl, p16, nullptr, 0, nullptr), CATSEG_EINVAL, "conv bwd_weight bf16x3: alignment");
-    EXPECT_ERR(catseg_conv2d_bwd_weight_bf16x3(&huge, pl, pl, p16, nullptr, 0, nullptr), CATSEG_EINVAL, "conv bwd_weight bf16x3: 32-bit offsets");
+    EXPECT_ERR(wgrad(B3, c12, pl, nullptr, pl, nullptr, p16, nullptr, 0), CATSEG_EINVAL, "conv bwd_weight bf16x3: dense, Cin % 8 == 0");
+    EXPECT_ERR(wgrad(B3, ok, off, nullptr, pl, nullptr, p16, nullptr, 0), CATSEG_EINVAL, "conv bwd_weight bf16x3: alignment");
+    EXPECT_ERR(wgrad(B3, huge, pl, nullptr, pl, nullptr, p16, nullptr, 0), CATSEG_EINVAL, "conv bwd_weight bf16x3: 32-bit offsets");
     char msg[96];
-    std::snprintf(msg, sizeof msg, "conv bwd_weight bf16x3: workspace 256 < %zu", catseg_conv2d_bwd_weight_bf16x3_workspace(&head));
-    EXPECT(catseg_conv2d_bwd_weight_bf16x3_workspace(&head) > 256);
-    EXPECT_ERR(catseg_conv2d_bwd_weight_bf16x3(&head, pl, pl, p16, p16, 256, nullptr), CATSEG_EWORKSPACE, msg);
-    std::snprintf(msg, sizeof msg, "conv bwd_weight bf16x3: workspace %zu < %zu", (size_t)1 << 40, catseg_conv2d_bwd_weight_bf16x3_workspace(&head));
-    EXPECT_ERR(catseg_conv2d_bwd_weight_bf16x3(&head, pl, pl, p16, nullptr, (size_t)1 << 40, nullptr), CATSEG_EWORKSPACE, msg);   // null workspace
+    std::snprintf(msg, sizeof msg, "conv bwd_weight bf16x3: workspace 256 < %zu", catseg_conv2d_bwd_weight_workspace(&head, B3));
+    EXPECT(catseg_conv2d_bwd_weight_workspace(&head, B3) > 256);
+    EXPECT_ERR(wgrad(B3, head, pl, nullptr, pl, nullptr, p16, p16, 256), CATSEG_EWORKSPACE, msg);
+    std::snprintf(msg, sizeof msg, "conv bwd_weight bf16x3: workspace %zu < %zu", (size_t)1 << 40, catseg_conv2d_bwd_weight_workspace(&head, B3));
+    EXPECT_ERR(wgrad(B3, head, pl, nullptr, pl, nullptr, p16, nullptr, (size_t)1 << 40), CATSEG_EWORKSPACE, msg);   // null workspace
 
     const void* sc = p16;           // {amax bits, exponent}: never read on the host
-    EXPECT_ERR(catseg_conv2d_fwd_f16x2_blocked(&c24, pl, sc, pl, sc, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(fwd(H2B, c24, pl, sc, pl, sc, nullptr, p16, 0), CATSEG_EINVAL,
                "conv fwd f16x2: needs Cin % 16 == 0");
-    EXPECT_ERR(catseg_conv2d_fwd_f16x2_blocked(&ok, off, sc, pl, sc, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(fwd(H2B, ok, off, sc, pl, sc, nullptr, p16, 0), CATSEG_EINVAL,
                "conv fwd f16x2: alignment");
-    EXPECT_ERR(catseg_conv2d_fwd_f16x2_blocked(&ok, pl, nullptr, pl, sc, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(fwd(H2B, ok, pl, nullptr, pl, sc, nullptr, p16, 0), CATSEG_EINVAL,
                "conv fwd f16x2: alignment");
-    EXPECT_ERR(catseg_conv2d_fwd_f16x2_blocked(&ok, pl, sc, pl, sc, nullptr, p16, 0, p16, 64, &tr, nullptr, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(fwd(H2B, ok, pl, sc, pl, sc, nullptr, p16, 0, p16, 64, &tr, nullptr), CATSEG_EINVAL,
                "conv fwd f16x2: tile_rows / n_tiles");
     tr = ntl = -1;
-    EXPECT_ERR(catseg_conv2d_fwd_f16x2_blocked(&huge, pl, sc, pl, sc, nullptr, p16, 0, p16, (size_t)1 << 40, &tr, &ntl, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(fwd(H2B, huge, pl, sc, pl, sc, nullptr, p16, 0, p16, (size_t)1 << 40, &tr, &ntl), CATSEG_EINVAL,
                "f16x2 blocked planes: an operand's two planes must stay below 4 GB");
     EXPECT(tr == 256 && ntl == 64 * 1024 * 1024 / 256);                     // (claimed for 256-row tiles, then refused by the launcher)
-    EXPECT_ERR(catseg_conv2d_fwd_fused_f16x2_blocked(&c24, pl, sc, pl, sc, nullptr, nullptr, 0, 0, p16, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(fwd(H2B, c24, pl, sc, pl, sc, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, 1), CATSEG_EINVAL,
                "conv fwd fused f16x2: needs Cin % 16 == 0");
-    EXPECT_ERR(catseg_conv2d_fwd_fused_f16x2_blocked(&ok, pl, sc, pl, sc, nullptr, p16, 8, 0, p16, nullptr), CATSEG_EINVAL, "conv fwd fused f16x2: bad args");
-    EXPECT_ERR(catseg_conv2d_fwd_fused_f16x2_blocked(&ok, pl, sc, pl, nullptr, nullptr, nullptr, 0, 0, p16, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(fwd(H2B, ok, pl, sc, pl, sc, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, p16, 8, 0), CATSEG_EINVAL, "conv fwd fused f16x2: bad args");
+    EXPECT_ERR(fwd(H2B, ok, pl, sc, pl, nullptr, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, 1), CATSEG_EINVAL,
                "conv fwd fused f16x2: bad args");
-    EXPECT_ERR(catseg_conv2d_fwd_fused_f16x2_blocked(&huge, pl, sc, pl, sc, nullptr, nullptr, 0, 0, p16, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(fwd(H2B, huge, pl, sc, pl, sc, nullptr, p16, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, 0), CATSEG_EINVAL,
                "f16x2 blocked planes: an operand's two planes must stay below 4 GB");
-    EXPECT_ERR(catseg_conv2d_bwd_data_f16x2_blocked(&s2, pl, sc, pl, sc, p16, 0, nullptr), CATSEG_EINVAL, "conv bwd_data f16x2: stride 1");
-    EXPECT_ERR(catseg_conv2d_bwd_data_f16x2_blocked(&ok, pl, sc, off, sc, p16, 0, nullptr), CATSEG_EINVAL, "conv bwd_data f16x2: alignment");
-    EXPECT_ERR(catseg_conv2d_bwd_data_f16x2_blocked(&huge, pl, sc, pl, sc, p16, 1, nullptr), CATSEG_EINVAL,
+    EXPECT_ERR(dgrad(H2B, s2, pl, sc, pl, sc, p16, 0), CATSEG_EINVAL, "conv bwd_data f16x2: stride 1");
+    EXPECT_ERR(dgrad(H2B, ok, pl, sc, off, sc, p16, 0), CATSEG_EINVAL, "conv bwd_data f16x2: alignment");
+    EXPECT_ERR(dgrad(H2B, huge, pl, sc, pl, sc, p16, 1), CATSEG_EINVAL,
                "f16x2 blocked planes: an operand's two planes must stay below 4 GB");
-    std::snprintf(msg, sizeof msg, "conv bwd_weight f16x2: workspace 256 < %zu", catseg_conv2d_bwd_weight_f16x2_workspace(&head));
+    std::snprintf(msg, sizeof msg, "conv bwd_weight f16x2: workspace 256 < %zu", catseg_conv2d_bwd_weight_workspace(&head, H2P));
     for (int blocked = 0; blocked < 2; ++blocked) {
-      auto wgrad = blocked ? catseg_conv2d_bwd_weight_f16x2_blocked : catseg_conv2d_bwd_weight_f16x2;
-      EXPECT_ERR(wgrad(&c12, pl, sc, pl, sc, p16, nullptr, 0, nullptr), CATSEG_EINVAL, "conv bwd_weight f16x2: dense, Cin % 8 == 0");
-      EXPECT_ERR(wgrad(&ok, pl, sc, off, sc, p16, nullptr, 0, nullptr), CATSEG_EINVAL, "conv bwd_weight f16x2: alignment");
-      EXPECT_ERR(wgrad(&ok, pl, sc, pl, nullptr, p16, nullptr, 0, nullptr), CATSEG_EINVAL, "conv bwd_weight f16x2: alignment");
-      EXPECT_ERR(wgrad(&huge, pl, sc, pl, sc, p16, nullptr, 0, nullptr), CATSEG_EINVAL, "conv bwd_weight f16x2: an operand's two planes must stay below 4 GB");
-      EXPECT_ERR(wgrad(&head, pl, sc, pl, sc, p16, p16, 256, nullptr), CATSEG_EWORKSPACE, msg);
+      const int h2 = blocked ? H2B : H2P;
+      EXPECT_ERR(wgrad(h2, c12, pl, sc, pl, sc, p16, nullptr, 0), CATSEG_EINVAL, "conv bwd_weight f16x2: dense, Cin % 8 == 0");
+      EXPECT_ERR(wgrad(h2, ok, pl, sc, off, sc, p16, nullptr, 0), CATSEG_EINVAL, "conv bwd_weight f16x2: alignment");
+      EXPECT_ERR(wgrad(h2, ok, pl, sc, pl, nullptr, p16, nullptr, 0), CATSEG_EINVAL, "conv bwd_weight f16x2: alignment");
+      EXPECT_ERR(wgrad(h2, huge, pl, sc, pl, sc, p16, nullptr, 0), CATSEG_EINVAL, "conv bwd_weight f16x2: an operand's two planes must stay below 4 GB");
+      EXPECT_ERR(wgrad(h2, head, pl, sc, pl, sc, p16, p16, 256), CATSEG_EWORKSPACE, msg);
     }
   }
   EXPECT(catseg_lovasz_softmax(p16, (const int64_t*)p16, 100, 200, 1.0f, p16, nullptr, 0, p16, (size_t)1 << 30, nullptr) != CATSEG_OK);   // K > 64

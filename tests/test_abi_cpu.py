@@ -34,10 +34,10 @@ def test_argument_validation_without_gpu():
     """bad descriptors are rejected on the host, with a message, before any launch"""
     from miccai2021_cataract_semantic_segmentation_amd import _lib
     d = _lib.ConvDesc(1, 8, 8, 6, 8, 8, 16, 1, 1, 1, 0, 1, 8, 16, 0)   # Cin = 6 is not a multiple of 4
-    rc = _lib.lib.catseg_conv2d_fwd(ctypes.byref(d), 16, 16, 0, 16, 0, None)
+    rc = _lib.lib.catseg_conv2d_fwd(ctypes.byref(_lib.ConvFwdDesc(geo=d, x=16, w=16, y=16)), None)
     assert rc == 1 and b"multiple of 4" in _lib.lib.catseg_last_error()
     d = _lib.ConvDesc(1, 8, 8, 8, 9, 8, 16, 3, 3, 1, 1, 1, 8, 16, 0)   # Ho inconsistent with the geometry
-    assert _lib.lib.catseg_conv2d_fwd(ctypes.byref(d), 16, 16, 0, 16, 0, None) == 1
+    assert _lib.lib.catseg_conv2d_fwd(ctypes.byref(_lib.ConvFwdDesc(geo=d, x=16, w=16, y=16)), None) == 1
     assert _lib.lib.catseg_lovasz_softmax(16, 16, 100, 200, 1.0, 16, 0, 0, 16, 1 << 30, None) == 1  # K > 64
     assert _lib.lib.catseg_lovasz_workspace(4177920, 25) > 4177920 * 25 * 16
     with pytest.raises(_lib.CatsegError):
@@ -196,8 +196,176 @@ def test_add_n_act_rejects_one_defect(what, args, message):
 
 
 def test_abi_version_tells_the_descriptor_entries_from_the_positional_ones():
+    """2: the BatchNorm descriptors; 3: the convolution descriptors (catseg_conv2d_* with new signatures under old names)"""
     from miccai2021_cataract_semantic_segmentation_amd import _lib
-    assert _lib.lib.catseg_version() >= 2
+    assert _lib.lib.catseg_version() == 3
+
+
+# ---- catseg_conv2d_fwd / _bwd_data / _bwd_weight: one defect per case on a descriptor that is valid for its operand form.  1 x 8 x 8 x 32 -> 208,
+# 3 x 3 / pad 1 (208 > 192 output columns, Cin % 16 == 0: every form takes it).  Valid descriptors must NOT go through these tables: with
+# fake pointers they would launch.
+F32, B3, B3B, H2P, H2B = range(5)              # CATSEG_OPERANDS_* of include/catseg.h
+CONV_GEO = dict(B=1, H=8, W=8, Cin=32, Ho=8, Wo=8, Cout=208, kh=3, kw=3, stride=1, pad=1, dil=1, ldx=32, ldy=208, stem4=0, groups=1)
+
+
+def _conv_desc(direction, form, geo=None, **kw):
+    """(descriptor, entry point name) of a call that is valid for `form` but for the fields in geo / kw"""
+    from miccai2021_cataract_semantic_segmentation_amd import _lib
+    h2 = form in (H2P, H2B)
+    if direction == "fwd":
+        cls, f = _lib.ConvFwdDesc, dict(x=A[0], w=A[1], y=A[2], x_scale=A[3] if h2 else None, w_scale=A[4] if h2 else None)
+    elif direction == "bwd_data":
+        cls, f = _lib.ConvBwdDataDesc, dict(dy=A[0], w=A[1], dx=A[2], dy_scale=A[3] if h2 else None, w_scale=A[4] if h2 else None)
+    else:
+        cls, f = _lib.ConvBwdWeightDesc, dict(x=A[0], dy=A[1], dw=A[2], x_scale=A[3] if h2 else None, dy_scale=A[4] if h2 else None, workspace=A[5],
+                                              workspace_bytes=1 << 30)
+    f.update(kw)
+    return cls(geo=_lib.ConvDesc(**dict(CONV_GEO, **(geo or {}))), operands=form, **f), "catseg_conv2d_" + direction
+
+
+BN = dict(bn_part=A[6], bn_part_floats=1 << 20)         # + tile_rows / n_tiles: a refused call writes to neither
+TILES = dict(tile_rows=A[7], n_tiles=A[8])
+CONV_DEFECTS = [
+    # combinations no entry point offered before the descriptors (the last word of a row: what the message must name)
+    ("unknown operand form", "fwd", 5, {}, {}, b"unknown operand form"),
+    ("unknown operand form (backward-data)", "bwd_data", -1, {}, {}, b"unknown operand form"),
+    ("unknown operand form (backward-weight)", "bwd_weight", 99, {}, {}, b"unknown operand form"),
+    ("a scale record with fp32 operands", "fwd", F32, {}, dict(x_scale=A[3]), b"scale record"),
+    ("a scale record with bf16x3 operands", "bwd_data", B3B, {}, dict(w_scale=A[4]), b"scale record"),
+    ("a scale record with bf16x3 operands (backward-weight)", "bwd_weight", B3, {}, dict(dy_scale=A[4]), b"scale record"),
+    ("f16x2 without the activation's scale record", "fwd", H2B, {}, dict(x_scale=None), b"conv fwd f16x2: alignment"),
+    ("f16x2 without the weight's scale record", "bwd_data", H2B, {}, dict(w_scale=None), b"conv bwd_data f16x2: alignment"),
+    ("f16x2 without a scale record (backward-weight)", "bwd_weight", H2P, {}, dict(dy_scale=None), b"conv bwd_weight f16x2: alignment"),
+    ("planar f16x2 in forward", "fwd", H2P, {}, {}, b"backward-weight only"),
+    ("planar f16x2 in backward-data", "bwd_data", H2P, {}, {}, b"backward-weight only"),
+    ("blocked bf16x3 in backward-weight", "bwd_weight", B3B, {}, {}, b"forward and backward-data only"),
+    ("relu with planar bf16x3", "fwd", B3, {}, dict(relu=1), b"not planar bf16x3"),
+    ("residual with planar bf16x3", "fwd", B3, {}, dict(residual=A[9], ldr=208), b"not planar bf16x3"),
+    ("relu with zero_to", "fwd", F32, {}, dict(relu=1, zero_to=208), b"exclude zero_to and bn_part"),
+    ("residual with bn_part", "fwd", B3B, {}, dict(residual=A[9], ldr=208, **BN, **TILES), b"exclude zero_to and bn_part"),
+    ("relu with bn_part (f16x2)", "fwd", H2B, {}, dict(relu=1, **BN, **TILES), b"exclude zero_to and bn_part"),
+    ("bn_part without tile_rows (fp32)", "fwd", F32, {}, dict(BN, n_tiles=A[8]), b"conv fwd bnstats: bad args"),
+    ("bn_part without n_tiles (planar bf16x3)", "fwd", B3, {}, dict(BN, tile_rows=A[7]), b"conv fwd bf16x3: bad args"),
+    ("bn_part without tile_rows / n_tiles (blocked bf16x3)", "fwd", B3B, {}, BN, b"tile_rows / n_tiles"),
+    ("bn_part without n_tiles (f16x2)", "fwd", H2B, {}, dict(BN, tile_rows=A[7]), b"tile_rows / n_tiles"),
+    ("planes with groups", "fwd", B3, dict(groups=2), {}, b"dense"),
+    ("planes with groups (blocked)", "fwd", B3B, dict(groups=2), {}, b"dense"),
+    ("planes with stem4", "fwd", H2B, dict(stem4=1), {}, b"dense"),
+    ("planes with groups (backward-data)", "bwd_data", B3B, dict(groups=2), {}, b"dense"),
+    ("planes with stem4 (backward-data)", "bwd_data", H2B, dict(stem4=1), {}, b"dense"),
+    ("planes with groups (backward-weight)", "bwd_weight", B3, dict(groups=2), {}, b"dense"),
+    ("planes with stem4 (backward-weight)", "bwd_weight", H2B, dict(stem4=1), {}, b"dense"),
+    ("plane backward-data, stride 2", "bwd_data", B3, dict(stride=2, Ho=4, Wo=4), {}, b"stride 1"),
+    ("plane backward-data, stride 2 (blocked)", "bwd_data", B3B, dict(stride=2, Ho=4, Wo=4), {}, b"stride 1"),
+    ("plane backward-data, stride 2 (f16x2)", "bwd_data", H2B, dict(stride=2, Ho=4, Wo=4), {}, b"stride 1"),
+    ("dbias with bf16x3 planes", "bwd_weight", B3, {}, dict(dbias=A[9]), b"dbias needs fp32 operands"),
+    ("dbias with f16x2 planes", "bwd_weight", H2B, {}, dict(dbias=A[9]), b"dbias needs fp32 operands"),
+    # one rule per form that its entry points always had
+    ("misaligned x (fp32)", "fwd", F32, {}, dict(x=A[0] + 4), b"16-byte aligned"),
+    ("misaligned w (fp32 backward-data)", "bwd_data", F32, {}, dict(w=A[1] + 8), b"16-byte aligned"),
+    ("misaligned dw (fp32 backward-weight)", "bwd_weight", F32, {}, dict(dw=A[2] + 4), b"16-byte aligned"),
+    ("misaligned planes (planar bf16x3)", "fwd", B3, {}, dict(w=A[1] + 8), b"conv fwd bf16x3: alignment"),
+    ("misaligned planes (blocked bf16x3)", "bwd_data", B3B, {}, dict(dy=A[0] + 2), b"conv bwd_data bf16x3 blocked: alignment"),
+    ("misaligned planes (planar f16x2)", "bwd_weight", H2P, {}, dict(x=A[0] + 8), b"conv bwd_weight f16x2: alignment"),
+    ("misaligned y (blocked f16x2)", "fwd", H2B, {}, dict(y=A[2] + 4), b"conv fwd f16x2: alignment"),
+    ("Cin = 24, blocked bf16x3", "fwd", B3B, dict(Cin=24, ldx=24), {}, b"Cin % 16 == 0"),
+    ("Cin = 24, blocked f16x2", "fwd", H2B, dict(Cin=24, ldx=24), {}, b"Cin % 16 == 0"),
+    ("Cin = 12, planar bf16x3", "bwd_weight", B3, dict(Cin=12, ldx=12), {}, b"Cin % 8 == 0"),
+    ("33 taps, planar bf16x3", "fwd", B3, dict(kw=11, pad=0, Ho=6, Wo=1, W=11), {}, b"<= 32 taps"),
+    ("33 taps, blocked bf16x3 backward-data", "bwd_data", B3B, dict(kw=11, pad=0, Ho=6, Wo=1, W=11), {}, b"<= 32 taps"),
+    ("33 taps, f16x2", "fwd", H2B, dict(kw=11, pad=0, Ho=6, Wo=1, W=11), {}, b"<= 32 taps"),
+    ("Cin % 4 != 0 (fp32)", "bwd_weight", F32, dict(Cin=30, ldx=32), {}, b"multiple of 4"),
+]
+
+
+@pytest.mark.parametrize("what,direction,form,geo,fields,message", CONV_DEFECTS, ids=[c[0] for c in CONV_DEFECTS])
+def test_conv_rejects_one_defect(what, direction, form, geo, fields, message):
+    """every combination of descriptor fields that none of the twenty positional convolution entry points offered, and one inherited rule per
+    operand form, is refused on the host -- not launched -- with the entry point's name in front of the message"""
+    from miccai2021_cataract_semantic_segmentation_amd import _lib
+    desc, entry = _conv_desc(direction, form, geo, **fields)
+    rc = getattr(_lib.lib, entry)(ctypes.byref(desc), None)
+    err = _lib.lib.catseg_last_error()
+    assert rc == EINVAL and err.startswith(entry.encode() + b":") and message in err, (what, rc, err)
+
+
+def test_conv_workspace_query_and_too_small_workspace():
+    """the query knows the forms backward-weight takes (0 for the others), and a workspace below it is CATSEG_EWORKSPACE, not EINVAL"""
+    from miccai2021_cataract_semantic_segmentation_amd import _lib
+    lib = _lib.lib
+    head = _lib.ConvDesc(B=8, H=136, W=240, Cin=720, Ho=136, Wo=240, Cout=512, kh=3, kw=3, stride=1, pad=1, dil=1, ldx=720, ldy=512, stem4=0, groups=1)
+    need = {form: lib.catseg_conv2d_bwd_weight_workspace(ctypes.byref(head), form) for form in (F32, B3, H2P, H2B)}
+    assert need[B3] == need[H2P] == need[H2B] > 256 and need[F32] > 256
+    assert lib.catseg_conv2d_bwd_weight_workspace(ctypes.byref(head), B3B) == 0 and lib.catseg_conv2d_bwd_weight_workspace(ctypes.byref(head), 7) == 0
+    assert lib.catseg_conv2d_bwd_weight_workspace(None, F32) == 0
+    for form in (F32, B3, H2P, H2B):
+        desc, _ = _conv_desc("bwd_weight", form, geo={f: getattr(head, f) for f, _ in head._fields_}, workspace_bytes=need[form] - 1)
+        rc = lib.catseg_conv2d_bwd_weight(ctypes.byref(desc), None)
+        err = lib.catseg_last_error()
+        assert rc == EWORKSPACE and err.startswith(b"catseg_conv2d_bwd_weight:") and b"workspace" in err, (form, rc, err)
+
+
+# ---- the ctypes table against the header: a swapped I / L / F in _SIGS, or a field out of order in a Structure mirror, loads and runs
+def _header_text():
+    inc = os.path.join(ROOT, "include")
+    hdr = "".join(open(os.path.join(inc, f)).read() for f in sorted(os.listdir(inc)) if f.endswith(".h"))
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)                     # comments first: they quote prototypes
+    hdr = re.sub(r"//[^\n]*", " ", hdr)
+    return re.sub(r"^\s*#[^\n]*$", " ", hdr, flags=re.M).replace('extern "C" {', " ")
+
+
+_VALUE_TYPES = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
+
+
+def _ctype(text, result=False, structs=None):
+    """the ctypes type of a C type as the header spells it"""
+    t = " ".join(text.replace("*", " * ").split())
+    if result and t == "void":
+        return None
+    if result and t == "const char *":
+        return ctypes.c_char_p
+    if "*" in t or t == "catseg_stream_t":
+        return ctypes.c_void_p
+    if structs and t in structs:
+        return structs[t]
+    return _VALUE_TYPES[t.replace("const ", "")]
+
+
+def test_signature_table_matches_the_header():
+    """return type, argument count and every argument type of every catseg_* prototype, against _lib._SIGS"""
+    from miccai2021_cataract_semantic_segmentation_amd import _lib
+    hdr = re.sub(r"typedef\s+struct\s*\{.*?\}\s*\w+\s*;", " ", _header_text(), flags=re.S).replace("}", " ")      # (the brace of extern "C")
+    protos = {}
+    for stmt in hdr.split(";"):
+        m = re.match(r"^\s*(?:typedef\b.*|(.+?)\b(catseg_[a-z0-9_]+)\s*\((.*)\))\s*$", stmt, flags=re.S)
+        assert m or not stmt.strip(), "cannot parse %r" % stmt
+        if m and m.group(2):
+            args = [a.strip() for a in m.group(3).split(",")]
+            args = [] if args == ["void"] else [re.match(r"^(.*?)\w+$", a, flags=re.S).group(1) for a in args]
+            protos[m.group(2)] = (_ctype(m.group(1), result=True), [_ctype(a) for a in args])
+    assert sorted(protos) == _header_symbols() == sorted(_lib._SIGS) and len(protos) == 180
+    for name, sig in protos.items():
+        assert _lib._SIGS[name] == sig, "%s: header %r, _lib._SIGS %r" % (name, sig, _lib._SIGS[name])
+
+
+def test_structure_mirrors_match_the_header():
+    """field order and types of every descriptor struct, against the ctypes.Structure mirrors"""
+    from miccai2021_cataract_semantic_segmentation_amd import _lib
+    mirrors = {"catseg_conv_desc": _lib.ConvDesc, "catseg_conv_fwd_desc": _lib.ConvFwdDesc, "catseg_conv_bwd_data_desc": _lib.ConvBwdDataDesc,
+               "catseg_conv_bwd_weight_desc": _lib.ConvBwdWeightDesc, "catseg_bn_apply_desc": _lib.BnApplyDesc,
+               "catseg_bn_backward_desc": _lib.BnBackwardDesc, "catseg_pointrend_gather_desc": _lib.PointrendGatherDesc,
+               "catseg_pointrend_gather_bwd_desc": _lib.PointrendGatherBwdDesc}
+    found = re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", _header_text(), flags=re.S)
+    assert sorted(name for _, name in found) == sorted(mirrors)
+    for body, name in found:
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            m = re.match(r"^(.*?)(\w+(?:\[\d+\])?(?:\s*,\s*\w+(?:\[\d+\])?)*)$", decl, flags=re.S)
+            base = _ctype(m.group(1), structs=mirrors)
+            for item in m.group(2).split(","):
+                field, _, n = item.strip().partition("[")
+                fields.append((field, base * int(n[:-1]) if n else base))
+        assert [(f[0], f[1]) for f in mirrors[name]._fields_] == fields, name
 
 
 def test_no_cpu_fallback():

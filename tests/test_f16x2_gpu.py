@@ -102,6 +102,7 @@ def test_forward_and_backward_data_vs_fp64(ops, case):
     xp, xs = ops.split2h_blocked(xd)
     wp, ws = ops.split2h_weight_blocked(wd)
     import ctypes
+    from miccai2021_cataract_semantic_segmentation_amd import _lib
     from miccai2021_cataract_semantic_segmentation_amd._lib import lib
     Ho, Wo = y64.shape[2:]
     ld = (Co + 8 + 31) // 32 * 32
@@ -111,9 +112,11 @@ def test_forward_and_backward_data_vs_fp64(ops, case):
     nt_max = (B * Ho * Wo + 255) // 256
     part = torch.empty(3 * nt_max * Co).cuda()
     tr, nt = ctypes.c_int(0), ctypes.c_int(0)
-    ops.check(lib.catseg_conv2d_fwd_f16x2_blocked(ctypes.byref(dsc), ops.ptr(xp), ops.ptr(xs), ops.ptr(wp), ops.ptr(ws), ops.ptr(b.cuda()),
-                                                  ops.ptr(yv), Co + 8, ops.ptr(part), part.numel(), ctypes.byref(tr), ctypes.byref(nt),
-                                                  ops.stream()))
+    bd = b.cuda()
+    q = _lib.ConvFwdDesc(geo=dsc, operands=_lib.OPERANDS_F16X2_BLOCKED, x=ops.ptr(xp), x_scale=ops.ptr(xs), w=ops.ptr(wp), w_scale=ops.ptr(ws),
+                         bias=ops.ptr(bd), y=ops.ptr(yv), zero_to=Co + 8, bn_part=ops.ptr(part), bn_part_floats=part.numel(),
+                         tile_rows=ctypes.addressof(tr), n_tiles=ctypes.addressof(nt))
+    ops.check(lib.catseg_conv2d_fwd(ctypes.byref(q), ops.stream()))
     e = close(nchw(yv), y64.detach(), 2e-5)
     assert float(out[..., Co:Co + 8].abs().max()) == 0.0
     if ld > Co + 8:
@@ -131,11 +134,12 @@ def test_forward_and_backward_data_vs_fp64(ops, case):
         wtp, wts = ops.split2h_weight_t_blocked(wd)
         dx = torch.full((B, H, W, Ci), float("nan")).cuda()
         dsc = ops.make_desc(xd.shape, Ci, Co, (Co + 7) // 8 * 8, k, k, s, p, d)
-        ops.check(lib.catseg_conv2d_bwd_data_f16x2_blocked(ctypes.byref(dsc), ops.ptr(gp), ops.ptr(gs), ops.ptr(wtp), ops.ptr(wts), ops.ptr(dx), 0,
-                                                           ops.stream()))
+        q = _lib.ConvBwdDataDesc(geo=dsc, operands=_lib.OPERANDS_F16X2_BLOCKED, dy=ops.ptr(gp), dy_scale=ops.ptr(gs), w=ops.ptr(wtp),
+                                 w_scale=ops.ptr(wts), dx=ops.ptr(dx), accumulate=0)
+        ops.check(lib.catseg_conv2d_bwd_data(ctypes.byref(q), ops.stream()))
         e2 = close(nchw(dx), xr.grad, 2e-5)
-        ops.check(lib.catseg_conv2d_bwd_data_f16x2_blocked(ctypes.byref(dsc), ops.ptr(gp), ops.ptr(gs), ops.ptr(wtp), ops.ptr(wts), ops.ptr(dx), 1,
-                                                           ops.stream()))
+        q.accumulate = 1
+        ops.check(lib.catseg_conv2d_bwd_data(ctypes.byref(q), ops.stream()))
         close(nchw(dx), 2 * xr.grad, 2e-5)
         print("f16x2 %s: forward %.2g, backward-data %.2g of the output scale" % (case, e, e2))
     # backward-weight from the planar planes (written by the same pass as the blocked ones)
@@ -146,18 +150,20 @@ def test_forward_and_backward_data_vs_fp64(ops, case):
     assert torch.equal(xb, xp)
     _, gpl, gsc = ops.split2h(gyd, blocked=False, planar=True)
     dsc = ops.make_desc(xd.shape, Ci, Co, (Co + 7) // 8 * 8, k, k, s, p, d)
-    ws = torch.empty(max(lib.catseg_conv2d_bwd_weight_f16x2_workspace(ctypes.byref(dsc)), 256), dtype=torch.uint8).cuda()
+    ws = torch.empty(max(lib.catseg_conv2d_bwd_weight_workspace(ctypes.byref(dsc), _lib.OPERANDS_F16X2), 256), dtype=torch.uint8).cuda()
     dw = torch.full((Co, Ci, k, k), float("nan")).cuda().contiguous(memory_format=torch.channels_last)
-    ops.check(lib.catseg_conv2d_bwd_weight_f16x2(ctypes.byref(dsc), ops.ptr(xpl), ops.ptr(xsc), ops.ptr(gpl), ops.ptr(gsc), ops.ptr(dw),
-                                                 ops.ptr(ws), ws.numel(), ops.stream()))
+    q = _lib.ConvBwdWeightDesc(geo=dsc, operands=_lib.OPERANDS_F16X2, x=ops.ptr(xpl), x_scale=ops.ptr(xsc), dy=ops.ptr(gpl), dy_scale=ops.ptr(gsc),
+                               dw=ops.ptr(dw), workspace=ops.ptr(ws), workspace_bytes=ws.numel())
+    ops.check(lib.catseg_conv2d_bwd_weight(ctypes.byref(q), ops.stream()))
     e3 = close(dw, w64.grad, 2e-5)
     print("f16x2 %s: backward-weight %.2g of the output scale" % (case, e3))
     # ... and from the BLOCKED planes (the operand layout of the forward / backward-data kernels): the same values reach the same MFMAs in the
     # same order -- bit-identical results
     gb = ops.split2h_blocked(gyd)[0]
     dwb = torch.full((Co, Ci, k, k), float("nan")).cuda().contiguous(memory_format=torch.channels_last)
-    ops.check(lib.catseg_conv2d_bwd_weight_f16x2_blocked(ctypes.byref(dsc), ops.ptr(xb), ops.ptr(xsc), ops.ptr(gb), ops.ptr(gsc), ops.ptr(dwb),
-                                                         ops.ptr(ws), ws.numel(), ops.stream()))
+    q = _lib.ConvBwdWeightDesc(geo=dsc, operands=_lib.OPERANDS_F16X2_BLOCKED, x=ops.ptr(xb), x_scale=ops.ptr(xsc), dy=ops.ptr(gb),
+                               dy_scale=ops.ptr(gsc), dw=ops.ptr(dwb), workspace=ops.ptr(ws), workspace_bytes=ws.numel())
+    ops.check(lib.catseg_conv2d_bwd_weight(ctypes.byref(q), ops.stream()))
     assert torch.equal(dwb, dw), "backward-weight from blocked planes differs from the planar-plane result"
 
 
@@ -168,6 +174,7 @@ def test_fast_epilogue_bit_identical_to_the_general_one(ops, case):
     into a RAGGED column count (N = Cin not a multiple of 256: the HRNet head's 720) with and without accumulation -- bit for bit; and the
     forward against fp64."""
     import ctypes
+    from miccai2021_cataract_semantic_segmentation_amd import _lib
     from miccai2021_cataract_semantic_segmentation_amd._lib import lib
     B, H, W, Ci, Co, k = case
     assert (B * H * W) % 256 == 0
@@ -190,15 +197,19 @@ def test_fast_epilogue_bit_identical_to_the_general_one(ops, case):
             dsc = ops.make_desc(xd.shape, Ci, Co, Co, k, k, 1, k // 2, 1)
             part = torch.full((3 * (B * H * W // 256) * Co,), float("nan")).cuda()
             tr, nt = ctypes.c_int(0), ctypes.c_int(0)
-            ops.check(lib.catseg_conv2d_fwd_f16x2_blocked(ctypes.byref(dsc), ops.ptr(xp), ops.ptr(xs), ops.ptr(wp), ops.ptr(ws), ops.ptr(b.cuda()),
-                                                          ops.ptr(y), 0, ops.ptr(part), part.numel(), ctypes.byref(tr), ctypes.byref(nt), ops.stream()))
+            bd = b.cuda()
+            q = _lib.ConvFwdDesc(geo=dsc, operands=_lib.OPERANDS_F16X2_BLOCKED, x=ops.ptr(xp), x_scale=ops.ptr(xs), w=ops.ptr(wp), w_scale=ops.ptr(ws),
+                                 bias=ops.ptr(bd), y=ops.ptr(y), bn_part=ops.ptr(part), bn_part_floats=part.numel(),
+                                 tile_rows=ctypes.addressof(tr), n_tiles=ctypes.addressof(nt))
+            ops.check(lib.catseg_conv2d_fwd(ctypes.byref(q), ops.stream()))
             dx0 = torch.full((B, H, W, Ci), float("nan")).cuda()
             dsc = ops.make_desc(xd.shape, Ci, Co, (Co + 7) // 8 * 8, k, k, 1, k // 2, 1)
-            ops.check(lib.catseg_conv2d_bwd_data_f16x2_blocked(ctypes.byref(dsc), ops.ptr(gp), ops.ptr(gs), ops.ptr(wtp), ops.ptr(wts), ops.ptr(dx0), 0,
-                                                               ops.stream()))
+            q = _lib.ConvBwdDataDesc(geo=dsc, operands=_lib.OPERANDS_F16X2_BLOCKED, dy=ops.ptr(gp), dy_scale=ops.ptr(gs), w=ops.ptr(wtp),
+                                     w_scale=ops.ptr(wts), dx=ops.ptr(dx0), accumulate=0)
+            ops.check(lib.catseg_conv2d_bwd_data(ctypes.byref(q), ops.stream()))
             dx1 = base.clone()
-            ops.check(lib.catseg_conv2d_bwd_data_f16x2_blocked(ctypes.byref(dsc), ops.ptr(gp), ops.ptr(gs), ops.ptr(wtp), ops.ptr(wts), ops.ptr(dx1), 1,
-                                                               ops.stream()))
+            q.dx, q.accumulate = ops.ptr(dx1), 1
+            ops.check(lib.catseg_conv2d_bwd_data(ctypes.byref(q), ops.stream()))
             torch.cuda.synchronize()
             res.append((y, part, dx0, dx1))
     finally:

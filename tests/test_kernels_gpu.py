@@ -512,7 +512,7 @@ B3_CASES = [
 @pytest.mark.parametrize("tile", [0, 1, 2, 3, 4, 5, 6, 7, 8, 9])
 @pytest.mark.parametrize("case", B3_CASES)
 def test_conv_bf16x3_split_precision(ops, case, tile):
-    """catseg_split3 + catseg_conv2d_fwd_bf16x3 / _bwd_data_bf16x3 (six bf16 MFMA partial products per block) against an fp64
+    """catseg_split3 + catseg_conv2d_fwd / _bwd_data on CATSEG_OPERANDS_BF16X3 (six bf16 MFMA partial products per block) against an fp64
     F.conv2d: the error must be of fp32 size (2e-5 of the output scale; measured 2e-7 ... 3e-6), for every block-tile form,
     on inputs with a wide dynamic range (per-channel scales e^(2 N(0,1)))"""
     from miccai2021_cataract_semantic_segmentation_amd import _lib
@@ -591,7 +591,7 @@ def test_conv_bf16x3_blocked_planes(ops, case):
     y64.backward(gy.double())
     xd, wd = nhwc(x), ohwi(w)
     ld = (Cout + 3) // 4 * 4 + 4
-    y = ops.conv_fwd_b3_blocked(tuple(xd.shape), ops.split3_blocked(xd)[0], ops.split3_weight_blocked(wd), b.cuda(), Cout, k, k, s, p, d, zero_to=ld)
+    y = ops.conv_fwd_b3(tuple(xd.shape), ops.split3_blocked(xd)[0], ops.split3_weight_blocked(wd), b.cuda(), Cout, k, k, s, p, d, zero_to=ld, blocked=True)
     close(nchw(y), y64.detach(), atol=0, rtol=2e-5)
     full = torch.as_strided(y, y.shape[:3] + (ld,), y.stride())
     assert float(full[..., Cout:].abs().max()) == 0.0
@@ -599,9 +599,9 @@ def test_conv_bf16x3_blocked_planes(ops, case):
         gyd = ops.new_act(B, y64.shape[2], y64.shape[3], Cout, xd.device, zero=True)
         gyd.copy_(nhwc(gy))
         dyb, wtb = ops.split3_blocked(gyd)[0], ops.split3_weight_t_blocked(wd)
-        dx = ops.conv_bwd_data_b3_blocked(dyb, wtb, tuple(xd.shape), Cout, k, k, s, p, d)
+        dx = ops.conv_bwd_data_b3(dyb, wtb, tuple(xd.shape), Cout, k, k, s, p, d, blocked=True)
         close(nchw(dx), xr.grad, atol=0, rtol=2e-5)
-        dx2 = ops.conv_bwd_data_b3_blocked(dyb, wtb, tuple(xd.shape), Cout, k, k, s, p, d, out=dx.clone(), accumulate=True)
+        dx2 = ops.conv_bwd_data_b3(dyb, wtb, tuple(xd.shape), Cout, k, k, s, p, d, out=dx.clone(), accumulate=True, blocked=True)
         close(nchw(dx2), 2 * xr.grad, atol=0, rtol=2e-5)
 
 
@@ -654,7 +654,7 @@ B3_WGRAD_CASES = B3_CASES + [(2, 70, 90, 64, 64, 3, 1, 1, 1), (1, 68, 120, 720, 
 
 @pytest.mark.parametrize("case", B3_WGRAD_CASES)
 def test_conv_bwd_weight_bf16x3(ops, case):
-    """catseg_conv2d_bwd_weight_bf16x3 (pixel-major operands, ds_read_b64_tr_b16 transposed fragments, split reduction) and
+    """catseg_conv2d_bwd_weight on CATSEG_OPERANDS_BF16X3 (pixel-major operands, ds_read_b64_tr_b16 transposed fragments, split reduction) and
     catseg_bias_grad against an fp64 F.conv2d weight gradient"""
     import ctypes
     from miccai2021_cataract_semantic_segmentation_amd import _lib
@@ -674,10 +674,11 @@ def test_conv_bwd_weight_bf16x3(ops, case):
     dw = torch.empty((Cout, Cin, k, k), device="cuda").contiguous(memory_format=torch.channels_last)
     db = torch.empty(Cout, device="cuda")
     desc = ops.make_desc(xd.shape, Cin, Cout, (Cout + 7) // 8 * 8, k, k, s, p, d)
-    ws = ops.workspace(_lib.lib.catseg_conv2d_bwd_weight_bf16x3_workspace(ctypes.byref(desc)) + 256 * Cout * 4, xd.device)
+    ws = ops.workspace(_lib.lib.catseg_conv2d_bwd_weight_workspace(ctypes.byref(desc), _lib.OPERANDS_BF16X3) + 256 * Cout * 4, xd.device)
     xp, dyp = ops.split3(xd), ops.split3(gyd)      # (keep both alive: the planes are only referenced by raw pointers)
-    _lib.check(_lib.lib.catseg_conv2d_bwd_weight_bf16x3(ctypes.byref(desc), ops.ptr(xp), ops.ptr(dyp), ops.ptr(dw),
-                                                        ops.ptr(ws), ws.numel(), ops.stream()))
+    q = _lib.ConvBwdWeightDesc(geo=desc, operands=_lib.OPERANDS_BF16X3, x=ops.ptr(xp), dy=ops.ptr(dyp), dw=ops.ptr(dw), workspace=ops.ptr(ws),
+                               workspace_bytes=ws.numel())
+    _lib.check(_lib.lib.catseg_conv2d_bwd_weight(ctypes.byref(q), ops.stream()))
     _lib.check(_lib.lib.catseg_bias_grad(ops.ptr(gyd), ops.ld_of(gyd), ops.rows_of(gyd), Cout, ops.ptr(db), ops.ptr(ws), ws.numel(), ops.stream()))
     close(dw.cpu(), w.grad, atol=0, rtol=3e-5)
     close(db, b.grad, atol=0, rtol=3e-5)
@@ -707,7 +708,7 @@ BNSTAT_CASES = [
 @pytest.mark.parametrize("mode", ["fp32", "bf16x3"])
 @pytest.mark.parametrize("case", BNSTAT_CASES)
 def test_conv_epilogue_bn_statistics(ops, case, mode):
-    """BatchNorm batch statistics from the convolution epilogue (catseg_conv2d_fwd_bnstats / _bf16x3_bnstats + catseg_bn_finalize)
+    """BatchNorm batch statistics from the convolution epilogue (catseg_conv2d_fwd given bn_part + catseg_bn_finalize)
     against torch's float64 statistics of the convolution output, and against the separate statistics pass (catseg_bn_train_stats)"""
     B, H, W, Cin, Cout, k, s, p = case
     g = torch.Generator().manual_seed(sum(case))

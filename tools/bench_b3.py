@@ -62,15 +62,17 @@ SHAPES = [("head 3x3 720>512 @136x240", 8, 136, 240, 720, 512, 3, 1, 1, 1), ("oc
 def _wgrad32(x, dy, dw, k, s, p, d):
     import ctypes
     desc = ops.make_desc(x.shape, ops.ld_of(x), dy.shape[-1], ops.ld_of(dy), k, k, s, p, d)
-    ws = ops.workspace(_lib.lib.catseg_conv2d_bwd_weight_workspace(ctypes.byref(desc)), x.device)
-    _lib.check(_lib.lib.catseg_conv2d_bwd_weight(ctypes.byref(desc), ops.ptr(x), ops.ptr(dy), ops.ptr(dw), 0, ops.ptr(ws), ws.numel(), ops.stream()))
+    ws = ops.workspace(_lib.lib.catseg_conv2d_bwd_weight_workspace(ctypes.byref(desc), _lib.OPERANDS_F32), x.device)
+    q = _lib.ConvBwdWeightDesc(geo=desc, operands=_lib.OPERANDS_F32, x=ops.ptr(x), dy=ops.ptr(dy), dw=ops.ptr(dw), workspace=ops.ptr(ws), workspace_bytes=ws.numel())
+    _lib.check(_lib.lib.catseg_conv2d_bwd_weight(ctypes.byref(q), ops.stream()))
 
 
 def _wgradb3(x, dy, dw, xp, dyp, Co, Ci, k, s, p, d):
     import ctypes
     desc = ops.make_desc(x.shape, Ci, Co, (Co + 7) // 8 * 8, k, k, s, p, d)
-    ws = ops.workspace(_lib.lib.catseg_conv2d_bwd_weight_bf16x3_workspace(ctypes.byref(desc)) + 1024, x.device)
-    _lib.check(_lib.lib.catseg_conv2d_bwd_weight_bf16x3(ctypes.byref(desc), ops.ptr(xp), ops.ptr(dyp), ops.ptr(dw), ops.ptr(ws), ws.numel(), ops.stream()))
+    ws = ops.workspace(_lib.lib.catseg_conv2d_bwd_weight_workspace(ctypes.byref(desc), _lib.OPERANDS_BF16X3) + 1024, x.device)
+    q = _lib.ConvBwdWeightDesc(geo=desc, operands=_lib.OPERANDS_BF16X3, x=ops.ptr(xp), dy=ops.ptr(dyp), dw=ops.ptr(dw), workspace=ops.ptr(ws), workspace_bytes=ws.numel())
+    _lib.check(_lib.lib.catseg_conv2d_bwd_weight(ctypes.byref(q), ops.stream()))
 
 
 def speed(tiles):

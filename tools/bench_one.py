@@ -23,6 +23,7 @@ if kind.startswith("b3"):
         xb, wb, dyb, wtb = ops.split3_blocked(x)[0], ops.split3_weight_blocked(w), ops.split3_blocked(dy)[0], ops.split3_weight_t_blocked(w)
 if kind.startswith("h2"):
     import ctypes
+    from miccai2021_cataract_semantic_segmentation_amd import _lib
     from miccai2021_cataract_semantic_segmentation_amd._lib import lib
     xb, xpl, xsc = ops.split2h(x, True, True)
     gb, gpl, gsc = ops.split2h(dy, True, True)
@@ -30,21 +31,23 @@ if kind.startswith("h2"):
     wtb, wtsc = ops.split2h_weight_t_blocked(w)
     dfw = ops.make_desc(x.shape, Ci, Co, ops.ld_of(y), k, k, s, p, d)
     dbw = ops.make_desc(x.shape, Ci, Co, (Co + 7) // 8 * 8, k, k, s, p, d)
-    ws = torch.empty(max(lib.catseg_conv2d_bwd_weight_f16x2_workspace(ctypes.byref(dbw)), 256), dtype=torch.uint8, device=dev)
+    h2 = _lib.OPERANDS_F16X2_BLOCKED
+    qf = _lib.ConvFwdDesc(geo=dfw, operands=h2, x=ops.ptr(xb), x_scale=ops.ptr(xsc), w=ops.ptr(wb), w_scale=ops.ptr(wsc), y=ops.ptr(y))
+    qd = _lib.ConvBwdDataDesc(geo=dbw, operands=h2, dy=ops.ptr(gb), dy_scale=ops.ptr(gsc), w=ops.ptr(wtb), w_scale=ops.ptr(wtsc), dx=ops.ptr(dx))
+    ws = torch.empty(max(lib.catseg_conv2d_bwd_weight_workspace(ctypes.byref(dbw), _lib.OPERANDS_F16X2), 256), dtype=torch.uint8, device=dev)
+    qw = _lib.ConvBwdWeightDesc(geo=dbw, operands=_lib.OPERANDS_F16X2, x=ops.ptr(xpl), x_scale=ops.ptr(xsc), dy=ops.ptr(gpl), dy_scale=ops.ptr(gsc),
+                                dw=ops.ptr(dw), workspace=ops.ptr(ws), workspace_bytes=ws.numel())
 torch.cuda.synchronize()
 for _ in range(n):
     if kind == "h2fwd":
-        ops.check(lib.catseg_conv2d_fwd_f16x2_blocked(ctypes.byref(dfw), ops.ptr(xb), ops.ptr(xsc), ops.ptr(wb), ops.ptr(wsc), None, ops.ptr(y), 0,
-                                                      None, 0, None, None, ops.stream()))
+        ops.check(lib.catseg_conv2d_fwd(ctypes.byref(qf), ops.stream()))
     elif kind == "h2dgrad":
-        ops.check(lib.catseg_conv2d_bwd_data_f16x2_blocked(ctypes.byref(dbw), ops.ptr(gb), ops.ptr(gsc), ops.ptr(wtb), ops.ptr(wtsc), ops.ptr(dx), 0,
-                                                           ops.stream()))
+        ops.check(lib.catseg_conv2d_bwd_data(ctypes.byref(qd), ops.stream()))
     elif kind == "h2wgrad":
-        ops.check(lib.catseg_conv2d_bwd_weight_f16x2(ctypes.byref(dbw), ops.ptr(xpl), ops.ptr(xsc), ops.ptr(gpl), ops.ptr(gsc), ops.ptr(dw),
-                                                     ops.ptr(ws), ws.numel(), ops.stream()))
+        ops.check(lib.catseg_conv2d_bwd_weight(ctypes.byref(qw), ops.stream()))
     elif kind == "b3fwd": ops.conv_fwd_b3(tuple(x.shape), xp, wp, None, Co, k, k, s, p, d, out=y)
-    elif kind == "b3fwdblk": ops.conv_fwd_b3_blocked(tuple(x.shape), xb, wb, None, Co, k, k, s, p, d, out=y)
-    elif kind == "b3dgradblk": ops.conv_bwd_data_b3_blocked(dyb, wtb, tuple(x.shape), Co, k, k, s, p, d, out=dx)
+    elif kind == "b3fwdblk": ops.conv_fwd_b3(tuple(x.shape), xb, wb, None, Co, k, k, s, p, d, out=y, blocked=True)
+    elif kind == "b3dgradblk": ops.conv_bwd_data_b3(dyb, wtb, tuple(x.shape), Co, k, k, s, p, d, out=dx, blocked=True)
     elif kind == "b3dgrad": ops.conv_bwd_data_b3(dyp, wtp, tuple(x.shape), Co, k, k, s, p, d, out=dx)
     elif kind == "fwd": ops.conv_fwd(x, w, None, Co, k, k, s, p, d, out=y)
     elif kind == "dgrad": ops.conv_bwd_data(dy, w, tuple(x.shape), k, k, s, p, d, out=dx)

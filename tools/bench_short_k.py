@@ -20,7 +20,7 @@ for (B, H, W, Ci, Co) in [(8, 68, 120, 96, 256), (8, 136, 240, 48, 256), (8, 34,
     y = torch.empty(B, H, W, Co, device=dev)
     if Ci % 16 == 0:
         xb, wb = ops.split3_blocked(x)[0], ops.split3_weight_blocked(w)
-        t = timeit(lambda: ops.conv_fwd_b3_blocked(tuple(x.shape), xb, wb, None, Co, 3, 3, 1, 1, 1, out=y))
+        t = timeit(lambda: ops.conv_fwd_b3(tuple(x.shape), xb, wb, None, Co, 3, 3, 1, 1, 1, out=y, blocked=True))
         ts = timeit(lambda: ops.split3_blocked(x))
     else:
         t = ts = float("nan")
