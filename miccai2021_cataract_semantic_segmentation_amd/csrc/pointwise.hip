@@ -311,7 +311,9 @@ __global__ __launch_bounds__(256) void bilinear_fwd_lds_kernel(const float* __re
   const f32x4* g1 = (const f32x4*)(x + ((long long)b * H + y1) * rowf);
   f32x4* s0 = (f32x4*)bl_rows;
   f32x4* s1 = (f32x4*)(bl_rows + rowf);
-  for (int i = threadIdx.x; i < (rowf >> 2); i += 256) {
+  // (up to the last pixel's C channels, not its whole pitch: behind a source that is a channel slice the last row of x ends there)
+  const int nstage = ((W - 1) * ldx + C + 3) >> 2;
+  for (int i = threadIdx.x; i < nstage; i += 256) {
     s0[i] = g0[i];
     s1[i] = g1[i];
   }
