@@ -258,6 +258,16 @@ for _name, (_res, _args) in _SIGS.items():
 
 EXPORTS = tuple(_SIGS)
 
+# the entry points of the extension headers (include/ext/*.h), bound the same way; not part of EXPORTS (= the prototypes of include/*.h)
+_SIGS_EXT = {
+    "catseg_crop_freq_workspace": (SZ, [I, I, I, I]),
+    "catseg_crop_freq_pick": (I, [P, I, I, I, P, P, P, I, I, I, P, P, P, P, P, P, SZ, P]),
+}
+for _name, (_res, _args) in _SIGS_EXT.items():
+    _fn = getattr(lib, _name)
+    _fn.restype = _res
+    _fn.argtypes = _args
+
 if os.environ.get("CATSEG_SYNC"):  # debugging aid: synchronise after every entry point so a device fault names its launch
     class _SyncLib:
         def __init__(self, inner):

@@ -10,6 +10,7 @@
 // Every source read is guarded by a bounds test in the flipped frame's coordinates: whatever the matrix / origin hold, the worst case is zeros.
 // HBM-bound: <= 4 x 4 B read (neighbours share cache lines), 12 (+16) (+3) + 8 B written per pixel; ~10 fp64 operations beside it.
 #include "common.h"
+#include "warp_label.h"
 
 namespace {
 
@@ -19,19 +20,6 @@ __device__ __forceinline__ int reflect(int r, int n) {  // np.pad(mode='reflect'
   r = r % period;
   if (r < 0) r += period;
   return r < n ? r : period - r;
-}
-
-// fixed-point source coordinate of canvas pixel (x, y) for one row (a, b, c) of the inverse matrix
-__device__ __forceinline__ int warp_coord(double a, double b, double c, double x, double y) {
-#pragma clang fp contract(off)          // mul, mul, add, add, mul as five roundings: __dmul_rn / __dadd_rn alone still came out as v_fmac_f64
-  const double p = a * x;
-  const double q = b * y;
-  const double s = p + q;
-  const double t = s + c;
-  double v = rint(t * 32.0);            // round half to even
-  if (!(v >= -2147483648.0)) v = -2147483648.0;   // (NaN lands here too: far outside every frame)
-  if (v > 2147483647.0) v = 2147483647.0;
-  return (int)v;
 }
 
 __global__ __launch_bounds__(256) void ingest_warp_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ lbl, int B, int H, int W,
@@ -50,30 +38,9 @@ __global__ __launch_bounds__(256) void ingest_warp_kernel(const uint8_t* __restr
   // canvas pixel of this output pixel (padding: only with a window as tall as the canvas, so the reflected row is a canvas row)
   const long long cy = (long long)reflect(r - pad_top, Hc) + (origin ? origin[2 * b] : 0);
   const long long cx = (long long)c + (origin ? origin[2 * b + 1] : 0);
-  int wt[4] = {0, 0, 0, 0};
-  long long src[4] = {0, 0, 0, 0};
-  if (cy >= 0 && cy < Hc && cx >= 0 && cx < Wc) {          // (an origin outside the canvas: zeros)
-    int X, Y;
-    if (minv) {
-      const double* m = minv + (long long)b * 6;
-      const double xd = (double)(int)cx, yd = (double)(int)cy;
-      X = warp_coord(m[0], m[1], m[2], xd, yd);
-      Y = warp_coord(m[3], m[4], m[5], xd, yd);
-    } else {
-      X = (int)cx * 32;
-      Y = (int)cy * 32;
-    }
-    const int sx = X >> 5, fx = X & 31, sy = Y >> 5, fy = Y & 31;    // |sx|, |sy| <= 2^26: sx + 1 cannot overflow
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int yy = sy + (k >> 1), xx = sx + (k & 1);
-      const int w = ((k & 1) ? fx : 32 - fx) * ((k >> 1) ? fy : 32 - fy);
-      if (w > 0 && yy >= 0 && yy < H && xx >= 0 && xx < W) {         // the guard of the read below
-        wt[k] = w;
-        src[k] = ((long long)b * H + ((f & 2) ? H - 1 - yy : yy)) * W + ((f & 1) ? W - 1 - xx : xx);   // un-flip, as ingest_kernel
-      }
-    }
-  }
+  int wt[4];
+  long long src[4];
+  warp_taps(minv ? minv + (long long)b * 6 : nullptr, b, f, cy, cx, H, W, Hc, Wc, wt, src);   // csrc/warp_label.h, shared with cropfreq.hip
   if (img) {
     int acc[3] = {0, 0, 0};
 #pragma unroll
@@ -102,24 +69,7 @@ __global__ __launch_bounds__(256) void ingest_warp_kernel(const uint8_t* __restr
     }
     if (x_nhwc4) *reinterpret_cast<float4*>(x_nhwc4 + i * 4) = make_float4(v[0], v[1], v[2], 0.f);
   }
-  if (lbl) {
-    int lab[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      lab[k] = 0;
-      if (wt[k] > 0) lab[k] = lut ? lut[lbl[src[k]]] : lbl[src[k]];   // remap precedes the warp
-    }
-    int best = 0, bestw = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (wt[j] > 0) {
-        int s = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s += (lab[k] == lab[j]) ? wt[k] : 0;   // (wt = 0 where nothing was read)
-        if (s > bestw || (s == bestw && lab[j] < best)) { best = lab[j]; bestw = s; }
-      }
-    labels[i] = (int64_t)best;
-  }
+  if (lbl) labels[i] = (int64_t)warp_label(lbl, lut, wt, src);
 }
 
 }  // namespace

@@ -2058,12 +2058,24 @@ def ingest_u8(img, lbl, lut=None, flips=None, pad_top=0, pad_bottom=0, mean=None
     return (x4 if nhwc4 else x), labels
 
 
+def _warp_matrices(minv, B, dev, who):
+    """HOST canvas -> frame matrices [B,3,3] (or [B,2,3]) -> DEVICE float64 [B,6] (rows 0 and 1), or None"""
+    if minv is None:
+        return None
+    m = np.ascontiguousarray(np.asarray(minv, dtype=np.float64)[:, :2, :])
+    if m.shape != (B, 2, 3) or not np.isfinite(m).all():
+        raise ValueError("%s: the inverse matrices must be finite float64 [B, 3, 3], got shape %s" % (who, np.shape(minv)))
+    return torch.from_numpy(m.reshape(B, 6)).to(dev, non_blocking=True)
+
+
 def ingest_warp_u8(img, lbl, lut=None, flips=None, minv=None, canvas=None, origin=None, window=None, pad_top=0, pad_bottom=0,
                    mean=None, std=None, outputs=("nchw",)):
     """ingest_u8 with the geometric augmentations fused in (csrc/warp.hip): remap -> flip -> warp onto `canvas` (Hc, Wc) -> `window`
     (Hw, Ww) of the canvas at the per-frame `origin` -> reflect pad of the rows -> ToTensor / Normalize.
     minv: HOST float64 [B,3,3] (or [B,2,3]) canvas -> frame matrices (utils.geometry.affine_inverse), None = identity on canvas = frame;
-    origin: HOST int [B,2] = (v, h), None = (0, 0); outputs: any of "nchw", "nhwc4", "u8" (the image forms; ignored without img).
+    origin: HOST int [B,2] = (v, h), None = (0, 0), or a DEVICE int32 [B,2] tensor (crop_freq_pick's result), which is passed on without a
+    host check: the kernel is guarded, window pixels outside the canvas are zeros; outputs: any of "nchw", "nhwc4", "u8" (the image forms;
+    ignored without img).
     Returns {"nchw" | "nhwc4" | "u8": tensor, ..., "labels": int64 [B,H',Ww] or None}.  The host-side values are checked here (finite
     matrices, windows inside the canvas); whatever reaches the kernel regardless yields zeros, never an unguarded read."""
     ref = img if img is not None else lbl
@@ -2075,13 +2087,11 @@ def ingest_warp_u8(img, lbl, lut=None, flips=None, minv=None, canvas=None, origi
     assert set(outputs) <= {"nchw", "nhwc4", "u8"} and (img is None or len(outputs) > 0)
     Hc, Wc = (int(canvas[0]), int(canvas[1])) if canvas is not None else (H, W)
     Hw, Ww = (int(window[0]), int(window[1])) if window is not None else (Hc, Wc)
-    minv_d = origin_d = None
-    if minv is not None:
-        m = np.ascontiguousarray(np.asarray(minv, dtype=np.float64)[:, :2, :])
-        if m.shape != (B, 2, 3) or not np.isfinite(m).all():
-            raise ValueError("ingest_warp_u8: the inverse matrices must be finite float64 [B, 3, 3], got shape %s" % (np.shape(minv),))
-        minv_d = torch.from_numpy(m.reshape(B, 6)).to(dev, non_blocking=True)
-    if origin is not None:
+    minv_d, origin_d = _warp_matrices(minv, B, dev, "ingest_warp_u8"), None
+    if isinstance(origin, torch.Tensor) and origin.is_cuda:
+        assert origin.dtype == torch.int32 and tuple(origin.shape) == (B, 2) and origin.is_contiguous() and origin.device == dev
+        origin_d = origin
+    elif origin is not None:
         o = np.ascontiguousarray(np.asarray(origin, dtype=np.int64))
         if o.shape != (B, 2) or (o < 0).any() or (o[:, 0] + Hw > Hc).any() or (o[:, 1] + Ww > Wc).any():
             raise ValueError("ingest_warp_u8: window origins must be [B, 2] = (v, h) with the %d x %d window inside the %d x %d canvas"
@@ -2104,6 +2114,52 @@ def ingest_warp_u8(img, lbl, lut=None, flips=None, minv=None, canvas=None, origi
                                     pad_top, pad_bottom, ptr(mean), ptr(std), ptr(out.get("nchw")), ptr(out.get("nhwc4")),
                                     ptr(out.get("u8")), ptr(out["labels"]), stream()))
     return out
+
+
+def crop_freq_table(wq, device):
+    """the 256-entry DEVICE weight table of crop_freq_pick from the integer class weights (utils.geometry.freq_weight_table); label values
+    past the last class weigh 0"""
+    wq = [int(v) for v in wq]
+    if len(wq) > 256 or any(v < 0 or v >= 1 << 62 for v in wq):
+        raise ValueError("crop_freq_table: at most 256 weights in [0, 2^62)")
+    return torch.tensor(wq + [0] * (256 - len(wq)), dtype=torch.int64).to(device)
+
+
+def crop_freq_pick(lbl, lut, flips, minv, canvas, px, wq, m53, return_debug=False):
+    """the window origins of CropNP(crop_mode='freq') on the device (csrc/cropfreq.hip): lbl uint8 [B,H,W] raw ids, lut / flips / minv / canvas
+    as ingest_warp_u8 takes them (the labels weighed are the labels that launch writes); px: the window edge (utils.geometry.crop_px);
+    wq: the integer class weights (a sequence of Python ints, or the device table crop_freq_table made of them); m53: per frame
+    int(u * 2 ** 53) of utils.geometry.sample_freq_u's u.  Returns a DEVICE int32 [B,2] = (v, h) for ingest_warp_u8(origin=...);
+    return_debug: (origins, totals int64 [B], flat region indices int64 [B]).  Refuses (ValueError) weights whose sum over the region could
+    pass 2^62."""
+    from .utils.geometry import check_freq_weights, crop_freq_region
+    B, H, W = lbl.shape
+    dev = lbl.device
+    assert lbl.dtype == torch.uint8 and lbl.is_contiguous() and lbl.is_cuda
+    assert lut is None or (lut.dtype == torch.uint8 and lut.is_contiguous() and lut.is_cuda and lut.numel() == 256)
+    assert flips is None or (flips.dtype == torch.int32 and flips.numel() == B and flips.is_cuda)
+    Hc, Wc = (int(canvas[0]), int(canvas[1])) if canvas is not None else (H, W)
+    px = int(px)
+    if isinstance(wq, torch.Tensor):
+        assert wq.dtype == torch.int64 and wq.numel() == 256 and wq.is_contiguous() and wq.device == dev
+        table = wq
+    else:
+        _, rh, rw = crop_freq_region(Hc, Wc, px)
+        check_freq_weights([int(v) for v in wq], rh * rw)
+        table = crop_freq_table(wq, dev)
+    m = [int(v) for v in m53]
+    if len(m) != B or any(v < 0 or v >= 1 << 53 for v in m):
+        raise ValueError("crop_freq_pick: m53 must hold B integers in [0, 2^53)")
+    m_d = torch.tensor(m, dtype=torch.int64).to(dev, non_blocking=True)
+    minv_d = _warp_matrices(minv, B, dev, "crop_freq_pick")
+    origin = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    total = torch.empty(B, dtype=torch.int64, device=dev) if return_debug else None
+    flat = torch.empty(B, dtype=torch.int64, device=dev) if return_debug else None
+    nbytes = lib.catseg_crop_freq_workspace(B, Hc, Wc, px)
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=dev)
+    check(lib.catseg_crop_freq_pick(ptr(lbl), B, H, W, ptr(lut), ptr(flips), ptr(minv_d), Hc, Wc, px, ptr(table), ptr(m_d), ptr(origin),
+                                    ptr(total), ptr(flat), ptr(ws), nbytes, stream()))
+    return (origin, total, flat) if return_debug else origin
 
 
 def resize_nearest(src, Ho, Wo, flip=0, out=None, accumulate=False, divide_by=0.0):

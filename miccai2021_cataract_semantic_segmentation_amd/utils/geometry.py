@@ -4,15 +4,25 @@ Restatement of what the reference does with the `rot` / `shift` / `shear` / `aff
 config list: the keyword table of ``parse_transform_list`` (utils/utils.py:356-401), the random draws and matrices of ``AffineNP``
 (utils/transforms.py:38-105) and the window of ``CropNP`` in mode 'random' (:270-303).  The pixels themselves are computed on the
 device: ``ops.ingest_warp_u8`` / ``GpuIngest(..., affine=, crop=)`` (csrc/warp.hip).  Pinned bit for bit against
-tests/golden/geometry.npz, which the reference's own methods wrote."""
+tests/golden/geometry.npz, which the reference's own methods wrote.
+
+``CropNP`` in mode 'freq' (:282-293) picks its window from the warped labels, so the pick itself runs on the device
+(``ops.crop_freq_pick``, csrc/cropfreq.hip); this module holds its host side: the region, the class table of ``CropNP.__init__``, the
+exact integer weights and the one uniform per frame.  The device pick is the reference's wherever that uniform lies farther than 2^-22
+from every cumulative fraction; it is opt-in for that reason (``crop['on_device']``).  Pinned against
+tests/golden/cropfreq.npz, which the reference's ``CropNP`` wrote."""
 import random as _random
+from fractions import Fraction
 
 import numpy as np
 
 
 def geometry_from_transforms(transform_list, transform_values=None):
     """The reference's keyword table (utils/utils.py:356-388) and its pad rule (:394-398) ->
-    ``{"affine": None | params of AffineNP, "crop": None | {"size", "mode"}, "pad": (top, bottom)}``"""
+    ``{"affine": None | params of AffineNP, "crop": None | {"size", "mode"}, "pad": (top, bottom)}``.
+    crop_mode 'freq' needs ``transform_values['crop_freq_on_device'] = True`` (the device pick, see check_crop) and the class table as
+    ``transform_values['class_sums']`` (the 36 per-raw-class pixel counts, with ``transform_values['experiment']``) or
+    ``transform_values['class_frequencies']``"""
     transform_values = transform_values or {}
     rotation, rot_centre_offset, shift, shear, shear_centre_offset = 0, (.2, .2), 0, (0, 0), (.2, .2)
     set_affine = False
@@ -31,6 +41,12 @@ def geometry_from_transforms(transform_list, transform_values=None):
     crop = None
     if 'crop' in transform_list:
         crop = {"size": transform_values['crop_size'], "mode": transform_values['crop_mode']}
+        if transform_values.get('crop_freq_on_device', False):
+            crop["on_device"] = True
+            if 'class_frequencies' in transform_values:
+                crop["class_frequencies"] = transform_values['class_frequencies']
+            elif 'class_sums' in transform_values:
+                crop["class_frequencies"] = class_frequencies(transform_values['class_sums'], transform_values['experiment'])
         check_crop(crop)
     pad = (2, 2) if ('pad' in transform_list and 'crop' not in transform_list) else (0, 0)   # padding only if nothing was cropped
     return {"affine": affine, "crop": crop, "pad": pad}
@@ -45,8 +61,15 @@ def check_affine(params):
 def check_crop(params):
     mode = params.get("mode", "random")
     if mode == "freq":
-        raise NotImplementedError("crop_mode 'freq' is not supported: the pick depends on the warped labels (a sequential float64 "
-                                  "accumulate over float32 class weights, random.choices); only crop_mode 'random' runs on the device")
+        if not params.get("on_device", False):
+            raise NotImplementedError("crop_mode 'freq' is not supported without crop['on_device'] = True (transform_values["
+                                      "'crop_freq_on_device']): the reference's pick is a sequential float64 accumulate over float32 class "
+                                      "weights (random.choices); the device evaluates it in exact integers, which is the reference's "
+                                      "pick only where the draw lies farther than 2^-22 from every cumulative fraction")
+        if params.get("class_frequencies") is None and params.get("class_sums") is None:
+            raise ValueError("crop_mode 'freq' needs the class table: crop['class_sums'] (per raw class pixel counts, with "
+                             "crop['experiment']) or crop['class_frequencies']")
+        return
     if mode != "random":
         raise ValueError("Crop mode '{}' not recognised.".format(mode))
 
@@ -134,3 +157,63 @@ def sample_crops(batch, canvas, px, random=_random):
         out[b, 0] = random.randint(0, v_max) if v_max > 0 else 0
         out[b, 1] = random.randint(0, h_max) if h_max > 0 else 0
     return out
+
+
+def crop_freq_region(h, w, px):
+    """CropNP 'freq' (utils/transforms.py:287-288): (margin, rows, columns) of the region ``lbl[margin:h - margin, margin:h - margin]`` the
+    pick is drawn from.  The reference slices the COLUMNS with the height too: with w > h the right part of the frame is never picked, with
+    w < h numpy clips the slice at w.  The picked pixel's index in the region is used as the window's upper-left corner as it is."""
+    h, w, px = int(h), int(w), int(px)
+    margin = px // 2
+    return margin, max(h - 2 * margin, 0), max(min(h - margin, w) - margin, 0)
+
+
+def class_frequencies(class_sums, experiment):
+    """CropNP.__init__'s table (utils/transforms.py:264-268): per network class the sum of the per-raw-class pixel counts `class_sums` (36
+    entries: what a label table carries for the repeat-factor sampler) over the experiment's remap list, as float32, divided by their
+    float32 sum.  The class after the last key of the remap is the ignore class and takes key 255.
+    Experiment 3 is NOT pinned to the reference: its CropNP.__init__ raises KeyError(25) in every mode (it looks class 17 up under 255 and
+    class 25 under 25); this is the evident intent -- class i from key i, the last class from key 255."""
+    from .classes import CLASS_REMAP
+    remap = CLASS_REMAP[experiment]
+    counts = np.array(class_sums)
+    sums = np.zeros(len(remap), 'f')
+    for i in range(len(remap)):
+        sums[i] = np.sum(counts[remap[i if i in remap else 255]])
+    return sums / np.sum(sums)
+
+
+def freq_weight_table(freqs):
+    """(wq, s): the weights w_c = float32(1) / f_c of CropNP 'freq' as exact Python integers wq_c = w_c * s, s (a Fraction) the smallest
+    power of two that makes every one an integer (a float32 is an integer over a power of two).  The pick only sees ratios: s cancels."""
+    f = np.asarray(freqs, dtype=np.float32)
+    with np.errstate(divide="ignore"):
+        w = np.float32(1) / f
+    if f.ndim != 1 or f.size == 0 or f.size > 256 or not np.isfinite(w).all() or (w <= 0).any():
+        raise ValueError("freq_weight_table: 1 to 256 positive class frequencies whose float32 reciprocals are finite")
+    fr = [Fraction(float(v)) for v in w]
+    e = max(d.denominator.bit_length() - 1 for d in fr)        # denominators are powers of two: every w * 2^e is an integer
+    wq = [int(d * (1 << e)) for d in fr]
+    while all(q % 2 == 0 for q in wq):                         # (all of them multiples of two: a smaller power serves)
+        wq, e = [q // 2 for q in wq], e - 1
+    s = Fraction(2) ** e
+    assert all(Fraction(q) / s == d for q, d in zip(wq, fr))
+    return wq, s
+
+
+def check_freq_weights(wq, region_pixels):
+    """the device sums the weights of a region in 64 bits: refuse tables that could reach 2^62"""
+    if max(wq) * max(int(region_pixels), 1) >= 1 << 62:
+        raise ValueError("crop_mode 'freq': max(wq) * region pixels = %d * %d reaches 2^62: the class frequencies span too many binades "
+                         "for the integer pick" % (max(wq), region_pixels))
+
+
+def sample_freq_u(batch, random=_random):
+    """CropNP 'freq': ONE ``random.random()`` of Python's random module per frame -- what ``random.choices(..., k=1)`` consumes -- in place
+    of the two ``randint`` of mode 'random'.  Returns float64 [B]; the device takes m = int(u * 2 ** 53), which is exact."""
+    return np.array([random.random() for _ in range(batch)], dtype=np.float64)
+
+
+def freq_m53(u):
+    """the integers int(u * 2^53) of the uniforms (exact: random.random() is a multiple of 2^-53)"""
+    return [int(float(v) * 9007199254740992.0) for v in np.asarray(u, dtype=np.float64).reshape(-1)]

@@ -5,7 +5,9 @@ host: ``remap_mask(..., to_network=True)`` (utils/utils.py:23-47), ``FlipNP`` (u
 ``PadNP(ver=(2, 2), hor=(0, 0), 'reflect')`` (utils/transforms.py:8-20, wired at utils/utils.py:394-401), ``ToTensor`` and the
 optional ``Normalize`` (utils/utils.py:440-447); optionally the PIL blur / colour jitter between pad and ToTensor (utils/augment.py).
 The affine / crop augmentations (``AffineNP`` with crop_to_fit=False, ``CropNP`` 'random': utils/transforms.py:23-105, 254-303) run in the
-same launch (csrc/warp.hip): ``GpuIngest(...)(..., affine=matrices, crop=(origins, px))``, parameters drawn by utils/geometry.py."""
+same launch (csrc/warp.hip): ``GpuIngest(...)(..., affine=matrices, crop=(origins, px))``, parameters drawn by utils/geometry.py.
+``CropNP`` 'freq' (:282-293) picks its origins from the warped labels on the device first (csrc/cropfreq.hip):
+``crop={"mode": "freq", "u": uniforms, "px": px, "table": integer class weights}``; they never visit the host."""
 import numpy as np
 import torch
 
@@ -51,6 +53,9 @@ class GpuIngest:
         """affine: float64 [B,3,3] frame -> canvas matrices (utils.geometry.sample_affine): the frame is warped onto the reference's
         2H x 2W canvas; crop: (origins int32 [B,2] = (v, h), px) (utils.geometry.crop_px / sample_crops): only that px x px window of
         the canvas (without an affine: of the frame) is computed, and -- the reference's pad rule -- the rows are not padded.
+        crop may also be {"mode": "freq", "u": float64 [B] (utils.geometry.sample_freq_u), "px": px, "table": the integer class weights of
+        utils.geometry.freq_weight_table, or ops.crop_freq_table of them}: the origins are picked on the device from the warped labels
+        (CropNP 'freq'; needs lbl) by two small launches ahead of the ingest's, on the same stream.
         blur_radii: per-frame GaussianBlur radius (0 = none; utils.augment.sample_blur); jitter: (orders, factors) of
         utils.augment.sample_color_jitter.  With either, the image takes the reference's order of operations on uint8
         (flip + reflect pad -> blur -> colour jitter -> ToTensor / Normalize: utils/utils.py:394-447) in a few more kernels."""
@@ -81,7 +86,14 @@ class GpuIngest:
         H, W = int(ref.shape[1]), int(ref.shape[2])
         minv = affine_inverse(affine) if affine is not None else None
         canvas = (2 * H, 2 * W) if affine is not None else (H, W)
-        origin, window = (crop[0], (int(crop[1]), int(crop[1]))) if crop is not None else (None, canvas)
+        if isinstance(crop, dict):
+            from .geometry import freq_m53
+            if crop.get("mode") != "freq" or lbl is None:
+                raise ValueError("GpuIngest: a crop given as a dict is the 'freq' form {'mode': 'freq', 'u', 'px', 'table'} and needs labels")
+            origin = ops.crop_freq_pick(lbl.contiguous(), self.lut, flips, minv, canvas, int(crop["px"]), crop["table"], freq_m53(crop["u"]))
+            window = (int(crop["px"]), int(crop["px"]))
+        else:
+            origin, window = (crop[0], (int(crop[1]), int(crop[1]))) if crop is not None else (None, canvas)
         pad = self.pad if crop is None else (0, 0)          # utils/utils.py:396: padding only if no cropping has happened
         staged = img is not None and (blur_radii is not None or jitter is not None)
         form = "u8" if staged else ("nhwc4" if nhwc4 else "nchw")

@@ -14,6 +14,8 @@ second element is ignored) -- e.g. ``cv2.imread`` + BGR->RGB as datasets/Dataset
 the index stream is sharded by rank (dist.ShardedSampler).  blur= / colorjitter= apply BlurPIL / ColorJitter on the GPU (utils/augment.py).
 affine= / crop= (the dicts utils.geometry.geometry_from_transforms returns for the 'rot' / 'shift' / 'shear' / 'affine' / 'crop' keywords) apply
 AffineNP / CropNP('random') in the ingest's own launch (csrc/warp.hip): x is then [B,3,px,px] for a crop, [B,3,2H+4,2W] for an affine alone.
+crop={"size", "mode": "freq", "on_device": True, "class_sums" (+ "experiment") | "class_frequencies"} applies CropNP('freq'): the window is
+picked on the device from the warped labels (csrc/cropfreq.hip) ahead of the ingest's launch; the host only draws one uniform per frame.
 """
 import multiprocessing
 import multiprocessing.connection
@@ -26,7 +28,8 @@ import numpy as np
 import torch
 
 from .augment import sample_blur, sample_color_jitter
-from .geometry import check_affine, check_crop, crop_px, sample_affine, sample_crops
+from .geometry import (check_affine, check_crop, check_freq_weights, class_frequencies, crop_freq_region, crop_px, freq_weight_table,
+                       sample_affine, sample_crops, sample_freq_u)
 from .ingest import GpuIngest, sample_flips
 
 
@@ -142,7 +145,13 @@ class PinnedFrameLoader:
         if affine is not None:
             check_affine(affine)        # (crop_to_fit=True is refused)
         if crop is not None:
-            check_crop(crop)            # (crop_mode 'freq' is refused)
+            check_crop(crop)            # (crop_mode 'freq' is refused without crop['on_device'])
+        self._freq_wq = self._freq_table = None
+        if crop is not None and crop.get("mode", "random") == "freq":
+            freqs = crop.get("class_frequencies")
+            if freqs is None:
+                freqs = class_frequencies(crop["class_sums"], crop.get("experiment", experiment))
+            self._freq_wq = freq_weight_table(freqs)[0]
         # workers = 0: no fill thread -- each batch is stacked into its staging slot by the CONSUMER's thread inside next(), i.e. after the
         # previous step's kernels have been enqueued and while the GPU runs them (a fill thread shares the interpreter lock with the
         # launch loop of ~3000 kernels per step: on a busy host that stretched an HRNet-W48 step by 10 - 30 ms; the inline fill costs the
@@ -222,7 +231,8 @@ class PinnedFrameLoader:
 
     def _geometry(self, batches, frame, rng):
         """per batch {"affine": matrices, "crop": (origins, px)} for GpuIngest (empty dicts without affine= / crop=).  The affine draws
-        continue the epoch's numpy stream after the flips and blurs; the crops take Python's random module, as CropNP does"""
+        continue the epoch's numpy stream after the flips and blurs; the crops take Python's random module, as CropNP does: two randint
+        per frame in mode 'random', one random() per frame in mode 'freq' (the pick itself happens on the device)"""
         if self.affine is None and self.crop is None:
             return [{} for _ in batches]
         h, w = (2 * frame[0], 2 * frame[1]) if self.affine is not None else frame     # CropNP sees the canvas
@@ -233,7 +243,14 @@ class PinnedFrameLoader:
             g = {}
             if self.affine is not None:
                 g["affine"] = sample_affine(len(b), frame, self.affine, rng)[1]
-            if self.crop is not None:
+            if self._freq_wq is not None:
+                if self._freq_table is None:
+                    from .. import ops
+                    _, rh, rw = crop_freq_region(h, w, px)
+                    check_freq_weights(self._freq_wq, rh * rw)
+                    self._freq_table = ops.crop_freq_table(self._freq_wq, self.device)
+                g["crop"] = {"mode": "freq", "u": sample_freq_u(len(b), pyrng), "px": px, "table": self._freq_table}
+            elif self.crop is not None:
                 g["crop"] = (sample_crops(len(b), (h, w), px, pyrng), px)
             out.append(g)
         return out
