@@ -268,6 +268,18 @@ for _name, (_res, _args) in _SIGS_EXT.items():
     _fn.restype = _res
     _fn.argtypes = _args
 
+# the per-frame label-table forms of the ingest launches (include/ext/tables/catseg_ingest_tables.h): the plain entry's arguments with
+# (T, table_of_frame) after the tables
+_SIGS_TABLES = {
+    "catseg_ingest_u8_tables": (I, [P, P, I, I, I, P, I, P, P, I, I, P, P, P, P, P, P]),
+    "catseg_ingest_warp_u8_tables": (I, [P, P, I, I, I, P, I, P, P, P, I, I, P, I, I, I, I, P, P, P, P, P, P, P]),
+    "catseg_crop_freq_pick_tables": (I, [P, I, I, I, P, I, P, P, P, I, I, I, P, P, P, P, P, P, SZ, P]),
+}
+for _name, (_res, _args) in _SIGS_TABLES.items():
+    _fn = getattr(lib, _name)
+    _fn.restype = _res
+    _fn.argtypes = _args
+
 if os.environ.get("CATSEG_SYNC"):  # debugging aid: synchronise after every entry point so a device fault names its launch
     class _SyncLib:
         def __init__(self, inner):

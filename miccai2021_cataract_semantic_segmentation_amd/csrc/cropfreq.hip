@@ -11,6 +11,7 @@
 // row per frame), through the guards of warp_taps; the tables by an 8-bit index.  8 B written per region row, 8 (+16) B per frame.
 #include "common.h"
 #include "ext/catseg_cropfreq.h"
+#include "ext/tables/catseg_ingest_tables.h"
 #include "warp_label.h"
 
 namespace {
@@ -18,8 +19,8 @@ namespace {
 typedef unsigned long long u64;
 
 struct RegionArgs {
-  const uint8_t* lbl; const uint8_t* lut; const int32_t* flips; const double* minv;
-  int H, W, Hc, Wc, margin, rh, rw;
+  const uint8_t* lbl; const uint8_t* luts; const int32_t* table_of_frame; const int32_t* flips; const double* minv;
+  int T, H, W, Hc, Wc, margin, rh, rw;      // luts: [T][256]; table_of_frame: [B] or null = row 0 for every frame
 };
 
 // integer weight of region pixel (r, c) of frame b; tab: the 256 weights in LDS
@@ -27,7 +28,7 @@ __device__ __forceinline__ u64 pixel_weight(const RegionArgs& a, const u64* tab,
   int wt[4];
   long long src[4];
   warp_taps(a.minv ? a.minv + (long long)b * 6 : nullptr, b, f, (long long)a.margin + r, (long long)a.margin + c, a.H, a.W, a.Hc, a.Wc, wt, src);
-  return tab[warp_label(a.lbl, a.lut, wt, src) & 255];
+  return tab[warp_label(a.lbl, label_table_row(a.luts, a.T, a.table_of_frame, b), wt, src) & 255];   // (the index is clamped into [0, T))
 }
 
 // inclusive scan of v over the 256 threads of the block (thread order), *block_total = the sum; sm: 4 words of LDS, free again on return
@@ -132,19 +133,12 @@ bool region_of(int Hc, int Wc, int px, int* margin, int* rh, int* rw) {
   return true;
 }
 
-}  // namespace
-
-extern "C" size_t catseg_crop_freq_workspace(int B, int Hc, int Wc, int px) {
-  int margin, rh, rw;
-  if (B <= 0 || !region_of(Hc, Wc, px, &margin, &rh, &rw) || rh <= 0 || rw <= 0) return 0;
-  return (size_t)B * (size_t)rh * sizeof(u64);
-}
-
 #define PICK_REQUIRE(cond, msg) CS_REQUIRE(cond, "catseg_crop_freq_pick: " msg)
 
-extern "C" int catseg_crop_freq_pick(const uint8_t* lbl, int B, int H, int W, const uint8_t* lut, const int32_t* flips, const double* minv, int Hc,
-                                     int Wc, int px, const uint64_t* wq, const uint64_t* m53, int32_t* origin, uint64_t* total, int64_t* flat,
-                                     void* workspace, size_t workspace_bytes, catseg_stream_t stream) {
+// the two launches behind both entry points
+int pick_launch(const uint8_t* lbl, int B, int H, int W, const uint8_t* luts, int T, const int32_t* table_of_frame, const int32_t* flips,
+                const double* minv, int Hc, int Wc, int px, const uint64_t* wq, const uint64_t* m53, int32_t* origin, uint64_t* total,
+                int64_t* flat, void* workspace, size_t workspace_bytes, catseg_stream_t stream) {
   PICK_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && Hc > 0 && Wc > 0, "bad dims");
   PICK_REQUIRE(H <= 16384 && W <= 16384 && Hc <= 16384 && Wc <= 16384, "frame and canvas are limited to 16384 x 16384");
   int margin = 0, rh = 0, rw = 0;
@@ -162,7 +156,7 @@ extern "C" int catseg_crop_freq_pick(const uint8_t* lbl, int B, int H, int W, co
                      workspace ? workspace_bytes : (size_t)0);
     return CATSEG_EWORKSPACE;
   }
-  RegionArgs a{lbl, lut, flips, minv, H, W, Hc, Wc, margin, rh, rw};
+  RegionArgs a{lbl, luts, table_of_frame, flips, minv, T, H, W, Hc, Wc, margin, rh, rw};
   u64* rowsum = (u64*)workspace;
   hipLaunchKernelGGL(crop_freq_rows_kernel, dim3((unsigned)rh, (unsigned)B), dim3(256), 0, (hipStream_t)stream, a, (const u64*)wq, rowsum);
   CS_LAUNCH_CHECK();
@@ -170,4 +164,28 @@ extern "C" int catseg_crop_freq_pick(const uint8_t* lbl, int B, int H, int W, co
                      (const u64*)rowsum, origin, (u64*)total, flat);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
+}
+
+}  // namespace
+
+extern "C" size_t catseg_crop_freq_workspace(int B, int Hc, int Wc, int px) {
+  int margin, rh, rw;
+  if (B <= 0 || !region_of(Hc, Wc, px, &margin, &rh, &rw) || rh <= 0 || rw <= 0) return 0;
+  return (size_t)B * (size_t)rh * sizeof(u64);
+}
+
+extern "C" int catseg_crop_freq_pick(const uint8_t* lbl, int B, int H, int W, const uint8_t* lut, const int32_t* flips, const double* minv, int Hc,
+                                     int Wc, int px, const uint64_t* wq, const uint64_t* m53, int32_t* origin, uint64_t* total, int64_t* flat,
+                                     void* workspace, size_t workspace_bytes, catseg_stream_t stream) {
+  return pick_launch(lbl, B, H, W, lut, 1, nullptr, flips, minv, Hc, Wc, px, wq, m53, origin, total, flat, workspace, workspace_bytes, stream);
+}
+
+extern "C" int catseg_crop_freq_pick_tables(const uint8_t* lbl, int B, int H, int W, const uint8_t* luts, int T, const int32_t* table_of_frame,
+                                            const int32_t* flips, const double* minv, int Hc, int Wc, int px, const uint64_t* wq,
+                                            const uint64_t* m53, int32_t* origin, uint64_t* total, int64_t* flat, void* workspace,
+                                            size_t workspace_bytes, catseg_stream_t stream) {
+  PICK_REQUIRE(T >= 1 && (luts != nullptr || table_of_frame == nullptr), "a table index needs T >= 1 tables");
+  PICK_REQUIRE((((uintptr_t)table_of_frame) & 3) == 0, "the table index must be 4-byte aligned");
+  return pick_launch(lbl, B, H, W, luts, T, table_of_frame, flips, minv, Hc, Wc, px, wq, m53, origin, total, flat, workspace, workspace_bytes,
+                     stream);
 }

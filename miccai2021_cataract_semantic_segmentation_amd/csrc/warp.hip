@@ -10,6 +10,7 @@
 // Every source read is guarded by a bounds test in the flipped frame's coordinates: whatever the matrix / origin hold, the worst case is zeros.
 // HBM-bound: <= 4 x 4 B read (neighbours share cache lines), 12 (+16) (+3) + 8 B written per pixel; ~10 fp64 operations beside it.
 #include "common.h"
+#include "ext/tables/catseg_ingest_tables.h"
 #include "warp_label.h"
 
 namespace {
@@ -23,7 +24,8 @@ __device__ __forceinline__ int reflect(int r, int n) {  // np.pad(mode='reflect'
 }
 
 __global__ __launch_bounds__(256) void ingest_warp_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ lbl, int B, int H, int W,
-                                                          const uint8_t* __restrict__ lut, const int32_t* __restrict__ flips,
+                                                          const uint8_t* __restrict__ luts, int T,
+                                                          const int32_t* __restrict__ table_of_frame, const int32_t* __restrict__ flips,
                                                           const double* __restrict__ minv, int Hc, int Wc, const int32_t* __restrict__ origin,
                                                           int Ww, int pad_top, int Ho, const float* __restrict__ mean,
                                                           const float* __restrict__ stdv, float* __restrict__ x_nchw, float* __restrict__ x_nhwc4,
@@ -69,17 +71,15 @@ __global__ __launch_bounds__(256) void ingest_warp_kernel(const uint8_t* __restr
     }
     if (x_nhwc4) *reinterpret_cast<float4*>(x_nhwc4 + i * 4) = make_float4(v[0], v[1], v[2], 0.f);
   }
-  if (lbl) labels[i] = (int64_t)warp_label(lbl, lut, wt, src);
+  if (lbl) labels[i] = (int64_t)warp_label(lbl, label_table_row(luts, T, table_of_frame, b), wt, src);   // (the index is clamped into [0, T))
 }
-
-}  // namespace
 
 #define WARP_REQUIRE(cond, msg) CS_REQUIRE(cond, "catseg_ingest_warp_u8: " msg)
 
-extern "C" int catseg_ingest_warp_u8(const uint8_t* img, const uint8_t* lbl, int B, int H, int W, const uint8_t* lut, const int32_t* flips,
-                                     const double* minv, int Hc, int Wc, const int32_t* origin, int Hw, int Ww, int pad_top, int pad_bottom,
-                                     const float* mean, const float* stdv, float* x_nchw, float* x_nhwc4, uint8_t* x_u8, int64_t* labels,
-                                     catseg_stream_t stream) {
+// the one launch behind both entry points (luts: [T][256], table_of_frame: [B] or null = row 0)
+int warp_launch(const uint8_t* img, const uint8_t* lbl, int B, int H, int W, const uint8_t* luts, int T, const int32_t* table_of_frame,
+                const int32_t* flips, const double* minv, int Hc, int Wc, const int32_t* origin, int Hw, int Ww, int pad_top, int pad_bottom,
+                const float* mean, const float* stdv, float* x_nchw, float* x_nhwc4, uint8_t* x_u8, int64_t* labels, catseg_stream_t stream) {
   WARP_REQUIRE(B > 0 && H > 0 && W > 0 && Hc > 0 && Wc > 0 && Hw > 0 && Ww > 0 && pad_top >= 0 && pad_bottom >= 0, "bad dims");
   WARP_REQUIRE(H <= 16384 && W <= 16384 && Hc <= 16384 && Wc <= 16384, "frame and canvas are limited to 16384 x 16384");
   WARP_REQUIRE(Hw <= Hc && Ww <= Wc, "the window must fit into the canvas");
@@ -95,8 +95,29 @@ extern "C" int catseg_ingest_warp_u8(const uint8_t* img, const uint8_t* lbl, int
   const int Ho = Hw + pad_top + pad_bottom;
   const long long n = (long long)B * Ho * Ww;
   WARP_REQUIRE((n + 255) / 256 <= 0x7fffffffLL, "too many output pixels for one launch");
-  hipLaunchKernelGGL(ingest_warp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, img, lbl, B, H, W, lut, flips,
-                     minv, Hc, Wc, origin, Ww, pad_top, Ho, mean, stdv, x_nchw, x_nhwc4, x_u8, labels);
+  hipLaunchKernelGGL(ingest_warp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, img, lbl, B, H, W, luts, T,
+                     table_of_frame, flips, minv, Hc, Wc, origin, Ww, pad_top, Ho, mean, stdv, x_nchw, x_nhwc4, x_u8, labels);
   CS_LAUNCH_CHECK();
   return CATSEG_OK;
+}
+
+}  // namespace
+
+extern "C" int catseg_ingest_warp_u8(const uint8_t* img, const uint8_t* lbl, int B, int H, int W, const uint8_t* lut, const int32_t* flips,
+                                     const double* minv, int Hc, int Wc, const int32_t* origin, int Hw, int Ww, int pad_top, int pad_bottom,
+                                     const float* mean, const float* stdv, float* x_nchw, float* x_nhwc4, uint8_t* x_u8, int64_t* labels,
+                                     catseg_stream_t stream) {
+  return warp_launch(img, lbl, B, H, W, lut, 1, nullptr, flips, minv, Hc, Wc, origin, Hw, Ww, pad_top, pad_bottom, mean, stdv, x_nchw, x_nhwc4,
+                     x_u8, labels, stream);
+}
+
+extern "C" int catseg_ingest_warp_u8_tables(const uint8_t* img, const uint8_t* lbl, int B, int H, int W, const uint8_t* luts, int T,
+                                            const int32_t* table_of_frame, const int32_t* flips, const double* minv, int Hc, int Wc,
+                                            const int32_t* origin, int Hw, int Ww, int pad_top, int pad_bottom, const float* mean,
+                                            const float* stdv, float* x_nchw, float* x_nhwc4, uint8_t* x_u8, int64_t* labels,
+                                            catseg_stream_t stream) {
+  WARP_REQUIRE(T >= 1 && (luts != nullptr || table_of_frame == nullptr), "a table index needs T >= 1 tables");
+  WARP_REQUIRE((((uintptr_t)table_of_frame) & 3) == 0, "the table index must be 4-byte aligned");
+  return warp_launch(img, lbl, B, H, W, luts, T, table_of_frame, flips, minv, Hc, Wc, origin, Hw, Ww, pad_top, pad_bottom, mean, stdv, x_nchw,
+                     x_nhwc4, x_u8, labels, stream);
 }

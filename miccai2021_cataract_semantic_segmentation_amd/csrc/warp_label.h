@@ -51,7 +51,16 @@ __device__ __forceinline__ void warp_taps(const double* __restrict__ m, int b, i
   }
 }
 
-// the label of a canvas pixel from its taps: remap (lut, may be null) precedes the warp
+// row `t` of T 256-entry label tables, t clamped into [0, T): whatever a per-frame table index holds, the row read is one of the T given
+__device__ __forceinline__ const uint8_t* label_table_row(const uint8_t* __restrict__ luts, int T, const int32_t* __restrict__ table_of_frame,
+                                                          int b) {
+  if (!luts || !table_of_frame) return luts;          // null index: row 0 for every frame
+  int t = table_of_frame[b];
+  t = t < 0 ? 0 : (t >= T ? T - 1 : t);
+  return luts + (long long)t * 256;
+}
+
+// the label of a canvas pixel from its taps: remap (lut = the frame's table row, may be null) precedes the warp
 __device__ __forceinline__ int warp_label(const uint8_t* __restrict__ lbl, const uint8_t* __restrict__ lut, const int (&wt)[4],
                                           const long long (&src)[4]) {
   int lab[4];

@@ -5,3 +5,4 @@ from .two_scale import TwoScaleLoss  # noqa: F401
 from .wrapper import LossWrapper  # noqa: F401
 from .overlap import GenDiceLoss, SoftIoU  # noqa: F401
 from .focal import FocalLoss  # noqa: F401
+from .semi import SemiSupervisedLoss  # noqa: F401

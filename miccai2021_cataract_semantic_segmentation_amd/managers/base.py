@@ -42,6 +42,21 @@ def _item(v):
     return v[0] if isinstance(v, (list, tuple)) else v
 
 
+def _is_frame_triple(v):
+    return isinstance(v, (tuple, list)) and len(v) == 3 and isinstance(v[0], torch.Tensor) and isinstance(v[1], torch.Tensor)
+
+
+def unpack_batch(batch):
+    """(img, lbl) of what a loader yields: the (img, lbl, metadata) triple of every dataset here, or -- a utils.BalancedConcatDataset of
+    (labelled, pseudo-labelled) members under torch's DataLoader -- one such triple per member, joined along the batch as
+    [labelled frames | pseudo-labelled frames], the layout losses.SemiSupervisedLoss splits"""
+    if _is_frame_triple(batch):
+        return batch[0], batch[1]
+    if isinstance(batch, (tuple, list)) and batch and all(_is_frame_triple(m) for m in batch):
+        return torch.cat([m[0] for m in batch]), torch.cat([m[1] for m in batch])
+    raise ValueError("a batch must be (img, lbl, metadata), or one such triple per member of a BalancedConcatDataset")
+
+
 def merge_defaults(config):
     """utils/utils.py:533-542: flat defaults + nested defaults for 'data' / 'train' ('loss' must exist)"""
     cfg = dict(DEFAULTS)
@@ -96,6 +111,7 @@ class BaseManager:
         self.video_set, self.frame_sink = video_set, frame_sink
         self.load_model()
         self.loss = self.optimiser = self.scheduler = None
+        self.labeled_validation = False      # inside _eval_pass(with_loss=True): a SemiSupervisedLoss scores the whole batch as labelled
         if self.config["mode"] == "training":
             self.load_loss()
             torch.manual_seed(self.config["seed"])      # after model construction, as BaseManager.py:104-112
@@ -151,7 +167,15 @@ class BaseManager:
     def forward_loss(self, img, lbl):
         """returns (loss, final logits)"""
         out = self.model(img.float())
+        if isinstance(self.loss, _losses.SemiSupervisedLoss):
+            return self.semi_loss(out, lbl.long()), out
         return self.loss(out, lbl.long()), out
+
+    def semi_loss(self, logits, lbl):
+        """a SemiSupervisedLoss on a tensor (single-output nets) or on [interm, final] (OCRNet).  Build-side wiring: the reference's managers
+        never call this loss (OCRNet_Manager.py:87 hands it three arguments, which SemiSupervisedLoss.forward cannot take).  In training the
+        batch is [labelled | pseudo-labelled]; validation batches are labelled throughout (run_on_labeled_validation)"""
+        return self.loss(logits, lbl, run_on_labeled_validation=self.labeled_validation)
 
     def final_output(self, out):
         return out
@@ -178,7 +202,8 @@ class BaseManager:
         # step instead of ~3000 launches); batches of another shape (a ragged last batch) run the loop below
         graphed = None
         use_graph = bool(self.config.get("train", {}).get("hip_graph", False)) and isinstance(self.optimiser, FusedAdam)
-        for img, lbl, _ in self.train_loader:
+        for batch in self.train_loader:
+            img, lbl = unpack_batch(batch)
             img, lbl = img.to(self.device, non_blocking=True), lbl.to(self.device, non_blocking=True)
             if use_graph and graphed is None:
                 from ..graph import GraphedTrainStep
@@ -224,18 +249,22 @@ class BaseManager:
         cm = torch.zeros((K, K), dtype=torch.int32, device=self.device)
         loss_sum = torch.zeros((), device=self.device)
         n = 0
-        with torch.no_grad():
-            for i, (img, lbl, _) in enumerate(loader):
-                if self.world > 1 and i % self.world != self.rank:   # frames sharded round-robin over ranks
-                    continue
-                img, lbl = img.to(self.device), lbl.to(self.device)
-                if with_loss:
-                    loss, out = self.forward_loss(img, lbl)
-                    loss_sum += loss
-                else:
-                    out = self.final_output(self.model(img.float()))
-                t_get_confusion_matrix(out, lbl, cm)
-                n += 1
+        self.labeled_validation = bool(with_loss)
+        try:
+            with torch.no_grad():
+                for i, (img, lbl, _) in enumerate(loader):
+                    if self.world > 1 and i % self.world != self.rank:   # frames sharded round-robin over ranks
+                        continue
+                    img, lbl = img.to(self.device), lbl.to(self.device)
+                    if with_loss:
+                        loss, out = self.forward_loss(img, lbl)
+                        loss_sum += loss
+                    else:
+                        out = self.final_output(self.model(img.float()))
+                    t_get_confusion_matrix(out, lbl, cm)
+                    n += 1
+        finally:
+            self.labeled_validation = False
         if self.world > 1:                                            # one exchange at the end
             import torch.distributed as dist
             cm64 = cm.to(torch.int64)
@@ -339,6 +368,78 @@ class BaseManager:
                     slot["event"].record(side)
                 slot["dev"], slot["tag"] = canvas, (_item(vid_id), _item(frame_idx))      # the device picture lives until its copy has ended
                 flush(ring[(n + 1) % 2])                         # frame n - 1: its copy ran beside this frame's forward pass
+                n += 1
+        flush(ring[n % 2])
+        flush(ring[(n + 1) % 2])
+        return n
+
+    def pseudo_label(self, frame_set=None, label_sink=None, threshold=None):
+        """Pseudo labels for unlabelled frames, in the form DatasetFromDF(labels_remaped=True) reads (datasets/Dataset_from_df.py:49-53):
+        the eval-mode forward as infer() runs it (the model, an Ensemble, or TTA per config['tta']) over every frame of frame_set (items
+        (frame float [3, H, W], ...); default: video_set), then utils.GpuEgress with `threshold` and the pad rows of config['demo_crop']
+        cropped.  label_sink(index, labels) receives, in order, a uint8 [H, W] map of the experiment's NETWORK ids in which the
+        experiment's ignore id marks the pixels whose largest softmax score is below the threshold (utils.clipped_argmax).  The maps
+        travel to the host through demo_infer's two-slot pinned ring, beside the next frame's forward pass.  Experiment 1 has no ignore
+        id: a threshold is refused there.  Returns the number of frames."""
+        frame_set = self.video_set if frame_set is None else frame_set
+        if frame_set is None or not callable(label_sink):
+            raise ValueError("pseudo_label needs frame_set= (or video_set) and a callable label_sink(index, labels)")
+        if threshold and self.experiment not in (2, 3):
+            raise ValueError("pseudo_label: experiment {} has no ignore id to mark pixels below the threshold with (clipped_argmax asserts a "
+                             "truthy ignore_value); use threshold=None".format(self.experiment))
+        flags = {f: getattr(self.model, f) for f in ("get_intermediate", "get_features") if hasattr(self.model, f)}
+        was_training = self.model.training
+        try:
+            return self._pseudo_label(frame_set, label_sink, threshold)
+        finally:                                     # a training manager goes on training: (interm, final) outputs, train mode
+            for f, v in flags.items():
+                setattr(self.model, f, v)
+            self.model.train(was_training)
+
+    def _pseudo_label(self, frame_set, label_sink, threshold):
+        from ..utils import IGNORE_LABEL
+        from ..utils.egress import GpuEgress
+        self.model.eval()
+        if hasattr(self.model, "get_intermediate"):
+            self.model.get_intermediate = False
+        if hasattr(self.model, "get_features"):
+            self.model.get_features = False
+        if self.config["mode"] != "training":        # as infer(): the run's 'best' checkpoint; a training manager labels with the weights it holds
+            self.load_inference_weights()
+        probs = isinstance(self.model, _models.Ensemble)
+        net = self.model
+        if self.config["tta"]:
+            from ..utils.tta import SegmentationTTA
+            net = SegmentationTTA(self.model)
+        egress = GpuEgress(self.experiment, crop=tuple(self.config.get("demo_crop", (0, 0))), threshold=threshold,
+                           ignore_value=IGNORE_LABEL[self.experiment] if self.experiment in (2, 3) else 0, device=self.device)
+        egress.lut = torch.arange(256, dtype=torch.uint8, device=self.device)      # the uint8 maps keep the network ids
+        main, side = torch.cuda.current_stream(self.device), torch.cuda.Stream(self.device)
+        ring = [{"host": None, "event": torch.cuda.Event(), "dev": None, "tag": None} for _ in range(2)]
+
+        def flush(slot):
+            if slot["tag"] is not None:
+                slot["event"].synchronize()
+                label_sink(slot["tag"], slot["host"].numpy().copy())
+                slot["tag"] = slot["dev"] = None
+
+        n = 0
+        with torch.no_grad():
+            for item in DataLoader(frame_set, batch_size=1, shuffle=False):
+                frame = (item[0] if isinstance(item, (tuple, list)) else item).to(self.device, non_blocking=True).float()
+                out = self.final_output(net(frame))
+                if isinstance(out, (tuple, list)):
+                    out = out[-1]
+                labels = egress(out, want="labels_u8", probs=probs)[0]
+                slot = ring[n % 2]
+                if slot["host"] is None or slot["host"].shape != labels.shape:
+                    slot["host"] = torch.empty(labels.shape, dtype=torch.uint8, pin_memory=True)
+                side.wait_stream(main)
+                with torch.cuda.stream(side):
+                    slot["host"].copy_(labels, non_blocking=True)
+                    slot["event"].record(side)
+                slot["dev"], slot["tag"] = labels, n
+                flush(ring[(n + 1) % 2])
                 n += 1
         flush(ring[n % 2])
         flush(ring[(n + 1) % 2])

@@ -3,7 +3,7 @@ CaDIS-like dataset for smoke runs and benchmarks."""
 import torch
 from torch.utils.data import Dataset
 
-from ..losses import LossWrapper
+from ..losses import LossWrapper, SemiSupervisedLoss
 from .base import BaseManager
 
 
@@ -14,6 +14,8 @@ class OCRNetManager(BaseManager):
         interm, out = self.model(img.float())
         if isinstance(self.loss, LossWrapper):
             return self.loss(None, out, lbl.long(), interm_prediction=interm), out
+        if isinstance(self.loss, SemiSupervisedLoss):
+            return self.semi_loss([interm, out], lbl.long()), out
         return self.loss(interm, out, lbl.long()), out
 
     def final_output(self, out):
@@ -27,6 +29,8 @@ class DeepLabv3PlusManager(BaseManager):
         out = self.model(img.float())
         if isinstance(self.loss, LossWrapper):
             return self.loss(None, out, lbl.long()), out
+        if isinstance(self.loss, SemiSupervisedLoss):
+            return self.semi_loss(out, lbl.long()), out
         return self.loss(out, lbl.long()), out
 
 
@@ -75,6 +79,10 @@ class EncDecManager(BaseManager):
     def load_loss(self):
         from ..losses import CrossEntropyLoss
         from ..utils import ce_ignore_index
+        if self.config["loss"].get("name") == "SemiSupervisedLoss":
+            raise NotImplementedError("EncDecManager always builds a LossWrapper from config['loss'] (managers/EncDec_Manager.py:23-29) and "
+                                      "calls it with deep features and an epoch: a SemiSupervisedLoss has no place in that call; train "
+                                      "on pseudo labels with OCRNetManager or a single-output manager")
         self.config["loss"]["experiment"] = self.experiment
         self.config["loss"]["device"] = str(self.device)
         self.loss = LossWrapper(self.config["loss"])

@@ -2035,13 +2035,28 @@ def focal_bwd(logits, labels, gamma, alpha, upstream):
     return dlogits
 
 
-def ingest_u8(img, lbl, lut=None, flips=None, pad_top=0, pad_bottom=0, mean=None, std=None, nhwc4=False):
-    """img uint8 [B,H,W,3] and / or lbl uint8 [B,H,W] -> (x float32 [B,3,H',W] (or NHWC-4 [B,H',W,4]), labels int64 [B,H',W])"""
+def _label_tables(lut, tables, B):
+    """(T, per-frame table index or None) for the `_tables` entry points, or None for the plain ones: lut uint8 [T,256] with
+    tables DEVICE int32 [B] (None = row 0 for every frame; csrc/warp_label.h clamps the index into [0, T)); lut [256] or None: plain"""
+    if lut is None or lut.dim() == 1:
+        assert tables is None, "a per-frame table index needs label tables uint8 [T, 256]"
+        assert lut is None or lut.numel() == 256
+        return None
+    assert lut.dim() == 2 and lut.shape[1] == 256 and lut.shape[0] >= 1, "label tables are uint8 [T, 256]"
+    assert tables is None or (tables.dtype == torch.int32 and tables.numel() == B and tables.is_contiguous() and tables.device == lut.device)
+    return int(lut.shape[0]), tables
+
+
+def ingest_u8(img, lbl, lut=None, flips=None, pad_top=0, pad_bottom=0, mean=None, std=None, nhwc4=False, tables=None):
+    """img uint8 [B,H,W,3] and / or lbl uint8 [B,H,W] -> (x float32 [B,3,H',W] (or NHWC-4 [B,H',W,4]), labels int64 [B,H',W]).
+    tables: DEVICE int32 [B], the row of lut uint8 [T,256] every frame's labels go through (a batch of raw and already remapped label maps
+    in one launch; None with such a lut: row 0 for every frame); lut [256]: one table, the plain entry point"""
     ref = img if img is not None else lbl
     B, H, W = ref.shape[:3]
     Ho = H + pad_top + pad_bottom
     for t in (img, lbl, lut):
         assert t is None or (t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda)
+    tabled = _label_tables(lut, tables, B)
     assert flips is None or (flips.dtype == torch.int32 and flips.numel() == B)
     x = x4 = labels = None
     if img is not None:
@@ -2053,6 +2068,10 @@ def ingest_u8(img, lbl, lut=None, flips=None, pad_top=0, pad_bottom=0, mean=None
     if lbl is not None:
         assert lbl.shape == (B, H, W)
         labels = torch.empty((B, Ho, W), dtype=torch.int64, device=ref.device)
+    if tabled is not None:
+        check(lib.catseg_ingest_u8_tables(ptr(img), ptr(lbl), B, H, W, ptr(lut), tabled[0], ptr(tabled[1]), ptr(flips), pad_top, pad_bottom, ptr(mean),
+                                          ptr(std), ptr(x), ptr(x4), ptr(labels), stream()))
+        return (x4 if nhwc4 else x), labels
     check(lib.catseg_ingest_u8(ptr(img), ptr(lbl), B, H, W, ptr(lut), ptr(flips), pad_top, pad_bottom, ptr(mean), ptr(std),
                                ptr(x), ptr(x4), ptr(labels), stream()))
     return (x4 if nhwc4 else x), labels
@@ -2069,13 +2088,13 @@ def _warp_matrices(minv, B, dev, who):
 
 
 def ingest_warp_u8(img, lbl, lut=None, flips=None, minv=None, canvas=None, origin=None, window=None, pad_top=0, pad_bottom=0,
-                   mean=None, std=None, outputs=("nchw",)):
+                   mean=None, std=None, outputs=("nchw",), tables=None):
     """ingest_u8 with the geometric augmentations fused in (csrc/warp.hip): remap -> flip -> warp onto `canvas` (Hc, Wc) -> `window`
     (Hw, Ww) of the canvas at the per-frame `origin` -> reflect pad of the rows -> ToTensor / Normalize.
     minv: HOST float64 [B,3,3] (or [B,2,3]) canvas -> frame matrices (utils.geometry.affine_inverse), None = identity on canvas = frame;
     origin: HOST int [B,2] = (v, h), None = (0, 0), or a DEVICE int32 [B,2] tensor (crop_freq_pick's result), which is passed on without a
     host check: the kernel is guarded, window pixels outside the canvas are zeros; outputs: any of "nchw", "nhwc4", "u8" (the image forms;
-    ignored without img).
+    ignored without img); tables: as ingest_u8 takes it (lut is then uint8 [T,256]).
     Returns {"nchw" | "nhwc4" | "u8": tensor, ..., "labels": int64 [B,H',Ww] or None}.  The host-side values are checked here (finite
     matrices, windows inside the canvas); whatever reaches the kernel regardless yields zeros, never an unguarded read."""
     ref = img if img is not None else lbl
@@ -2085,6 +2104,7 @@ def ingest_warp_u8(img, lbl, lut=None, flips=None, minv=None, canvas=None, origi
         assert t is None or (t.dtype == torch.uint8 and t.is_contiguous() and t.is_cuda)
     assert flips is None or (flips.dtype == torch.int32 and flips.numel() == B)
     assert set(outputs) <= {"nchw", "nhwc4", "u8"} and (img is None or len(outputs) > 0)
+    tabled = _label_tables(lut, tables, B)
     Hc, Wc = (int(canvas[0]), int(canvas[1])) if canvas is not None else (H, W)
     Hw, Ww = (int(window[0]), int(window[1])) if window is not None else (Hc, Wc)
     minv_d, origin_d = _warp_matrices(minv, B, dev, "ingest_warp_u8"), None
@@ -2110,6 +2130,11 @@ def ingest_warp_u8(img, lbl, lut=None, flips=None, minv=None, canvas=None, origi
     if lbl is not None:
         assert lbl.shape == (B, H, W)
         out["labels"] = torch.empty((B, Ho, Ww), dtype=torch.int64, device=dev)
+    if tabled is not None:
+        check(lib.catseg_ingest_warp_u8_tables(ptr(img), ptr(lbl), B, H, W, ptr(lut), tabled[0], ptr(tabled[1]), ptr(flips), ptr(minv_d), Hc, Wc,
+                                               ptr(origin_d), Hw, Ww, pad_top, pad_bottom, ptr(mean), ptr(std), ptr(out.get("nchw")),
+                                               ptr(out.get("nhwc4")), ptr(out.get("u8")), ptr(out["labels"]), stream()))
+        return out
     check(lib.catseg_ingest_warp_u8(ptr(img), ptr(lbl), B, H, W, ptr(lut), ptr(flips), ptr(minv_d), Hc, Wc, ptr(origin_d), Hw, Ww,
                                     pad_top, pad_bottom, ptr(mean), ptr(std), ptr(out.get("nchw")), ptr(out.get("nhwc4")),
                                     ptr(out.get("u8")), ptr(out["labels"]), stream()))
@@ -2125,18 +2150,19 @@ def crop_freq_table(wq, device):
     return torch.tensor(wq + [0] * (256 - len(wq)), dtype=torch.int64).to(device)
 
 
-def crop_freq_pick(lbl, lut, flips, minv, canvas, px, wq, m53, return_debug=False):
+def crop_freq_pick(lbl, lut, flips, minv, canvas, px, wq, m53, return_debug=False, tables=None):
     """the window origins of CropNP(crop_mode='freq') on the device (csrc/cropfreq.hip): lbl uint8 [B,H,W] raw ids, lut / flips / minv / canvas
     as ingest_warp_u8 takes them (the labels weighed are the labels that launch writes); px: the window edge (utils.geometry.crop_px);
     wq: the integer class weights (a sequence of Python ints, or the device table crop_freq_table made of them); m53: per frame
     int(u * 2 ** 53) of utils.geometry.sample_freq_u's u.  Returns a DEVICE int32 [B,2] = (v, h) for ingest_warp_u8(origin=...);
-    return_debug: (origins, totals int64 [B], flat region indices int64 [B]).  Refuses (ValueError) weights whose sum over the region could
+    return_debug: (origins, totals int64 [B], flat region indices int64 [B]); tables: as ingest_u8 takes it (lut is then uint8 [T,256]).  Refuses (ValueError) weights whose sum over the region could
     pass 2^62."""
     from .utils.geometry import check_freq_weights, crop_freq_region
     B, H, W = lbl.shape
     dev = lbl.device
     assert lbl.dtype == torch.uint8 and lbl.is_contiguous() and lbl.is_cuda
-    assert lut is None or (lut.dtype == torch.uint8 and lut.is_contiguous() and lut.is_cuda and lut.numel() == 256)
+    assert lut is None or (lut.dtype == torch.uint8 and lut.is_contiguous() and lut.is_cuda)
+    tabled = _label_tables(lut, tables, B)
     assert flips is None or (flips.dtype == torch.int32 and flips.numel() == B and flips.is_cuda)
     Hc, Wc = (int(canvas[0]), int(canvas[1])) if canvas is not None else (H, W)
     px = int(px)
@@ -2157,6 +2183,10 @@ def crop_freq_pick(lbl, lut, flips, minv, canvas, px, wq, m53, return_debug=Fals
     flat = torch.empty(B, dtype=torch.int64, device=dev) if return_debug else None
     nbytes = lib.catseg_crop_freq_workspace(B, Hc, Wc, px)
     ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=dev)
+    if tabled is not None:
+        check(lib.catseg_crop_freq_pick_tables(ptr(lbl), B, H, W, ptr(lut), tabled[0], ptr(tabled[1]), ptr(flips), ptr(minv_d), Hc, Wc, px, ptr(table),
+                                               ptr(m_d), ptr(origin), ptr(total), ptr(flat), ptr(ws), nbytes, stream()))
+        return (origin, total, flat) if return_debug else origin
     check(lib.catseg_crop_freq_pick(ptr(lbl), B, H, W, ptr(lut), ptr(flips), ptr(minv_d), Hc, Wc, px, ptr(table), ptr(m_d), ptr(origin),
                                     ptr(total), ptr(flat), ptr(ws), nbytes, stream()))
     return (origin, total, flat) if return_debug else origin

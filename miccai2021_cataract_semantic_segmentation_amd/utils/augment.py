@@ -37,12 +37,43 @@ def sample_blur(batch, probability=0.05, kernel_limits=(3, 7), random=np.random)
     return radii
 
 
-def sample_color_jitter(batch, brightness=(2 / 3, 1.5), contrast=(2 / 3, 1.5), saturation=(2 / 3, 1.5), hue=(-0.05, 0.05), generator=None):
+def pseudo_jitter_ranges(strength=2):
+    """the ColorJitter arguments of the 'pseudo_colorjitter' transform keyword (utils/utils.py:419-436): (1 - 0.25 s, 1 + 0.25 s) for
+    brightness, contrast and saturation, hue +-0.02 s; s in {1, 2, 3} ({'strength': s} in the transform list), default 2.  The reference
+    wraps that ColorJitter in RandomApply(p=0.7): sample_color_jitter(..., apply_probability=PSEUDO_JITTER_PROBABILITY)"""
+    s = 2 if strength is None else strength
+    assert s in [1, 2, 3]
+    extent = (1 - s * 0.25, 1 + s * 0.25)
+    return {"brightness": extent, "contrast": extent, "saturation": extent, "hue": (-.02 * s, .02 * s)}
+
+
+PSEUDO_JITTER_PROBABILITY = 0.7
+
+
+def pseudo_jitter_strength(transform_list):
+    """the strength the reference reads off its `transforms` config list (utils/utils.py:421-429): None without the 'pseudo_colorjitter'
+    keyword, else the 'strength' of the first dict entry that has one (1, 2 or 3), default 2 -- for PinnedFrameLoader(pseudo_colorjitter=)"""
+    if 'pseudo_colorjitter' not in transform_list:
+        return None
+    for e in transform_list:
+        if isinstance(e, dict) and 'strength' in e:
+            assert e['strength'] in [1, 2, 3]
+            return e['strength']
+    return 2
+
+
+def sample_color_jitter(batch, brightness=(2 / 3, 1.5), contrast=(2 / 3, 1.5), saturation=(2 / 3, 1.5), hue=(-0.05, 0.05), generator=None,
+                        apply_probability=None):
     """per frame: a permutation of the four operations, then one uniform factor each in the order brightness, contrast,
-    saturation, hue (torchvision >= 0.9 ColorJitter.get_params).  Returns (orders int32 [B, 4], factors float64 [B, 4])"""
+    saturation, hue (torchvision >= 0.9 ColorJitter.get_params).  Returns (orders int32 [B, 4], factors float64 [B, 4]).
+    apply_probability = p: RandomApply([ColorJitter], p) -- one uniform per frame FIRST; where p is below it the frame is skipped:
+    nothing else is drawn for it and its orders are -1, which GpuAugment.color_jitter treats as no operation"""
     orders = np.zeros((batch, 4), dtype=np.int32)
     factors = np.zeros((batch, 4), dtype=np.float64)
     for i in range(batch):
+        if apply_probability is not None and apply_probability < float(torch.rand(1, generator=generator)):
+            orders[i] = -1        # (RandomApply.forward: `if self.p < torch.rand(1): return img`)
+            continue
         orders[i] = torch.randperm(4, generator=generator).numpy()
         for k, (lo, hi) in enumerate((brightness, contrast, saturation, hue)):
             factors[i, k] = float(torch.empty(1).uniform_(lo, hi, generator=generator))

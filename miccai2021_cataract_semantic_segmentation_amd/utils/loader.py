@@ -16,6 +16,10 @@ affine= / crop= (the dicts utils.geometry.geometry_from_transforms returns for t
 AffineNP / CropNP('random') in the ingest's own launch (csrc/warp.hip): x is then [B,3,px,px] for a crop, [B,3,2H+4,2W] for an affine alone.
 crop={"size", "mode": "freq", "on_device": True, "class_sums" (+ "experiment") | "class_frequencies"} applies CropNP('freq'): the window is
 picked on the device from the warped labels (csrc/cropfreq.hip) ahead of the ingest's launch; the host only draws one uniform per frame.
+A ``utils.BalancedConcatDataset(labelled, pseudo)`` with ``labels_remapped=(False, True)`` gives semi-supervised batches: batch_size // 2
+items, laid out [labelled frames | pseudo-labelled frames] as losses.SemiSupervisedLoss splits them; the pseudo frames' label maps hold network
+ids already and pass the remap table by (GpuIngest's label_tables), still in the one ingest launch.  pseudo_colorjitter=s adds the
+'pseudo_colorjitter' keyword's RandomApply(ColorJitter(strength s), p=0.7) after colorjitter.
 """
 import multiprocessing
 import multiprocessing.connection
@@ -27,10 +31,23 @@ import threading
 import numpy as np
 import torch
 
-from .augment import sample_blur, sample_color_jitter
+from .augment import PSEUDO_JITTER_PROBABILITY, pseudo_jitter_ranges, sample_blur, sample_color_jitter
 from .geometry import (check_affine, check_crop, check_freq_weights, class_frequencies, crop_freq_region, crop_px, freq_weight_table,
                        sample_affine, sample_crops, sample_freq_u)
 from .ingest import GpuIngest, sample_flips
+from .semi import BalancedConcatDataset
+
+
+class _MemberFrames:
+    """the frames of a two-member BalancedConcatDataset under the keys (member, index): the fill code asks for one frame per staging row"""
+
+    def __init__(self, paired):
+        self.members = paired.datasets
+
+    def __getitem__(self, key):
+        m, i = key
+        d = self.members[m]
+        return d[i % len(d)]
 
 
 def _worker_main(conn, dataset, slots, widx, nworkers):
@@ -130,13 +147,29 @@ class _WorkerPool:
 class PinnedFrameLoader:
     def __init__(self, dataset, batch_size, experiment, sampler=None, shuffle=True, drop_last=True, flip_probability=(0.0, 0.5),
                  pad=(2, 2), normalise=False, nhwc4=False, device="cuda", prefetch=3, workers=0, seed=0, rank=0, world=1,
-                 blur=False, colorjitter=False, worker_processes=0, affine=None, crop=None):
+                 blur=False, colorjitter=False, worker_processes=0, affine=None, crop=None, labels_remapped=None, pseudo_colorjitter=None):
         """blur / colorjitter: the 'blur' / 'colorjitter' entries of the reference's `transforms` config list (utils/utils.py:412-417):
         BlurPIL(probability=.05, kernel_limits=(3, 7)) and ColorJitter((2/3, 1.5) x 3, hue (-.05, .05)) on the padded uint8 frames,
         as GPU kernels (utils/augment.py).
         affine / crop: the "affine" / "crop" entries of utils.geometry.geometry_from_transforms (AffineNP's parameters; {"size", "mode"}).
-        Their draws are seeded per epoch like the flips; with a crop the rows are not padded (the reference's pad rule)"""
+        Their draws are seeded per epoch like the flips; with a crop the rows are not padded (the reference's pad rule).
+        labels_remapped: per member of a two-member BalancedConcatDataset, whether its label maps hold network ids already
+        (DatasetFromDF(labels_remaped=True), datasets/Dataset_from_df.py:49-53); (False, True) is the one form taken: labelled, then pseudo.
+        pseudo_colorjitter: the strength s in {1, 2, 3} of the 'pseudo_colorjitter' keyword (utils/utils.py:419-436; True = the default 2)"""
         self.dataset, self.batch, self.drop_last = dataset, int(batch_size), drop_last
+        self.paired = isinstance(dataset, BalancedConcatDataset)
+        if self.paired or labels_remapped is not None:
+            if not self.paired or len(dataset.datasets) != 2 or labels_remapped is None or tuple(bool(v) for v in labels_remapped) != (False, True):
+                raise ValueError("PinnedFrameLoader: semi-supervised batches need a BalancedConcatDataset of two members (labelled, pseudo-"
+                                 "labelled) with labels_remapped=(False, True)")
+            if self.batch < 2 or self.batch % 2:
+                raise ValueError("PinnedFrameLoader: a BalancedConcatDataset needs an even batch_size (half labelled, half pseudo-labelled "
+                                 "frames), got %d" % self.batch)
+        self.per_batch = self.batch // 2 if self.paired else self.batch        # dataset items per batch
+        self.frames = _MemberFrames(dataset) if self.paired else dataset        # what the fill code reads frames from
+        self.pseudo_jitter = None
+        if pseudo_colorjitter is not None and pseudo_colorjitter is not False:
+            self.pseudo_jitter = pseudo_jitter_ranges(2 if pseudo_colorjitter is True else pseudo_colorjitter)
         self.device = torch.device(device)
         self.ingest = GpuIngest(experiment, pad=pad, normalise=normalise, device=device)
         self.flip_p, self.nhwc4 = flip_probability, nhwc4
@@ -202,13 +235,13 @@ class PinnedFrameLoader:
             n = len(self.dataset)
             idx = torch.randperm(n, generator=torch.Generator().manual_seed(self.seed + self.epoch)).tolist() if self.shuffle else list(range(n))
         if self.world > 1:
-            n = len(idx) // (self.world * self.batch) * (self.world * self.batch)
+            n = len(idx) // (self.world * self.per_batch) * (self.world * self.per_batch)
             idx = idx[self.rank:n:self.world]
         return idx
 
     def __len__(self):
         n = len(self._indices()) if self.sampler is None else len(self.sampler) // max(self.world, 1)
-        return n // self.batch if self.drop_last else (n + self.batch - 1) // self.batch
+        return n // self.per_batch if self.drop_last else (n + self.per_batch - 1) // self.per_batch
 
     def _alloc(self, h, w):
         if self.nproc:
@@ -216,7 +249,7 @@ class PinnedFrameLoader:
             self.close()
             self._slots = [(torch.empty((self.batch, h, w, 3), dtype=torch.uint8).share_memory_(),
                             torch.empty((self.batch, h, w), dtype=torch.uint8).share_memory_()) for _ in range(self.prefetch + 1)]
-            self._pool = _WorkerPool(self.dataset, self._slots, self.nproc)
+            self._pool = _WorkerPool(self.frames, self._slots, self.nproc)
             rt = torch.cuda.cudart()
             self._registered = []
             for pair in self._slots:
@@ -313,18 +346,26 @@ class PinnedFrameLoader:
     def __iter__(self):
         idx = self._indices()
         self.epoch += 1
-        batches = [idx[i:i + self.batch] for i in range(0, len(idx), self.batch)]
-        if self.drop_last and batches and len(batches[-1]) < self.batch:
+        batches = [idx[i:i + self.per_batch] for i in range(0, len(idx), self.per_batch)]
+        if self.drop_last and batches and len(batches[-1]) < self.per_batch:
             batches.pop()
+        if self.paired:        # staging rows [labelled frames | pseudo-labelled frames]: one (member, index) key per row
+            batches = [[(0, i) for i in b] + [(1, i) for i in b] for b in batches]
         rng = np.random.RandomState(self.seed * 1000003 + self.epoch)
         flips = [sample_flips(len(b), self.flip_p, rng) for b in batches]
         gen = torch.Generator().manual_seed(self.seed * 1000003 + self.epoch)
         blurs = [sample_blur(len(b), random=rng) if self.blur else None for b in batches]
         jitters = [sample_color_jitter(len(b), generator=gen) if self.colorjitter else None for b in batches]
+        if self.pseudo_jitter is not None:      # after colorjitter, the reference's order (utils/utils.py:415-436)
+            jitters = [([j] if j is not None else []) + [sample_color_jitter(len(b), generator=gen, apply_probability=PSEUDO_JITTER_PROBABILITY,
+                                                                            **self.pseudo_jitter)] for j, b in zip(jitters, batches)]
         ready = queue.Queue(maxsize=self.prefetch)
         free = queue.Queue()
-        first = self.dataset[batches[0][0]] if batches else None
+        first = self.frames[batches[0][0]] if batches else None
         geos = self._geometry(batches, tuple(int(v) for v in np.asarray(first[0]).shape[:2]), rng) if batches else []
+        if self.paired:
+            for g, b in zip(geos, batches):
+                g["label_tables"] = np.array([m for m, _ in b], dtype=np.int32)     # member 1 = network ids already: the identity row
         if first is not None and (self._slots is None or tuple(self._slots[0][0].shape[1:3]) != tuple(np.asarray(first[0]).shape[:2])
                                   or (self.nproc and self._pool is None)):
             self._alloc(*np.asarray(first[0]).shape[:2])
@@ -338,7 +379,7 @@ class PinnedFrameLoader:
         def fill(slot, ids):
             img_buf, lbl_buf = self._slots[slot]
             def one(j):
-                item = self.dataset[ids[j]]
+                item = self.frames[ids[j]]
                 img_buf[j].copy_(torch.as_tensor(np.ascontiguousarray(item[0])))
                 lbl_buf[j].copy_(torch.as_tensor(np.ascontiguousarray(item[1])))
             if self.workers > 1 and len(ids) > 1:
