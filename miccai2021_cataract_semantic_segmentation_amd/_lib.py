@@ -280,6 +280,16 @@ for _name, (_res, _args) in _SIGS_TABLES.items():
     _fn.restype = _res
     _fn.argtypes = _args
 
+# the label census and the per-batch IoU average of the class-aware train loaders (include/ext/census/catseg_census.h)
+_SIGS_CENSUS = {
+    "catseg_label_census_u8": (I, [P, I, I, I, P, I, P, I, P]),
+    "catseg_iou_ema": (I, [P, P, I, F, F, P, P, P]),
+}
+for _name, (_res, _args) in _SIGS_CENSUS.items():
+    _fn = getattr(lib, _name)
+    _fn.restype = _res
+    _fn.argtypes = _args
+
 if os.environ.get("CATSEG_SYNC"):  # debugging aid: synchronise after every entry point so a device fault names its launch
     class _SyncLib:
         def __init__(self, inner):

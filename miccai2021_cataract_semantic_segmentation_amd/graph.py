@@ -89,7 +89,7 @@ class _CutRecorder:
 
 class GraphedTrainStep:
     def __init__(self, model, loss_fn, optimiser, img, lbl, confusion=None, warmup=2, keep_state=True, forward_loss=None,
-                 segment_bytes=None):
+                 segment_bytes=None, tracker=None):
         """model: an EngineNet in training mode; loss_fn(model_output, labels) -> scalar loss tensor (or forward_loss(img, labels) ->
         (loss, final logits), the managers' method, instead of model + loss_fn); optimiser: FusedAdam over the model;
         img / lbl: a batch of the shapes every later call will have; confusion: optional int32 [K, K] matrix the step accumulates its
@@ -97,13 +97,19 @@ class GraphedTrainStep:
         Warm-up: `warmup` eager steps on the capture stream (workspaces, weight images, allocator pools reach their steady state);
         keep_state restores parameters, Adam moments, step count and every module buffer afterwards, so that the first call of this
         object IS step 1 of the run.
-        segment_bytes: data parallel only -- see default_segment_bytes(); 0 = never cut (the whole exchange behind the backward pass)."""
+        segment_bytes: data parallel only -- see default_segment_bytes(); 0 = never cut (the whole exchange behind the backward pass).
+        tracker: optional utils.IoUTracker whose step(confusion) is launched behind the confusion matrix INSIDE the capture (None: the
+        captured graph is what it was).  Its device state (cm_prev, the averages) is saved and restored around the warm-up like the
+        confusion matrix: the warm-up steps would otherwise leave their batch in the average the first replay starts from."""
         if not isinstance(optimiser, FusedAdam):
             raise TypeError("GraphedTrainStep needs optim.FusedAdam (its kernel reads the step-dependent scalars from device memory)")
         if not model.training:
             raise RuntimeError("GraphedTrainStep captures a TRAINING step: call model.train() first")
         self.model, self.loss_fn, self.opt, self.confusion = model, loss_fn, optimiser, confusion
         self.forward_loss = forward_loss
+        self.tracker = tracker
+        if tracker is not None and confusion is None:
+            raise ValueError("GraphedTrainStep: a tracker follows the running confusion matrix: pass confusion=")
         # data parallel: the reducer is taken off the tape (a recorder takes its place during the capture); the replays drive it
         self.sync, model._grad_sync = model._grad_sync, None
         self.split = self.sync is not None
@@ -124,7 +130,7 @@ class GraphedTrainStep:
         if keep_state:
             saved = (fp.flat.clone(), m.clone(), v.clone(), [b.clone() for b in model.buffers()], optimiser._steps,
                      [(mod, mod._pending_batches) for mod in model.modules() if isinstance(mod, engine.BatchNorm2d)],
-                     None if confusion is None else confusion.clone())
+                     None if confusion is None else confusion.clone(), None if tracker is None else tracker.save())
         self.stream = torch.cuda.Stream(device=dev)
         self.stream.wait_stream(torch.cuda.current_stream(dev))
         self.graph = self.tail_graph = None
@@ -148,6 +154,8 @@ class GraphedTrainStep:
                     b.copy_(s)
                 if confusion is not None:
                     confusion.copy_(saved[6])
+                if tracker is not None:
+                    tracker.restore(saved[7])
             optimiser._steps = saved[4]
             for mod, n in saved[5]:
                 mod._pending_batches = n
@@ -266,6 +274,8 @@ class GraphedTrainStep:
             from .utils.metrics import t_get_confusion_matrix
             final = out[-1] if isinstance(out, (tuple, list)) else out
             t_get_confusion_matrix(final.detach(), self.lbl, self.confusion)
+            if self.tracker is not None:
+                self.tracker.step(self.confusion)
 
     # ------------------------------------------------------------------------------------------------ replay
     def __call__(self, img, lbl):

@@ -14,10 +14,12 @@ parallelism (absent in the reference) shards frames by rank and averages gradien
 The dataset is any ``torch.utils.data.Dataset`` yielding ``(img float[3,H,W], lbl int[H,W], metadata)`` like
 datasets/Dataset_from_df.py:69; the CaDIS cv2/PIL pipeline itself is outside the accelerated path.
 """
+import copy
 import datetime
 import json
 import pathlib
 
+import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
@@ -32,7 +34,14 @@ DEFAULTS = {"mode": "training", "debugging": False, "log_every_n_epochs": 100, "
             "gpu_device": 0, "seed": 0, "tta": False, "log_path": "logs"}
 TRAIN_DEFAULTS = {"epochs": 50, "lr_fct": "exponential", "lr_batchwise": False, "lr_restarts": [], "lr_restart_vals": 1,
                   "lr_params": None, "learning_rate": 1e-4}
-DATA_DEFAULTS = {"batch_size": 10, "num_workers": 0, "experiment": 1}
+DATA_DEFAULTS = {"batch_size": 10, "num_workers": 0, "experiment": 1,
+                 # the per-epoch loader schedule (utils/defaults.py:366-375 of the reference): [start, stop) epochs per loader type
+                 "weighted_random": [0, 0], "weighted_random_mode": "v1", "oversampling": [0, 0], "oversampling_frac": 0.2,
+                 "oversampling_preset": "default", "adaptive_batching": [0, 0], "adaptive_sel_size": 10, "adaptive_iou_update": 1,
+                 "repeat_factor": [0, 0], "repeat_factor_freq_thresh": 0.2,
+                 # build-side keys: the [frames, 36] class pixel table of the training set (None: train_set.label_table, or a census of
+                 # train_set.raw_labels()), and how many steps the adaptive sampler's IoU may lag behind (utils.IoUTracker)
+                 "label_table": None, "adaptive_iou_lag": 0}
 
 
 def _item(v):
@@ -62,7 +71,7 @@ def merge_defaults(config):
     cfg = dict(DEFAULTS)
     cfg.update(config)
     for key, dflt in (("train", TRAIN_DEFAULTS), ("data", DATA_DEFAULTS)):
-        merged = dict(dflt)
+        merged = copy.deepcopy(dflt)                   # (the schedule's lists are extended in place: never the defaults' own)
         merged.update(cfg.get(key, {}))
         cfg[key] = merged
     if "loss" not in cfg:
@@ -119,6 +128,9 @@ class BaseManager:
         elif self.config["mode"] not in ("inference", "demo_video_inference"):
             raise ValueError("mode: {} is not recognized".format(self.config["mode"]))
         self.history = []
+        # the per-epoch loader schedule (build_schedule): None = every epoch iterates self.train_loader
+        self.train_schedule, self.data_loaders = None, {}
+        self.iou_tracker = self.adaptive_sampler = self._label_table = self._checkpoint_iou = None
 
     # ------------------------------------------------------------------ construction
     def load_model(self):
@@ -163,6 +175,87 @@ class BaseManager:
         vl = DataLoader(self.valid_set, batch_size=1, shuffle=False) if self.valid_set is not None else None
         return tl, vl
 
+    def class_table(self):
+        """int64 [frames, 36]: pixels per canonical class and training frame -- what the reference reads from data/data.csv.  From, in
+        order: config['data']['label_table'], train_set.label_table, a census of train_set.raw_labels() (utils.label_census: the uint8
+        label maps, counted on the device)."""
+        if self._label_table is None:
+            table = self.config["data"].get("label_table")
+            if table is None:
+                table = getattr(self.train_set, "label_table", None)
+            if table is None and hasattr(self.train_set, "raw_labels"):
+                from ..utils import label_census
+                table = label_census(self.train_set.raw_labels(), 36, device=self.device)
+            if table is None:
+                raise ValueError("a scheduled class-aware train loader needs the [frames, 36] class pixel table of the training set: "
+                                 "config['data']['label_table'], train_set.label_table, or train_set.raw_labels() (the raw uint8 label "
+                                 "maps, for a census on the device)")
+            table = np.asarray(table)
+            if table.ndim != 2 or table.shape != (len(self.train_set), 36):
+                raise ValueError("the class pixel table must be [{}, 36] (one row per training frame), got {}".format(
+                    len(self.train_set), table.shape))
+            self._label_table = table.astype(np.int64)
+        return self._label_table
+
+    def build_schedule(self):
+        """BaseManager.py:198-213 of the reference: self.train_schedule (epoch -> loader name, utils.train_schedule) from the four
+        config['data'] keys adaptive_batching / oversampling / weighted_random / repeat_factor, and one loader per scheduled name in
+        self.data_loaders.  With every key at its default [0, 0] every epoch iterates self.train_loader and nothing else is built."""
+        from ..utils import train_schedule
+        self.train_schedule = train_schedule(self.config["data"], self.config["train"]["epochs"])
+        self.data_loaders = {"train_loader": self.train_loader, "valid_loader": self.valid_loader}
+        for name in sorted(set(self.train_schedule.values()) - {"train_loader"}):
+            self.data_loaders[name] = self.scheduled_loader(name)
+
+    def scheduled_loader(self, name):
+        """BaseManager.py:310-403: the loader `name` of the schedule over self.train_set.  Like loaders(), every loader drops the ragged
+        last batch.  Data parallel: oversampling and repeat-factor streams are the same on every rank and are sharded
+        (dist.ShardedSampler); adaptive batching and weighted random are refused."""
+        from ..utils import (CLASS_REMAP, OVERSAMPLING_PRESETS, AdaptiveBatchSampler, IoUTracker, RepeatFactorSampler, ShuffledIndexList,
+                             class_info, oversampled_indices, presence_of, weighted_random_weights)
+        dc = self.config["data"]
+        bs, workers = dc["batch_size"], dc["num_workers"]
+        if self.world > 1 and name == "train_adaptive_batching_loader":
+            raise ValueError("adaptive batching is refused with WORLD_SIZE > 1: every rank averages the IoU of its own batches and draws "
+                             "from its own numpy generator, so the ranks' batches would neither be disjoint nor follow one IoU")
+        if self.world > 1 and name == "train_weighted_random_loader":
+            raise ValueError("the weighted-random loader is refused with WORLD_SIZE > 1: torch's WeightedRandomSampler draws from each "
+                             "rank's own generator, so the ranks' streams differ and cannot be sharded")
+        table = self.class_table()
+        table_k = class_info(table, self.experiment)
+
+        def shard(sampler):
+            if self.world == 1:
+                return sampler
+            return D.ShardedSampler(sampler, self.rank, self.world, bs, seed=self.config["seed"])
+
+        if name == "train_adaptive_batching_loader":
+            # the tracker follows the network's confusion matrix (UNet and FCN predict the ignore class too: one row and column more);
+            # the sampler takes the experiment's real classes, the leading entries (t_get_mean_iou's `indices`)
+            real = table_k.shape[1]
+            self.iou_tracker = IoUTracker(self.model.num_classes, dc["adaptive_iou_update"], self.device, lag=dc["adaptive_iou_lag"])
+            if self._checkpoint_iou is not None:
+                self.iou_tracker.load_values(self._checkpoint_iou)
+            # (with num_workers > 0 torch draws batches `prefetch_factor * num_workers` ahead of the step, as it does in the reference)
+            self.adaptive_sampler = AdaptiveBatchSampler(table_k, np.array(self.iou_tracker.host()[:real], dtype=np.float32), "1-**2", bs,
+                                                         dc["adaptive_sel_size"], refresh=lambda: self.iou_tracker.host()[:real])
+            return DataLoader(self.train_set, batch_sampler=self.adaptive_sampler, num_workers=workers)
+        if name == "train_oversampling_loader":
+            class_list = OVERSAMPLING_PRESETS[dc["oversampling_preset"]][self.experiment - 1]
+            indices = oversampled_indices(table_k, class_list, dc["oversampling_frac"])
+            return DataLoader(self.train_set, batch_size=bs, sampler=shard(ShuffledIndexList(indices, seed=self.config["seed"])),
+                              drop_last=True, num_workers=workers)
+        if name == "train_weighted_random_loader":
+            weights = weighted_random_weights(table_k, dc["weighted_random_mode"])
+            return DataLoader(self.train_set, batch_size=bs, sampler=torch.utils.data.WeightedRandomSampler(weights, len(self.train_set)),
+                              drop_last=True, num_workers=workers)
+        if name == "train_repeat_factor_loader":
+            remap = CLASS_REMAP[self.experiment]
+            cmap = np.array([next(k for k, raw in remap.items() if j in raw) for j in range(36)], dtype=np.int64)
+            sampler = RepeatFactorSampler(presence_of(table), cmap, sorted(remap), dc["repeat_factor_freq_thresh"])
+            return DataLoader(self.train_set, batch_size=bs, sampler=shard(sampler), drop_last=True, num_workers=0)
+        raise ValueError("Dataloader special type '{}' not recognised".format(name))
+
     # ------------------------------------------------------------------ hooks for the subclasses
     def forward_loss(self, img, lbl):
         """returns (loss, final logits)"""
@@ -183,6 +276,7 @@ class BaseManager:
     # ------------------------------------------------------------------ loops
     def train(self):
         self.train_loader, self.valid_loader = self.loaders()
+        self.build_schedule()
         for self.epoch in range(self.config["train"]["epochs"]):
             self.train_one_epoch()
             if self.valid_loader is not None:
@@ -197,18 +291,28 @@ class BaseManager:
         n = 0
         if getattr(self, "shard_sampler", None) is not None:
             self.shard_sampler.set_epoch(self.epoch + self.start_epoch)
+        # the epoch's loader (OCRNet_Manager.py:72): self.train_loader unless build_schedule() put another one on this epoch
+        loader = self.train_loader
+        if self.train_schedule is not None and self.train_schedule.get(self.epoch, "train_loader") != "train_loader":
+            loader = self.data_loaders[self.train_schedule[self.epoch]]
+        # adaptive batching anywhere in the schedule: every step of every epoch ends with the per-batch IoU average on the device
+        # (OCRNet_Manager.py:114-117; utils.IoUTracker), published to the host behind the step
+        tracker = self.iou_tracker
+        if tracker is not None:
+            tracker.reset()                      # (running_cm starts at zero: so does the matrix the batch differences are taken from)
         # config['train']['hip_graph'] (build-side key, default off): the step -- zero_grad, forward, loss, backward, Adam, confusion matrix --
         # is recorded once per epoch into a hipGraph and replayed (graph.GraphedTrainStep: bit-identical to this loop, one host call per
         # step instead of ~3000 launches); batches of another shape (a ragged last batch) run the loop below
         graphed = None
         use_graph = bool(self.config.get("train", {}).get("hip_graph", False)) and isinstance(self.optimiser, FusedAdam)
-        for batch in self.train_loader:
+        for batch in loader:
             img, lbl = unpack_batch(batch)
             img, lbl = img.to(self.device, non_blocking=True), lbl.to(self.device, non_blocking=True)
             if use_graph and graphed is None:
                 from ..graph import GraphedTrainStep
                 img, lbl = img.float().contiguous(), lbl.long().contiguous()
-                graphed = GraphedTrainStep(self.model, None, self.optimiser, img, lbl, confusion=running_cm, forward_loss=self.forward_loss)
+                graphed = GraphedTrainStep(self.model, None, self.optimiser, img, lbl, confusion=running_cm, forward_loss=self.forward_loss,
+                                           tracker=tracker)
             if graphed is not None and img.shape == graphed.img.shape and lbl.shape == graphed.lbl.shape:
                 loss_sum += graphed(img, lbl)
             else:
@@ -220,7 +324,11 @@ class BaseManager:
                 loss.backward()
                 self.optimiser.step()
                 t_get_confusion_matrix(out.detach(), lbl, running_cm)      # accumulates on the device
+                if tracker is not None:
+                    tracker.step(running_cm)
                 loss_sum += loss.detach()
+            if tracker is not None:
+                tracker.publish()                # K floats on their way to the pinned buffer the next batch's draw reads
             n += 1
             self.global_step += 1
         if graphed is not None:
@@ -463,6 +571,8 @@ class BaseManager:
                  "best_miou": self.metrics["best_miou"], "is_best": is_best}
         if self.scheduler is not None:
             state["scheduler_state_dict"] = self.scheduler.state_dict()
+        if self.iou_tracker is not None:             # the adaptive sampler's per-class IoU averages (metrics['iou_values'] of the reference)
+            state["iou_values"] = self.iou_tracker.iou_values.detach().cpu().numpy()
         name = "chkpt_best.pt" if is_best else "chkpt_epoch_{:03d}.pt".format(state["epoch"])
         torch.save(state, base / name)
 
@@ -483,6 +593,10 @@ class BaseManager:
             if "scheduler_state_dict" in ck:
                 self.scheduler.load_state_dict(ck["scheduler_state_dict"])   # (the reference loads the optimiser dict here: a bug)
             self.start_epoch, self.global_step = ck["epoch"], ck["global_step"]
+            if "iou_values" in ck:                   # (the tracker is built with the schedule: kept for build_schedule if it comes later)
+                self._checkpoint_iou = ck["iou_values"]
+                if self.iou_tracker is not None:
+                    self.iou_tracker.load_values(ck["iou_values"])
         self.best_loss = ck["best_loss"]
         self.metrics["best_miou"] = ck["best_miou"]
 

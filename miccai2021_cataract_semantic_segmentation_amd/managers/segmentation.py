@@ -149,3 +149,9 @@ class SyntheticCataractDataset(Dataset):
         img[0] += (lbl.float() / (self.k + 1)) * 0.5
         img[1] += ((lbl * 7) % (self.k + 1)).float() / (self.k + 1) * 0.5
         return img, lbl, {"index": i}
+
+    def raw_labels(self):
+        """the frames' label maps as uint8, one after the other: what a scheduled class-aware loader takes its class table from
+        (BaseManager.class_table: a census on the device).  The synthetic ids stand in for the raw CaDIS ids."""
+        for i in range(self.n):
+            yield self[i][1].to(torch.uint8).numpy()

@@ -2192,6 +2192,39 @@ def crop_freq_pick(lbl, lut, flips, minv, canvas, px, wq, m53, return_debug=Fals
     return (origin, total, flat) if return_debug else origin
 
 
+def label_census(lbl, nbins=36, lut=None, out=None, accumulate=False):
+    """per-frame class pixel counts of raw label maps (csrc/census.hip): lbl uint8 [B,H,W] (any storage offset: no alignment is asked of
+    the frames), lut uint8 [256] on the device or None = identity.  Returns DEVICE int64 [B, nbins + 1]; the last column holds the pixels
+    whose (table-mapped) value is >= nbins.  out + accumulate=True adds to the counts already there (64-bit dataset totals)."""
+    assert lbl.dtype == torch.uint8 and lbl.dim() == 3 and lbl.is_contiguous() and lbl.is_cuda
+    assert lut is None or (lut.dtype == torch.uint8 and lut.numel() == 256 and lut.is_contiguous() and lut.device == lbl.device)
+    B, H, W = lbl.shape
+    nbins = int(nbins)
+    if out is None:
+        if accumulate:
+            raise ValueError("label_census: accumulate=True needs out=")
+        out = torch.empty((B, max(nbins, 0) + 1), dtype=torch.int64, device=lbl.device)
+    assert out.dtype == torch.int64 and tuple(out.shape) == (B, nbins + 1) and out.is_contiguous() and out.device == lbl.device
+    check(lib.catseg_label_census_u8(ptr(lbl), B, H, W, ptr(lut), nbins, ptr(out), 1 if accumulate else 0, stream()))
+    return out
+
+
+def iou_ema(cm_running, cm_prev, iou_values, update, iou_batch=None):
+    """the per-class IoU of the batch added to cm_running since the last call, and its exponential average (csrc/census.hip; one launch, no
+    host decision: it can be captured): iou_values = float32(1 - update) * iou_values + float32(update) * iou, cm_prev = cm_running.
+    cm_running / cm_prev: int32 [K,K]; iou_values (in/out), iou_batch (optional): float32 [K].  Returns iou_values."""
+    import numpy as np
+    K = cm_running.shape[0]
+    for t in (cm_running, cm_prev):
+        assert t.dtype == torch.int32 and tuple(t.shape) == (K, K) and t.is_contiguous() and t.is_cuda
+    for t in (iou_values, iou_batch):
+        assert t is None or (t.dtype == torch.float32 and t.numel() == K and t.is_contiguous() and t.device == cm_running.device)
+    a = float(update)
+    check(lib.catseg_iou_ema(ptr(cm_running), ptr(cm_prev), K, float(np.float32(1 - a)), float(np.float32(a)), ptr(iou_values), ptr(iou_batch),
+                             stream()))
+    return iou_values
+
+
 def resize_nearest(src, Ho, Wo, flip=0, out=None, accumulate=False, divide_by=0.0):
     """NHWC nearest resize (F.interpolate(mode='nearest', size=(Ho, Wo))); flip 1 = flip the source, 2 = flip the result"""
     B, Hi, Wi, C = src.shape

@@ -8,6 +8,9 @@ from .egress import (GpuEgress, clipped_argmax, get_cadis_colormap, get_remapped
                      network_lut, palette_table, to_comb_image)
 from .lr_functions import LRFcts  # noqa: F401
 from .sampling import RepeatFactorSampler, class_repeat_factors, image_repeat_factors  # noqa: F401
+from .census import IoUTracker, class_info, class_sums_of, label_census, presence_of  # noqa: F401
+from .class_sampling import (OVERSAMPLING_PRESETS, AdaptiveBatchSampler, ShuffledIndexList, oversampled_indices, train_schedule,  # noqa: F401
+                             weighted_random_weights)
 
 
 def __getattr__(name):  # metrics need the HIP library: import lazily so CPU-only tooling can use the rest

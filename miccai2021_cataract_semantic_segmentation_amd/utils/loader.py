@@ -156,6 +156,11 @@ class PinnedFrameLoader:
         labels_remapped: per member of a two-member BalancedConcatDataset, whether its label maps hold network ids already
         (DatasetFromDF(labels_remaped=True), datasets/Dataset_from_df.py:49-53); (False, True) is the one form taken: labelled, then pseudo.
         pseudo_colorjitter: the strength s in {1, 2, 3} of the 'pseudo_colorjitter' keyword (utils/utils.py:419-436; True = the default 2)"""
+        from .class_sampling import AdaptiveBatchSampler
+        if isinstance(sampler, AdaptiveBatchSampler):
+            raise ValueError("PinnedFrameLoader: adaptive batches are refused -- this loader fills its batches `prefetch` steps ahead, so a "
+                             "batch would be drawn before the IoU of the steps in front of it exists; use torch's DataLoader("
+                             "batch_sampler=...) as the manager does")
         self.dataset, self.batch, self.drop_last = dataset, int(batch_size), drop_last
         self.paired = isinstance(dataset, BalancedConcatDataset)
         if self.paired or labels_remapped is not None:

@@ -18,7 +18,8 @@ def t_get_confusion_matrix(prediction, target, existing_matrix=None, no_ignore_c
         lbl = target.reshape(-1)
         if lbl.dtype != torch.int64:
             lbl = lbl.long()
-        if not (no_ignore_class and K in (17, 25)) and int(lbl.max()) >= K:
+        # (the check reads the labels back: not inside a stream capture, whose warm-up steps ran it on the same batch)
+        if not (no_ignore_class and K in (17, 25)) and not torch.cuda.is_current_stream_capturing() and int(lbl.max()) >= K:
             raise RuntimeError("label >= num_classes (one_hot would raise in the reference)")
         cm = existing_matrix if existing_matrix is not None else torch.zeros((K, K), dtype=torch.int32, device=prediction.device)
         return ops.confusion_matrix(rows.reshape(-1, K), lbl.contiguous(), cm)
