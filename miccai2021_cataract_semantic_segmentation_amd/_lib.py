@@ -290,6 +290,20 @@ for _name, (_res, _args) in _SIGS_CENSUS.items():
     _fn.restype = _res
     _fn.argtypes = _args
 
+# the fused optimiser updates: Adam / AdamW / SGD with parameter groups, and the global gradient norm (include/ext/optim/catseg_optim.h)
+_SIGS_OPTIM = {
+    "catseg_optim_hyper": (None, [I, F, F, F, F, I, P, P, P]),
+    "catseg_adam_step_ex": (I, [P, P, P, P, P, L, P, I, P, P, F, F, F, I, P, P]),
+    "catseg_sgd_step": (I, [P, P, P, L, P, I, P, P, F, I, I, P, P]),
+    "catseg_grad_norm_workspace": (SZ, [L]),
+    "catseg_grad_norm": (I, [P, L, F, P, F, P, SZ, P, P]),
+    "catseg_optim_grid_cap": (I, []),
+}
+for _name, (_res, _args) in _SIGS_OPTIM.items():
+    _fn = getattr(lib, _name)
+    _fn.restype = _res
+    _fn.argtypes = _args
+
 if os.environ.get("CATSEG_SYNC"):  # debugging aid: synchronise after every entry point so a device fault names its launch
     class _SyncLib:
         def __init__(self, inner):

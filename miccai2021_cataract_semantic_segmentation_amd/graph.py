@@ -27,7 +27,8 @@ stream -- the tape holds a parallel region's 'gradient ready' signals back until
     graph 1: backward of the next HRNet modules ... second cut                  -> all_reduce(...)                    [comm stream]
     ...
     graph n: rest of the backward pass (stem)                                   -> all_reduce(tail bucket), wait for all of them
-    tail graph: Adam (reads the reduced gradients; 1/world folded in), confusion matrix
+    tail graph: the optimiser -- its gradient-norm launches, if it clips, then the update -- (reads the reduced gradients; 1/world
+    folded in), confusion matrix
 
 Each replay is one hipGraphLaunch on the launch stream; each all_reduce is ordered behind the launch stream's position at its call (the
 process group's event hand-over) and runs beside the next segment.  All segments allocate from ONE private pool and are replayed in
@@ -39,7 +40,7 @@ import torch
 
 from . import engine
 from . import plan as _plan
-from .optim import FusedAdam
+from .optim import FusedOptimizer
 
 
 def default_segment_bytes():
@@ -91,18 +92,19 @@ class GraphedTrainStep:
     def __init__(self, model, loss_fn, optimiser, img, lbl, confusion=None, warmup=2, keep_state=True, forward_loss=None,
                  segment_bytes=None, tracker=None):
         """model: an EngineNet in training mode; loss_fn(model_output, labels) -> scalar loss tensor (or forward_loss(img, labels) ->
-        (loss, final logits), the managers' method, instead of model + loss_fn); optimiser: FusedAdam over the model;
+        (loss, final logits), the managers' method, instead of model + loss_fn); optimiser: a fused optimiser of optim.py over the model;
         img / lbl: a batch of the shapes every later call will have; confusion: optional int32 [K, K] matrix the step accumulates its
         batch's confusion matrix into (the reference's per-step training metric).
         Warm-up: `warmup` eager steps on the capture stream (workspaces, weight images, allocator pools reach their steady state);
-        keep_state restores parameters, Adam moments, step count and every module buffer afterwards, so that the first call of this
+        keep_state restores parameters, the optimiser's state buffers, step count and every module buffer afterwards, so that the first call of this
         object IS step 1 of the run.
         segment_bytes: data parallel only -- see default_segment_bytes(); 0 = never cut (the whole exchange behind the backward pass).
         tracker: optional utils.IoUTracker whose step(confusion) is launched behind the confusion matrix INSIDE the capture (None: the
         captured graph is what it was).  Its device state (cm_prev, the averages) is saved and restored around the warm-up like the
         confusion matrix: the warm-up steps would otherwise leave their batch in the average the first replay starts from."""
-        if not isinstance(optimiser, FusedAdam):
-            raise TypeError("GraphedTrainStep needs optim.FusedAdam (its kernel reads the step-dependent scalars from device memory)")
+        if not isinstance(optimiser, FusedOptimizer):
+            raise TypeError("GraphedTrainStep needs a fused optimiser of optim.py -- FusedAdam, FusedAdamW, FusedSGD -- (their kernels read the "
+                            "step-dependent scalars from device memory)")
         if not model.training:
             raise RuntimeError("GraphedTrainStep captures a TRAINING step: call model.train() first")
         self.model, self.loss_fn, self.opt, self.confusion = model, loss_fn, optimiser, confusion
@@ -119,7 +121,7 @@ class GraphedTrainStep:
         self.lbl = torch.empty_like(lbl).copy_(lbl)
         optimiser.device_hyper()
         fp = model.flat()
-        m, v = optimiser._moments(fp)
+        state = optimiser.state_buffers()
         # Dropout2d, PointSampler: seeded here (the seeding is a host-to-device copy, which a capture cannot hold).  The warm-up steps draw masks: with
         # keep_state the 16-byte states -- non-persistent buffers of the model -- go back with the other buffers below, so that warm-up and
         # capture consume no draw (a capture launches nothing) and the first replay draws what the first eager step would have drawn
@@ -128,7 +130,7 @@ class GraphedTrainStep:
                 mod.ensure_seeded()
         saved = None
         if keep_state:
-            saved = (fp.flat.clone(), m.clone(), v.clone(), [b.clone() for b in model.buffers()], optimiser._steps,
+            saved = (fp.flat.clone(), [b.clone() for b in state], None, [b.clone() for b in model.buffers()], optimiser._steps,
                      [(mod, mod._pending_batches) for mod in model.modules() if isinstance(mod, engine.BatchNorm2d)],
                      None if confusion is None else confusion.clone(), None if tracker is None else tracker.save())
         self.stream = torch.cuda.Stream(device=dev)
@@ -148,8 +150,8 @@ class GraphedTrainStep:
         if saved is not None:
             with torch.no_grad():
                 fp.flat.copy_(saved[0])
-                m.copy_(saved[1])
-                v.copy_(saved[2])
+                for b, s in zip(state, saved[1]):
+                    b.copy_(s)
                 for b, s in zip(model.buffers(), saved[3]):
                     b.copy_(s)
                 if confusion is not None:

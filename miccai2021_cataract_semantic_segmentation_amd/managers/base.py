@@ -26,7 +26,7 @@ from torch.utils.data import DataLoader
 from .. import dist as D
 from .. import losses as _losses
 from .. import models as _models
-from ..optim import FusedAdam
+from ..optim import FusedOptimizer, build_optimiser
 from ..utils import LRFcts
 from ..utils.metrics import t_get_confusion_matrix, t_get_mean_iou, t_get_pixel_accuracy
 
@@ -150,7 +150,8 @@ class BaseManager:
 
     def load_optimiser(self):
         tc = self.config["train"]
-        self.optimiser = FusedAdam(self.model, lr=tc["learning_rate"], grad_scale=self.grad_scale)
+        # config['train']['optimiser'] (build-side key, optim.build_optimiser); without it: Adam(lr), what the reference builds
+        self.optimiser = build_optimiser(self.model, tc.get("optimiser"), tc["learning_rate"], self.grad_scale)
         self.scheduler = torch.optim.lr_scheduler.LambdaLR(self.optimiser, lr_lambda=LRFcts(tc, list(tc["lr_restarts"]), tc["epochs"]))
 
     def loaders(self):
@@ -304,7 +305,7 @@ class BaseManager:
         # is recorded once per epoch into a hipGraph and replayed (graph.GraphedTrainStep: bit-identical to this loop, one host call per
         # step instead of ~3000 launches); batches of another shape (a ragged last batch) run the loop below
         graphed = None
-        use_graph = bool(self.config.get("train", {}).get("hip_graph", False)) and isinstance(self.optimiser, FusedAdam)
+        use_graph = bool(self.config.get("train", {}).get("hip_graph", False)) and isinstance(self.optimiser, FusedOptimizer)
         for batch in loader:
             img, lbl = unpack_batch(batch)
             img, lbl = img.to(self.device, non_blocking=True), lbl.to(self.device, non_blocking=True)

@@ -47,9 +47,9 @@ class FCNManager(DeepLabv3PlusManager):
     by config['train']['lr_decay_gamma'] per epoch (the other managers' polynomial schedule is not used)."""
 
     def load_optimiser(self):
-        from ..optim import FusedAdam
+        from ..optim import build_optimiser
         tc = self.config["train"]
-        self.optimiser = FusedAdam(self.model, lr=tc["learning_rate"], grad_scale=self.grad_scale)
+        self.optimiser = build_optimiser(self.model, tc.get("optimiser"), tc["learning_rate"], self.grad_scale)
         self.scheduler = torch.optim.lr_scheduler.ExponentialLR(self.optimiser, tc["lr_decay_gamma"]) if "lr_decay_gamma" in tc else None
 
 

@@ -2326,6 +2326,56 @@ def adam_step_dev(p, g, m, v, hyper, beta1=0.9, beta2=0.999, eps=1e-8):
         check(lib.catseg_adam_step_dev(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(hyper), beta1, beta2, eps, stream()))
 
 
+# ---- the fused optimiser updates of include/ext/optim/catseg_optim.h.  hyper: the 20 step scalars (catseg_optim_hyper) as a HOST float32
+# tensor (passed by value) or a DEVICE one (read by the kernel: a captured launch replays with what was uploaded); group_map: uint8 per
+# 64-float chunk or None; clip: the float32[2] that grad_norm wrote, or None
+OPTIM_HYPER_FLOATS, OPTIM_MAX_GROUPS = 20, 8
+WD_NONE, WD_COUPLED, WD_DECOUPLED = range(3)
+
+
+def _hyper_args(hyper):
+    if hyper.dtype != torch.float32 or hyper.numel() < OPTIM_HYPER_FLOATS or not hyper.is_contiguous():
+        raise ValueError("the step-scalar row is %d contiguous float32 values" % OPTIM_HYPER_FLOATS)
+    return (None, ptr(hyper)) if hyper.is_cuda else (ptr(hyper), None)
+
+
+def optim_hyper(row, step, beta1, beta2, grad_scale, dampening, lrs, wds):
+    """fill a HOST float32 row with the step scalars of `step` (catseg_optim_hyper); lrs, wds: one value per parameter group"""
+    G = len(lrs)
+    if row.is_cuda or row.dtype != torch.float32 or row.numel() < OPTIM_HYPER_FLOATS or not 1 <= G <= OPTIM_MAX_GROUPS or len(wds) != G:
+        raise ValueError("optim_hyper: a host float32 row of %d values and 1..%d groups" % (OPTIM_HYPER_FLOATS, OPTIM_MAX_GROUPS))
+    lib.catseg_optim_hyper(int(step), beta1, beta2, grad_scale, dampening, G, (ctypes.c_float * G)(*lrs), (ctypes.c_float * G)(*wds), row.data_ptr())
+    return row
+
+
+def adam_step_ex(p, g, m, v, hyper, G=1, group_map=None, vmax=None, beta1=0.9, beta2=0.999, eps=1e-8, wd_mode=WD_NONE, clip=None):
+    nbytes = (28.0 + (8.0 if vmax is not None else 0.0) + (1.0 / 64 if group_map is not None else 0.0)) * p.numel()
+    hh, hd = _hyper_args(hyper)
+    with _Timed("hbm:adam_ex", nbytes):
+        check(lib.catseg_adam_step_ex(ptr(p), ptr(g), ptr(m), ptr(v), ptr(vmax), p.numel(), ptr(group_map), G, hh, hd, beta1, beta2, eps, wd_mode,
+                                      ptr(clip), stream()))
+
+
+def sgd_step(p, g, buf, hyper, G=1, group_map=None, momentum=0.0, nesterov=False, use_wd=False, clip=None):
+    nbytes = (12.0 + (8.0 if buf is not None else 0.0) + (1.0 / 64 if group_map is not None else 0.0)) * p.numel()
+    hh, hd = _hyper_args(hyper)
+    with _Timed("hbm:sgd", nbytes):
+        check(lib.catseg_sgd_step(ptr(p), ptr(g), ptr(buf), p.numel(), ptr(group_map), G, hh, hd, momentum, 1 if nesterov else 0,
+                                  1 if use_wd else 0, ptr(clip), stream()))
+
+
+def grad_norm_workspace(n):
+    return int(lib.catseg_grad_norm_workspace(n))
+
+
+def grad_norm(g, out, work, max_norm, grad_scale=1.0, hyper_dev=None):
+    """out[0] = ||g * grad_scale||_2, out[1] = min(1, max_norm / (out[0] + 1e-6)); two launches, deterministic; work: DEVICE bytes"""
+    with _Timed("hbm:grad_norm", 4.0 * g.numel()):
+        check(lib.catseg_grad_norm(ptr(g), g.numel(), grad_scale, ptr(hyper_dev), max_norm, ptr(work), work.numel() * work.element_size(), ptr(out),
+                                   stream()))
+    return out
+
+
 def add_n_act(terms, relu, out=None):
     """out = act(sum(terms)); terms: up to 4 NHWC tensors of one shape (row strides may differ)"""
     t0 = terms[0]
