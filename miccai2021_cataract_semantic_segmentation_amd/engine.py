@@ -14,6 +14,7 @@ from torch import nn
 
 from . import ops
 from . import plan as _plan
+from .weight_images import WeightImages, network_layers
 
 
 # --------------------------------------------------------------------------- parameter containers
@@ -1274,51 +1275,24 @@ class EngineNet(nn.Module):
         flush_bn_counters(self)
         return super().state_dict(*a, **k)
 
-    def _d3_bank(self):
-        """weight images of the direct 3x3 kernels (ops.Dconv3Bank): every eligible layer of the network, one launch per step"""
+    def weight_images(self):
+        """the network's bank of weight images (weight_images.WeightImages): every direct 3x3, pointwise and gather layer behind the stem"""
         fp = self.flat()
-        bank = getattr(self, "_d3bank", None)
-        h2 = ops._trunk_h2()
-        if bank is None or (bank is not False and (bank.flat is not fp.flat or bank.h2 != h2)):
-            ws = []
-            for m in self.modules():
-                if (isinstance(m, Conv2d) and not m.stem and m.stride[0] == m.stride[1] and m.padding[0] == m.padding[1]
-                        and m.dilation[0] == m.dilation[1] and id(m.weight) in fp.offsets
-                        and ops.d3_layer(m.in_channels, m.out_channels, *m.kernel_size, m.stride[0], m.padding[0], m.dilation[0], m.groups)):
-                    ws.append((m.weight.data, fp.offsets[id(m.weight)]))
-            bank = ops.Dconv3Bank(fp.flat, ws, h2=h2) if ws else False
-            self._d3bank = bank
-        return bank
-
-    def _p1_bank(self):
-        """weight images of the pointwise (1 x 1) layers for csrc/pconv1.hip (ops.P1Bank): every eligible layer, two launches per step"""
-        fp = self.flat()
-        bank = getattr(self, "_p1bank", None)
-        if bank is None or (bank is not False and bank.flat is not fp.flat):
-            ws = []
-            for m in self.modules():
-                if not (isinstance(m, Conv2d) and not m.stem and m.groups == 1 and id(m.weight) in fp.offsets and m.in_channels % 8 == 0
-                        and m.stride[0] == m.stride[1] and m.padding[0] == m.padding[1] and m.dilation[0] == m.dilation[1]):
-                    continue
-                O, I, (kh, kw), st, pd, dl = m.out_channels, m.in_channels, m.kernel_size, m.stride[0], m.padding[0], m.dilation[0]
-                if ops.p1_geometry(kh, kw, st, pd, 1):
-                    if ops.p1_layer(I, O, kh, kw, st, pd, 1) and ops.p1_layer(O, I, kh, kw, st, pd, 1):      # (forward and backward-data images)
-                        ws.append((m.weight.data, fp.offsets[id(m.weight)], 1, 0, 1))
-                elif ops.G1 and not ops.d3_layer(I, O, kh, kw, st, pd, dl, 1):
-                    if ops.g1_dgrad_layer(ops._g1_desc(I, O, kh, kw, st, pd, dl), I, O, kh, kw, st):
-                        ws.append((m.weight.data, fp.offsets[id(m.weight)], st, pd, dl))
-            bank = ops.P1Bank(fp.flat, ws) if ws else False
-            self._p1bank = bank
+        bank = getattr(self, "_wimages", None)
+        if bank is None or bank.stale(fp.flat):
+            convs = [m for m in self.modules() if isinstance(m, Conv2d) and not m.stem]
+            bank = self._wimages = WeightImages(fp.flat, network_layers(fp, convs))
         return bank
 
     def _run(self, x, record):
         stale = self._open_state() if self._open_state is not None else None
         if stale is not None:
             stale.release()             # (planes left over from this network's last recorded forward if it never saw its backward)
-        # what the pass caches between its launches -- split planes, weight images, the bank of head images (whose buffers stay with the
-        # network: a captured step replays into them) -- is the pass's own: its Ctx holds it, and it is current while the pass runs
+        # what the pass caches between its launches -- split planes, weight images made in line, which images of the network's bank are its
+        # own (the bank's buffers stay: a captured step replays into them) -- is the pass's own: its Ctx holds it, current while the pass runs
         cx = Ctx(self.training, record, None)
-        cx.state = ops.PassState(h2w=self.__dict__.setdefault("_h2w_images", {}))
+        bank = self.weight_images()
+        cx.state = ops.PassState(bank)
         self._open_state = weakref.ref(cx.state) if record else None
         ops.set_state(cx.state)
         # The per-step weight images (direct 3x3 kernels: 459 MB written for OCRNet-HRNet-W48, 0.43 ms; pointwise / gather kernels) are not
@@ -1327,30 +1301,20 @@ class EngineNet(nn.Module):
         # hipGraph (replay: 109.1 / 109.2 / 109.7 -> 108.5 / 109.2 / 109.0 ms): in the eager launch loop one more live stream shifts the runtime's
         # round-robin of streams over its four hardware queues, two branch streams of the parallel regions then share a queue and the step
         # LOSES 3 - 5 ms (116.4 / 119.5 against 113.5 / 114.3 ms; per-branch region times 1.9 / 2.7 / 2.7 / 2.7 instead of 2.2 / 2.3 / 2.0 / 2.3 ms).
-        # PREP_ASYNC = False: in line everywhere.
-        banks = []
-        if ops.DCONV3 and ops.PRECISION == "bf16x3" and self.training:
-            banks.append(self._d3_bank())
-        if ops.P1 and ops._trunk_h2() and self.training:
-            banks.append(self._p1_bank())
-        banks = [b for b in banks if b]
-        heads = ops.h2_weight_images_begin(self.flat().flat) and self.training and ops.H2W_BANK
-        if banks or heads:
-            if PREP_ASYNC and x.is_cuda and torch.cuda.is_current_stream_capturing():
-                main = torch.cuda.current_stream(x.device)
-                side = prep_stream(x.device)
-                side.wait_stream(main)          # (behind the optimiser's update of the weights and the last readers of the old images)
-                with torch.cuda.stream(side):
-                    for b in banks:
-                        b.refresh()
-                    if heads:
-                        ops.h2_weight_images_refresh()      # (the head layers' images: in line, in front of their GEMMs, in the launch loop)
-                    ev = torch.cuda.Event()
-                    ev.record(side)
-                ops.images_pending(ev, main)
-            else:
-                for b in banks:
-                    b.refresh()
+        # PREP_ASYNC = False: in line everywhere.  (The head layers' images join on the side stream only, else they are made at their GEMMs.)
+        aside = bool(PREP_ASYNC and x.is_cuda and torch.cuda.is_current_stream_capturing())
+        due = bank.due(self.training, with_heads=aside)
+        if due and aside:
+            main = torch.cuda.current_stream(x.device)
+            side = prep_stream(x.device)
+            side.wait_stream(main)          # (behind the optimiser's update of the weights and the last readers of the old images)
+            with torch.cuda.stream(side):
+                bank.refresh(due)
+                ev = torch.cuda.Event()
+                ev.record(side)
+            ops.images_pending(ev, main)
+        elif due:
+            bank.refresh(due)
         if ops._trunk_h2() and self.training:
             # the per-tensor amax records of this forward pass and of its backward: ONE chunk, zeroed here on the main stream, sized from
             # the previous pass of this network (+25 %: a rollover inside a parallel region would have to be ordered against its siblings)

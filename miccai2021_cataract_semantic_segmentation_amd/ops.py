@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from . import plan as _plan
+from . import weight_images as _wi
 from ._lib import (BnApplyDesc, BnBackwardDesc, ConvBwdDataDesc, ConvBwdWeightDesc, ConvDesc, ConvFwdDesc, OPERANDS_BF16X3, OPERANDS_BF16X3_BLOCKED,
                    OPERANDS_F16X2, OPERANDS_F16X2_BLOCKED, OPERANDS_F32, check, lib, ptr, stream)
 
@@ -234,23 +235,21 @@ class PassState:
     again for the backward, so that passes of several networks in flight never see, overwrite or release each other's operands; callers
     outside the engine (tests, tools) work on the module's default instance."""
 
-    def __init__(self, h2w=None):
+    def __init__(self, bank=None):
         self.last, self.last_dy = _no_planes(), _no_planes()    # planes of the last split activation / output gradient
         self.kept = {}          # recorded forward: planes of every split input, kept for the layer's backward-weight pass
-        self.d3_wimg, self.p1_wimg, self.p1_keep = {}, {}, []   # weight images of the direct / pointwise + gather kernels (and one-layer banks)
-        self.h2w = h2w          # the network's bank of head weight images (the buffers outlive the pass: EngineNet._h2w_images), or None
+        self.inline = {}        # weight images made in line during the pass (weight_images.weight_image: key -> image)
+        self.bank = bank        # the network's bank of weight images (weight_images.WeightImages: its buffers outlive the pass), or None
+        self.refreshed = {}     # family -> entries of the bank its refresh wrote for THIS pass (only those are this pass's images)
         self.images_event = None    # (event, origin stream): the pass's weight images are being written on a side stream
         self.amax_scope = None      # the AmaxScope new_amax() draws from
 
     def release(self):
-        """drops the planes and images (the memory of a finished pass); the head bank's images are no longer those of a running step"""
+        """drops the planes and images (the memory of a finished pass); the bank's images are no longer those of a running step"""
         self.last, self.last_dy = _no_planes(), _no_planes()
         self.kept.clear()
-        self.d3_wimg.clear()
-        self.p1_wimg.clear()
-        del self.p1_keep[:]
-        for e in (self.h2w or {}).values():
-            e["fresh"] = False
+        self.inline.clear()
+        self.refreshed = {}
 
 
 _default_state = _state = PassState()
@@ -441,59 +440,8 @@ def images_ready():
 
 
 def dconv3_weight_image(w, backward_data=False, h2=False):
-    """pre-split weight image of the direct kernel (cached in the current state: one per layer and direction per pass);
-    h2: the two-plane fp16 image and its scale record, (image, record)"""
-    images_ready()
-    key = (w.data_ptr(), bool(backward_data), bool(h2))
-    img = _state.d3_wimg.get(key)
-    if img is None:
-        C = w.shape[0]
-        if h2:       # (layers outside a Dconv3Bank: a one-layer bank over the weight tensor itself)
-            Dconv3Bank(w, [(w, 0)], h2=True).refresh()
-            return _state.d3_wimg[key]
-        img = torch.empty(lib.catseg_dconv3_wimg_bytes(C), dtype=torch.uint8, device=w.device)
-        check(lib.catseg_dconv3_prep(ptr(w), C, 1 if backward_data else 0, ptr(img), stream()))
-        _state.d3_wimg[key] = img
-    return img
-
-
-class Dconv3Bank:
-    """the weight images of every direct-kernel layer of one network, written by ONE launch per step
-    (catseg_dconv3_prep_batch over the flat parameter buffer) instead of two small launches per layer.
-    h2: the two-plane fp16 images of csrc/dconv3_f16x2.hip with their per-layer scale records (amax + image launch)"""
-
-    def __init__(self, flat, weights, h2=False):
-        """weights: [(parameter tensor (a view into flat), offset in floats)] of the eligible 3x3 layers"""
-        import numpy as np
-        self.flat = flat
-        self.h2 = h2
-        rec = np.zeros(2 * len(weights), dtype=[("w", "<i8"), ("img", "<i8"), ("C", "<i4"), ("KC", "<i4"), ("NT", "<i4"), ("dg", "<i4")])
-        off = 0
-        self.slices = []
-        kc, nt = ctypes.c_int(0), ctypes.c_int(0)
-        for i, (w, woff) in enumerate(weights):
-            C = w.shape[0]
-            lib.catseg_dconv3_layout(C, ctypes.byref(kc), ctypes.byref(nt))
-            nbytes = lib.catseg_dconv3_f16x2_wimg_bytes(C) if h2 else lib.catseg_dconv3_wimg_bytes(C)
-            for dg in (0, 1):
-                rec[2 * i + dg] = (woff, off, C, kc.value, nt.value, dg)
-                self.slices.append((w, dg, off, nbytes, 2 * i + dg))
-                off += (nbytes + 255) // 256 * 256
-        self.entries = torch.from_numpy(rec.view(np.uint8).copy()).to(flat.device)
-        self.n = len(rec)
-        self.images = torch.empty(max(off, 256), dtype=torch.uint8, device=flat.device)
-        self.records = torch.zeros(2 * self.n, dtype=torch.int32, device=flat.device) if h2 else None
-
-    def refresh(self):
-        """(re)write every image from the current parameters and publish them to the current state (dconv3_weight_image)"""
-        if self.h2:
-            check(lib.catseg_dconv3_f16x2_prep_batch(ptr(self.flat), self.n, ptr(self.entries), ptr(self.images), ptr(self.records), stream()))
-            for w, dg, off, nbytes, k in self.slices:
-                _state.d3_wimg[(w.data_ptr(), bool(dg), True)] = (self.images[off:off + nbytes], self.records[2 * k:2 * k + 2])
-            return
-        check(lib.catseg_dconv3_prep_batch(ptr(self.flat), self.n, ptr(self.entries), ptr(self.images), stream()))
-        for w, dg, off, nbytes, k in self.slices:
-            _state.d3_wimg[(w.data_ptr(), bool(dg), False)] = self.images[off:off + nbytes]
+    """pre-split weight image of the direct kernel; h2: the two-plane fp16 image and its scale record, (image, record)"""
+    return _wi.weight_image(w, "d3", backward_data, h2=h2)
 
 
 # Pointwise (1 x 1, stride 1) convolutions in split precision with the split in registers (csrc/pconv1.hip): every dense 1 x 1 layer whose
@@ -527,66 +475,9 @@ def _p1_ok(rows, Cin, Cout, kh, kw, stride, pad, dil, groups):
     return P1 and _trunk_h2() and p1_geometry(kh, kw, stride, pad, groups) and rows >= P1_MIN_ROWS and not _b3_wide_1x1(rows, Cout, 1, Cin)
 
 
-_P1_ENTRY = [("w", "<i8"), ("img", "<i8"), ("O", "<i4"), ("I", "<i4"), ("kh", "<i4"), ("kw", "<i4"), ("t", "<i4"), ("ky0", "<i4"), ("kys", "<i4"),
-             ("nky", "<i4"), ("kx0", "<i4"), ("kxs", "<i4"), ("nkx", "<i4"), ("pad", "<i4")]      # csrc/pconv1.hip: P1Entry (64 bytes)
-
-
-def _g1_desc(Cin, Cout, kh, kw, stride, pad, dil):
-    """conv descriptor for the shape-independent queries of the gather launches (csrc/pconv1.hip: catseg_gconv_*)"""
-    return ConvDesc(0, 0, 0, Cin, 0, 0, Cout, kh, kw, stride, pad, dil, Cin, Cout, 0, 1)
-
-
-class P1Bank:
-    """the weight images of every pointwise AND gather layer of one network for csrc/pconv1.hip -- per layer the forward image and the image(s)
-    of backward-data (1 x 1: the transposed image; kh x kw / stride s: one image per input-pixel parity class) -- written by ONE amax + ONE
-    image launch per step over the flat parameter buffer (catseg_pconv1_prep_batch)"""
-
-    def __init__(self, flat, weights):
-        """weights: [(parameter tensor [O, I, kh, kw] (a view into flat), offset in floats, stride, pad, dil)]"""
-        import numpy as np
-        self.flat = flat
-        recs, self.slices, off = [], [], 0
-        for w, woff, stride, pad, dil in weights:
-            O, I, kh, kw = w.shape
-            if kh == 1 and kw == 1 and stride == 1:
-                for t in (0, 1):
-                    nbytes = lib.catseg_pconv1_wimg_bytes(I if t else O, O if t else I)
-                    self.slices.append(((w.data_ptr(), bool(t)), off, nbytes, len(recs)))
-                    recs.append((woff, off, O, I, 1, 1, t, 0, 1, 1, 0, 1, 1, 0))
-                    off += (nbytes + 255) // 256 * 256
-                continue
-            d = _g1_desc(I, O, kh, kw, stride, pad, dil)
-            for bwd in (0, 1):
-                nbytes = lib.catseg_gconv_wimg_bytes(ctypes.byref(d), bwd)
-                buf = np.zeros(4, dtype=_P1_ENTRY)
-                n = lib.catseg_gconv_entries(ctypes.byref(d), bwd, woff, off, buf.ctypes.data)
-                assert n >= 1
-                self.slices.append(((w.data_ptr(), "g", bool(bwd), stride, pad, dil), off, nbytes, len(recs)))
-                recs.extend(tuple(int(v) for v in buf[i]) for i in range(n))
-                off += (nbytes + 255) // 256 * 256
-        rec = np.array(recs, dtype=_P1_ENTRY)
-        self.entries = torch.from_numpy(rec.view(np.uint8).copy()).to(flat.device)
-        self.n = len(rec)
-        self.images = torch.empty(max(off, 256), dtype=torch.uint8, device=flat.device)
-        self.records = torch.zeros(2 * self.n, dtype=torch.int32, device=flat.device)
-
-    def refresh(self):
-        check(lib.catseg_pconv1_prep_batch(ptr(self.flat), self.n, ptr(self.entries), ptr(self.images), ptr(self.records), stream()))
-        for key, off, nbytes, k in self.slices:
-            _state.p1_wimg[key] = (self.images[off:off + nbytes], self.records[2 * k:2 * k + 2])
-
-
 def p1_weight_image(w, transposed=False):
-    """(image, record) of a pointwise layer's weights [O, I, 1, 1] (physical OHWI = [O][I]); layers outside a P1Bank get a one-layer bank"""
-    images_ready()
-    key = (w.data_ptr(), bool(transposed))
-    img = _state.p1_wimg.get(key)
-    if img is None:
-        bank = P1Bank(w, [(w, 0, 1, 0, 1)])
-        bank.refresh()
-        _state.p1_keep.append(bank)
-        img = _state.p1_wimg[key]
-    return img
+    """(image, record) of a pointwise layer's weights [O, I, 1, 1] (physical OHWI = [O][I])"""
+    return _wi.weight_image(w, "p1", transposed)
 
 
 # Gather launches of the same kernels (csrc/pconv1.hip: catseg_gconv_*): dense kh x kw convolutions with stride 1 / 2 whose input carries an
@@ -610,7 +501,7 @@ def _g1_ok(rows, Cin, Cout, kh, kw, stride, pad, dil, groups):
 
 
 def g1_dgrad_layer(desc, Cin, Cout, kh, kw, stride):
-    """backward-data of a gather layer by library support: desc (the layer's descriptor, or _g1_desc's shape-independent one) is a gather
+    """backward-data of a gather layer by library support: desc (the layer's descriptor, or weight_images.gather_desc's shape-independent one) is a gather
     launch, and its parity-class launches are pointwise GEMMs with N = Cin, K = (taps of a class) * Cout (shared by the planner and the
     engine's weight-image bank)"""
     return bool(lib.catseg_gconv_supported(ctypes.byref(desc))
@@ -619,15 +510,7 @@ def g1_dgrad_layer(desc, Cin, Cout, kh, kw, stride):
 
 def g1_weight_image(w, backward_data, stride, pad, dil):
     """(image(s), record) of a gather layer: the forward image, or the stride^2 class images of backward-data back to back"""
-    images_ready()
-    key = (w.data_ptr(), "g", bool(backward_data), stride, pad, dil)
-    img = _state.p1_wimg.get(key)
-    if img is None:
-        bank = P1Bank(w, [(w, 0, stride, pad, dil)])
-        bank.refresh()
-        _state.p1_keep.append(bank)
-        img = _state.p1_wimg[key]
-    return img
+    return _wi.weight_image(w, "g1", backward_data, stride=stride, pad=pad, dil=dil)
 
 
 def pconv1(x, wimg, bias, N, out, accumulate=False, bn_stats=False):
@@ -1011,26 +894,26 @@ def conv_fwd(x, w_ptr_tensor, bias, Cout, kh, kw, stride=1, pad=0, dil=1, out=No
             x._planes = xp
         yrec = new_amax(x.device)
         with _Timed("fwd_d3p", flops):
-            res = dconv3_pl(xp, dconv3_weight_image(w_ptr_tensor, h2=True), None, out=out, bn_stats=bn_stats, out_rec=yrec)
+            res = dconv3_pl(xp, _wi.weight_image(w_ptr_tensor, "d3", h2=True), None, out=out, bn_stats=bn_stats, out_rec=yrec)
         return (res, yrec) if with_yrec else res
     if route in (D3H, D3):
         _refuse_placeholder(x, "the in-kernel-split direct 3x3 kernel")
         rec = amax_of(x) if route == D3H else None
-        wimg = dconv3_weight_image(w_ptr_tensor, h2=rec is not None)
+        wimg = _wi.weight_image(w_ptr_tensor, "d3", h2=rec is not None)
         with _Timed("fwd_d3h" if rec is not None else "fwd_d3", flops):
             res = dconv3(x, wimg, bias, out=out, bn_stats=bn_stats, x_amax=rec)
         return (res, None) if with_yrec else res
     _refuse_placeholder(x, "a convolution forward outside the planes route")
     if route == P1R:
         with _Timed("fwd_p1", flops):
-            res = pconv1(x, p1_weight_image(w_ptr_tensor), bias, Cout, out, bn_stats=bn_stats)
+            res = pconv1(x, _wi.weight_image(w_ptr_tensor, "p1"), bias, Cout, out, bn_stats=bn_stats)
         drop_amax(out)
         return (res, None) if with_yrec else res
     if route == S2P:
         d = make_desc(x.shape, ld_of(x), Cout, ld_of(out), kh, kw, stride, pad, dil)
         if bn_stats:
             part = _bn_part_buffer(3 * ((rows + 255) // 256) * Cout, x.device)
-        wimg = g1_weight_image(w_ptr_tensor, False, stride, pad, dil)
+        wimg = _wi.weight_image(w_ptr_tensor, "g1", stride=stride, pad=pad, dil=dil)
         with _Timed("fwd_s2p", flops):
             check(lib.catseg_gconv_fwd(ctypes.byref(d), ptr(x), ptr(amax_of(x)), ptr(wimg[0]), ptr(wimg[1]), ptr(bias), ptr(out), ptr(part),
                                        part.numel() if part is not None else 0, ctypes.byref(tr) if bn_stats else None,
@@ -1041,13 +924,13 @@ def conv_fwd(x, w_ptr_tensor, bias, Cout, kh, kw, stride=1, pad=0, dil=1, out=No
             kind, operands = "fwd_h2", OPERANDS_F16X2_BLOCKED
             with _Timed("split3", 0.0):
                 xp, xsc = _split3_cached(x, "h2", both=train and not H2T_BLOCKED, keep=train)
-                wp, wsc = split2h_weight_blocked(w_ptr_tensor)
+                wp, wsc = _wi.weight_image(w_ptr_tensor, "h2")
         elif route.kind == "b3":
             blk = route.blocked
             kind, operands, xsc, wsc = "fwd_b3", OPERANDS_BF16X3_BLOCKED if blk else OPERANDS_BF16X3, None, None
             with _Timed("split3", 0.0):
                 xp = _split3_cached(x, "blk" if blk else "planar", both=blk and train, keep=train)
-                wp = split3_weight_blocked(w_ptr_tensor) if blk else split3_weight(w_ptr_tensor)
+                wp = _wi.weight_image(w_ptr_tensor, "b3", blocked=blk)
         else:
             kind, operands, xp, xsc, wp, wsc = "fwd", OPERANDS_F32, x, None, w_ptr_tensor, None
         if operands == OPERANDS_F32:
@@ -1101,7 +984,7 @@ def conv_bwd_data(dy, w, xshape, kh, kw, stride=1, pad=0, dil=1, out=None, accum
                               dy_amax=amax_of(dy) is not None))
     if route in (D3H, D3):
         rec = amax_of(dy) if route == D3H else None
-        wimg = dconv3_weight_image(w, backward_data=True, h2=rec is not None)
+        wimg = _wi.weight_image(w, "d3", True, h2=rec is not None)
         kind = "dgrad_d3h" if rec is not None else "dgrad_d3"
         if bn_src is not None and BN_BWD_FUSE and not accumulate:
             q, stats, gamma, beta = bn_src
@@ -1119,10 +1002,10 @@ def conv_bwd_data(dy, w, xshape, kh, kw, stride=1, pad=0, dil=1, out=None, accum
             dconv3(dy, wimg, None, out=out, accumulate=accumulate, x_amax=rec)
     elif route == P1R:
         with _Timed("dgrad_p1", flops):
-            pconv1(dy, p1_weight_image(w, transposed=True), None, Cin, out, accumulate=accumulate)
+            pconv1(dy, _wi.weight_image(w, "p1", True), None, Cin, out, accumulate=accumulate)
     elif route == S2P:
         d = make_desc(xshape, ld_of(out), Cout, ld_of(dy), kh, kw, stride, pad, dil)
-        wimg = g1_weight_image(w, True, stride, pad, dil)
+        wimg = _wi.weight_image(w, "g1", True, stride=stride, pad=pad, dil=dil)
         with _Timed("dgrad_s2p", flops):
             check(lib.catseg_gconv_bwd_data(ctypes.byref(d), ptr(dy), ptr(amax_of(dy)), ptr(wimg[0]), ptr(wimg[1]), ptr(out),
                                             1 if accumulate else 0, stream()))
@@ -1131,13 +1014,13 @@ def conv_bwd_data(dy, w, xshape, kh, kw, stride=1, pad=0, dil=1, out=None, accum
             kind, operands = "dgrad_h2", OPERANDS_F16X2_BLOCKED
             with _Timed("split3", 0.0):
                 dyp, dysc = _split3_cached_dy(dy, "h2")
-                wtp, wtsc = split2h_weight_t_blocked(w)
+                wtp, wtsc = _wi.weight_image(w, "h2", True)
         elif route.kind == "b3":
             blk = route.blocked
             kind, operands, dysc, wtsc = "dgrad_b3", OPERANDS_BF16X3_BLOCKED if blk else OPERANDS_BF16X3, None, None
             with _Timed("split3", 0.0):
                 dyp = _split3_cached_dy(dy, "blk" if blk else "planar")
-                wtp = split3_weight_t_blocked(w) if blk else split3_weight_t(w)
+                wtp = _wi.weight_image(w, "b3", True, blocked=blk)
         else:
             kind, operands, dyp, dysc, wtp, wtsc = "dgrad", OPERANDS_F32, dy, None, w, None
         if operands == OPERANDS_F32:
@@ -1387,7 +1270,7 @@ def conv_bwd_data_pl(dyp, w, out, accumulate=False, bn_src=None, with_pre=False)
     """backward-data of a trunk 3x3 convolution from the planes of dy; bn_src as in conv_bwd_data: then returns
     (g, (partials, rows, g_record)) for bn_backward_pre(_planes); with_pre as in conv_bwd_data"""
     B, H, W, C = dyp.shape
-    wimg = dconv3_weight_image(w, backward_data=True, h2=True)
+    wimg = _wi.weight_image(w, "d3", True, h2=True)
     flops = 2.0 * B * H * W * C * C * 9
     drop_amax(out)
     if bn_src is not None and BN_BWD_FUSE and not accumulate:
@@ -1616,7 +1499,7 @@ def conv_bwd_data_h2(dyp, dysc, w, xshape, Cout, kh, kw, pad, dil, out, accumula
     drop_amax(out)
     d = make_desc(xshape, ld_of(out), Cout, (Cout + 7) // 8 * 8, kh, kw, 1, pad, dil)
     with _Timed("split3", 0.0):
-        wtp, wtsc = split2h_weight_t_blocked(w)
+        wtp, wtsc = _wi.weight_image(w, "h2", True)
     with _Timed("dgrad_h2", 2.0 * d.B * d.Ho * d.Wo * Cout * Cin * kh * kw):
         _conv_call(ConvBwdDataDesc, d, OPERANDS_F16X2_BLOCKED, dy=dyp, dy_scale=dysc, w=wtp, w_scale=wtsc, dx=out, accumulate=1 if accumulate else 0)
     return out
@@ -2459,15 +2342,12 @@ def conv_fwd_fused(x, w, bias, residual, relu, Cout, kh, kw, stride=1, pad=0, di
                         kind, operands = "fwd_h2", OPERANDS_F16X2_BLOCKED
                         xp, xsc = _split3_cached(xs, "h2") if nb == B else split2h_blocked(xs)
                         if wp is None:
-                            wp = torch.empty((2, kh * kw * Cin // 16, Cout, 16), dtype=torch.int16, device=w.device)
-                            wsc = torch.empty(2, dtype=torch.int32, device=w.device)
-                            check(lib.catseg_split2h_weight_blocked(ptr(w), Cout, kh * kw, Cin, ptr(wp), ptr(wsc), stream()))
+                            wp, wsc = _wi.weight_image(w, "h2", geometry=(Cout, kh * kw, Cin))
                     else:
                         kind, operands, xsc, wsc = "fwd_b3", OPERANDS_BF16X3_BLOCKED, None, None
                         xp = _split3_cached(xs, "blk") if nb == B else split3_blocked(xs)[0]
                         if wp is None:
-                            wp = torch.empty((3, kh * kw * Cin // 16, Cout, 16), dtype=torch.int16, device=w.device)
-                            check(lib.catseg_split3_weight_blocked(ptr(w), Cout, kh * kw, Cin, ptr(wp), stream()))
+                            wp = _wi.weight_image(w, "b3", blocked=True, geometry=(Cout, kh * kw, Cin))
                 with _Timed(kind, flops * xs.shape[0] / B):
                     _conv_call(ConvFwdDesc, d, operands, x=xp, x_scale=xsc, w=wp, w_scale=wsc, residual=rs, y=os_, **epilogue)
             return out
@@ -2516,104 +2396,34 @@ def split2h_blocked(x):
     return blk, scale
 
 
-# Weight images of the head layers (forward: blocked planes; backward-data: the transposed bank's).  Each was amax + split launched in line, in
-# front of its GEMM on the strictly serial head path (~55 us with the launch gaps, six times per step).  Round 6: a layer that took this route
-# once keeps its two image buffers in its network's bank (PassState.h2w), and while a step is being captured into a hipGraph EngineNet._run
-# refreshes them all on the weight-image side stream beside stem + stage 1 (h2_weight_images_refresh: the same hand-over as the trunk's banks,
-# ops.images_ready); everywhere else the images are made in line as before.
-# A bank: (data_ptr, shape, transposed) -> {"w": weights, "planes", "scale", "fresh": made for the RUNNING step by the refresh}
-H2W_BANK = _plan.get("h2w_bank")
+H2W_BANK = _plan.get("h2w_bank")     # head layers keep their image buffers in the network's bank (weight_images.py)
 
 
-def _h2w_entry(w, transposed):
-    O, I, kh, kw = w.shape
-    key = (w.data_ptr(), tuple(w.shape), transposed)
-    bank = _state.h2w
-    e = bank.get(key) if bank is not None else None
-    if e is None:
-        rows = kh * kw * ((O + 15) // 16) if transposed else kh * kw * I // 16
-        e = {"w": w, "planes": torch.empty((2, rows, I if transposed else O, 16), dtype=torch.int16, device=w.device),
-             "scale": torch.empty(2, dtype=torch.int32, device=w.device), "fresh": False}
-        if H2W_BANK and bank is not None and len(bank) < 64:
-            bank[key] = e
-    return e
-
-
-def _h2w_launch(e, transposed):
-    w = e["w"]
-    O, I, kh, kw = w.shape
-    fn = lib.catseg_split2h_weight_t_blocked if transposed else lib.catseg_split2h_weight_blocked
-    check(fn(ptr(w), O, kh * kw, I, ptr(e["planes"]), ptr(e["scale"]), stream()))
-
-
-def h2_weight_images_begin(flat):
-    """a pass of the network whose flat parameter buffer is `flat` starts: nothing in its bank is valid for this step yet, and entries
-    whose weights are not views into `flat` (the buffer was reallocated) go; -> the bank has entries to refresh"""
-    bank, base = _state.h2w, flat.untyped_storage().data_ptr()
-    for key in [k for k, e in bank.items() if e["w"].untyped_storage().data_ptr() != base]:
-        del bank[key]
-    for e in bank.values():
-        e["fresh"] = False
-    return bool(bank)
-
-
-def h2_weight_images_refresh():
-    """(on the weight-image side stream) both images of every head layer seen so far, for the step that starts now"""
-    for (_, _, transposed), e in _state.h2w.items():
-        _h2w_launch(e, transposed)
-        e["fresh"] = True
-
-
+# [O, I, kh, kw] weights (physical OHWI) -> the operand of a GEMM route, forward or (_t) backward-data (the transposed bank); shapes, and which
+# of them a network's bank keeps: weight_images.py.  split2h: (fp16 planes, scale record), I % 16 == 0; split3: bf16 planes, I % 8 == 0
+# (blocked: % 16)
 def split2h_weight_blocked(w):
-    """[O, I, kh, kw] weights (physical OHWI, I % 16 == 0) -> (fp16 planes [2, kh*kw*I/16, O, 16], scale record): forward operand"""
-    e = _h2w_entry(w, False)
-    if e["fresh"]:
-        images_ready()
-    else:
-        _h2w_launch(e, False)
-    return e["planes"], e["scale"]
+    return _wi.weight_image(w, "h2")
 
 
 def split2h_weight_t_blocked(w):
-    """OHWI weights -> (fp16 planes of the transposed bank [2, taps*roundup(O,16)/16, Cin, 16], scale record): backward-data operand"""
-    e = _h2w_entry(w, True)
-    if e["fresh"]:
-        images_ready()
-    else:
-        _h2w_launch(e, True)
-    return e["planes"], e["scale"]
+    return _wi.weight_image(w, "h2", True)
 
 
 def split3_weight_blocked(w):
-    """[O, I, kh, kw] weights (physical OHWI, I % 16 == 0) -> blocked planes [3, kh*kw*I/16, O, 16] (forward operand)"""
-    O, I, kh, kw = w.shape
-    planes = torch.empty((3, kh * kw * I // 16, O, 16), dtype=torch.int16, device=w.device)
-    check(lib.catseg_split3_weight_blocked(ptr(w), O, kh * kw, I, ptr(planes), stream()))
-    return planes
+    return _wi.weight_image(w, "b3", blocked=True)
 
 
 def split3_weight_t_blocked(w):
-    """OHWI weights -> blocked planes of the transposed bank [3, taps*roundup(O,16)/16, Cin, 16] (backward-data operand)"""
-    O, Cin, kh, kw = w.shape
-    planes = torch.empty((3, kh * kw * ((O + 15) // 16), Cin, 16), dtype=torch.int16, device=w.device)
-    check(lib.catseg_split3_weight_t_blocked(ptr(w), O, kh * kw, Cin, ptr(planes), stream()))
-    return planes
+    return _wi.weight_image(w, "b3", True, blocked=True)
 
 
 def split3_weight(w):
-    """[O, I, kh, kw] weights (physical OHWI) -> planes [3, O, kh*kw*I] (forward operand; I % 8 == 0)"""
-    O, I, kh, kw = w.shape
-    planes = torch.empty((3, O, kh * kw * I), dtype=torch.int16, device=w.device)
-    check(lib.catseg_split3(ptr(w), kh * kw * I, O, kh * kw * I, ptr(planes), stream()))
-    return planes
+    return _wi.weight_image(w, "b3")
 
 
 def split3_weight_t(w):
-    """OHWI weights -> planes of the transposed bank [3, Cin, taps, roundup(O, 8)] (backward-data operand)"""
-    O, Cin, kh, kw = w.shape
-    planes = torch.empty((3, Cin, kh * kw, (O + 7) // 8 * 8), dtype=torch.int16, device=w.device)
-    check(lib.catseg_split3_weight_t(ptr(w), O, kh * kw, Cin, ptr(planes), stream()))
-    return planes
+    return _wi.weight_image(w, "b3", True)
 
 
 def conv_fwd_b3(xshape, xp, wp, bias, Cout, kh, kw, stride=1, pad=0, dil=1, out=None, zero_to=0, blocked=False):

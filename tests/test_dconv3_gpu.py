@@ -244,8 +244,9 @@ def test_conv_dispatch_uses_direct_kernel(ops):
 
 
 def test_batched_weight_images_equal_single_prep(ops):
-    """ops.Dconv3Bank (one launch over the flat parameter buffer) writes the images catseg_dconv3_prep writes layer by layer"""
+    """weight_images.WeightImages (one launch over the flat parameter buffer) writes the images catseg_dconv3_prep writes layer by layer"""
     from miccai2021_cataract_semantic_segmentation_amd._lib import lib
+    from miccai2021_cataract_semantic_segmentation_amd.weight_images import WeightImages
     g = torch.Generator().manual_seed(3)
     widths = [48, 96, 48, 192]
     sizes = [c * c * 9 for c in widths]
@@ -255,26 +256,43 @@ def test_batched_weight_images_equal_single_prep(ops):
         o += (n + 63) // 64 * 64 + 64
     flat = torch.randn(o, generator=g).cuda()
     ws = [flat[a:a + n].view(c, 3, 3, c).permute(0, 3, 1, 2) for a, n, c in zip(offs, sizes, widths)]
-    bank = ops.Dconv3Bank(flat, list(zip(ws, offs)))
+    layers = [("d3", w, off, 1, 1, 1) for w, off in zip(ws, offs)]
     ops.release_b3_cache()
-    bank.refresh()
-    got = {k: v.clone() for k, v in ops._state.d3_wimg.items()}
-    ops.release_b3_cache()
-    for w in ws:
-        for dg in (False, True):
-            assert torch.equal(got[(w.data_ptr(), dg, False)], ops.dconv3_weight_image(w, backward_data=dg))
-    ops.release_b3_cache()
-    # the two-plane fp16 bank: every image = fp16 split of w * 2^e with the layer's own exponent e = 14 - floor(log2 max|w|)
-    bank = ops.Dconv3Bank(flat, list(zip(ws, offs)), h2=True)
-    bank.refresh()
-    for w, c in zip(ws, widths):
-        img, rec = ops._state.d3_wimg[(w.data_ptr(), False, True)]
-        amax = float(w.abs().max())
-        e = int(rec.cpu()[1])
-        assert 2.0 ** 14 <= amax * 2.0 ** e < 2.0 ** 15 and img.numel() == lib.catseg_dconv3_f16x2_wimg_bytes(c)
-        v = img.view(torch.float16).float()
-        assert float(v.abs().max()) <= 2.0 ** 15 and bool(torch.isfinite(v).all())
-    ops.release_b3_cache()
+    try:
+        bank = WeightImages(flat, layers, h2=False)
+        st = ops.PassState(bank)
+        ops.set_state(st)
+        bank.refresh()
+        assert st.refreshed["d3"] == 2 * len(ws) and not st.inline
+        got = {(w.data_ptr(), dg): ops.dconv3_weight_image(w, backward_data=dg) for w in ws for dg in (False, True)}
+        assert not st.inline and all(v.data_ptr() == bank.table[("d3", p, dg, False)].data_ptr() for (p, dg), v in got.items()), "the bank's images"
+        ops.set_state(None)         # (the default state has no bank: every lookup makes its image in line, catseg_dconv3_prep)
+        for w in ws:
+            for dg in (False, True):
+                assert torch.equal(got[(w.data_ptr(), dg)], ops.dconv3_weight_image(w, backward_data=dg))
+        ops.release_b3_cache()
+        # the two-plane fp16 bank: every image = fp16 split of w * 2^e with the layer's own exponent e = 14 - floor(log2 max|w|) ...
+        bank = WeightImages(flat, layers, h2=True)
+        st = ops.PassState(bank)
+        ops.set_state(st)
+        bank.refresh()
+        got = {(w.data_ptr(), dg): ops.dconv3_weight_image(w, backward_data=dg, h2=True) for w in ws for dg in (False, True)}
+        assert not st.inline
+        ops.set_state(None)
+        for w, c in zip(ws, widths):
+            img, rec = got[(w.data_ptr(), False)]
+            amax = float(w.abs().max())
+            e = int(rec.cpu()[1])
+            assert 2.0 ** 14 <= amax * 2.0 ** e < 2.0 ** 15 and img.numel() == lib.catseg_dconv3_f16x2_wimg_bytes(c)
+            v = img.view(torch.float16).float()
+            assert float(v.abs().max()) <= 2.0 ** 15 and bool(torch.isfinite(v).all())
+            for dg in (False, True):    # ... and image and record are those of the layer's own one-layer launch
+                one_img, one_rec = ops.dconv3_weight_image(w, backward_data=dg, h2=True)
+                assert one_img.data_ptr() != got[(w.data_ptr(), dg)][0].data_ptr()
+                assert torch.equal(got[(w.data_ptr(), dg)][0], one_img) and torch.equal(got[(w.data_ptr(), dg)][1], one_rec)
+    finally:
+        ops.set_state(None)
+        ops.release_b3_cache()
 
 
 WG_CASES = [(2, 8, 32, 48), (1, 19, 37, 48), (3, 5, 7, 48), (1, 1, 50, 48), (2, 33, 1, 48),

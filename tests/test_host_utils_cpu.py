@@ -196,15 +196,15 @@ def _filled(ops, st, tag):
     st.last.update(key=("last", tag), x=t, planar=t)
     st.last_dy.update(key=("dy", tag), x=t, blk=t)
     st.kept[("kept", tag)] = {"key": ("kept", tag), "x": t, "planar": t, "blk": None, "h2": None, "h2p": None}
-    st.d3_wimg[(tag, False, False)] = t
-    st.p1_wimg[(tag, False)] = (t, t)
-    st.p1_keep.append(object())
+    st.inline[("d3", tag, False, False)] = t
+    st.inline[("p1", tag, False)] = (t, t)
+    st.refreshed = {"d3": 2}
     return t
 
 
 def _is_empty(st):
     return (st.last["x"] is None and st.last["planar"] is None and st.last_dy["x"] is None and st.last_dy["blk"] is None
-            and not st.kept and not st.d3_wimg and not st.p1_wimg and not st.p1_keep)
+            and not st.kept and not st.inline and not st.refreshed)
 
 
 def test_pass_states_release_only_themselves():
@@ -217,14 +217,14 @@ def test_pass_states_release_only_themselves():
         ta, tb, tc = (_filled(ops, st, i) for i, st in enumerate((a, b, c), 1))
         a.release()
         assert _is_empty(a) and not _is_empty(b) and not _is_empty(c)
-        assert b.kept[("kept", 2)]["planar"] is tb and b.d3_wimg[(2, False, False)] is tb and b.p1_wimg[(2, False)][0] is tb
-        assert b.last["planar"] is tb and b.last_dy["blk"] is tb and len(b.p1_keep) == 1
+        assert b.kept[("kept", 2)]["planar"] is tb and b.inline[("d3", 2, False, False)] is tb and b.inline[("p1", 2, False)][0] is tb
+        assert b.last["planar"] is tb and b.last_dy["blk"] is tb and len(b.inline) == 2 and b.refreshed == {"d3": 2}
         td = _filled(ops, default, 9)
         ops.set_state(b)
         assert ops._state is b
         ops.release_b3_cache()
         assert _is_empty(b) and _is_empty(default), "release_b3_cache() releases the current and the default state"
-        assert not _is_empty(c) and c.kept[("kept", 3)]["planar"] is tc and c.d3_wimg[(3, False, False)] is tc, "... and no third one"
+        assert not _is_empty(c) and c.kept[("kept", 3)]["planar"] is tc and c.inline[("d3", 3, False, False)] is tc, "... and no third one"
         ops.set_state(None)
         assert ops._state is default
         del ta, td
@@ -265,36 +265,57 @@ def test_amax_scope_accessors_follow_the_current_state():
 
 
 def test_head_bank_drops_entries_of_a_replaced_flat_buffer():
-    """ops.h2_weight_images_begin: entries whose weights are views into the flat parameter buffer stay (their `fresh` flags cleared), entries
-    of a buffer that has been reallocated go; releasing the pass's state clears the flags again"""
-    from miccai2021_cataract_semantic_segmentation_amd import ops
-
-    def entry(w):
-        return {"w": w, "planes": torch.empty(1), "scale": torch.empty(2), "fresh": True}
-
+    """the ONE rebuild rule of a network's bank of weight images (weight_images.WeightImages, EngineNet.weight_images): a bank built over the
+    flat parameter buffer keeps its head entries from pass to pass and hands back the identical entry on a second lookup; only weights that
+    are views into that buffer enter; releasing the pass's state clears its `refreshed` flag; a network whose flat buffer was replaced gets
+    a new, empty bank from which nothing of the old buffer is reachable"""
+    from miccai2021_cataract_semantic_segmentation_amd import ops, weight_images as wi
+    from miccai2021_cataract_semantic_segmentation_amd.engine import EngineNet
+    assert ops.H2W_BANK, "shipped default expected"
+    launched = []
+    real = wi.head_image_launch
     old, flat = torch.zeros(4096), torch.zeros(4096)
     w_old = old[64:64 + 512].view(8, 1, 1, 64).permute(0, 3, 1, 2)
     w_new = flat[64:64 + 512].view(8, 1, 1, 64).permute(0, 3, 1, 2)
     w_new2 = flat[1024:1024 + 1024].view(16, 1, 1, 64).permute(0, 3, 1, 2)
     alone = torch.zeros(8, 64, 1, 1)
-    bank = {}
-    for w in (w_old, w_new, w_new2, alone):
-        for t in (False, True):
-            bank[(w.data_ptr(), tuple(w.shape), t)] = entry(w)
-    st = ops.PassState(h2w=bank)
+    bank = wi.WeightImages(flat)
     try:
+        wi.head_image_launch = lambda w, t, planes, scale, geometry=None: launched.append((w, t, planes))    # (no device here)
+        ops.set_state(ops.PassState(bank))
+        first = {(id(w), t): wi.weight_image(w, "h2", t) for w in (w_old, w_new, w_new2, alone) for t in (False, True)}
+        assert len(launched) == 8 and not ops._state.refreshed
+        keys = sorted(("h2", w.data_ptr(), tuple(w.shape), t) for w in (w_new, w_new2) for t in (False, True))
+        assert sorted(bank.table) == keys and bank.n["h2"] == 4, "entries of weights outside the flat buffer do not enter"
+        assert all(e[0] is w for e, w in zip(bank.heads, (w_new, w_new, w_new2, w_new2)))
+        ops._state.release()
+        st = ops.PassState(bank)            # the next pass of the same network: the same entries, made in line again (nothing refreshed them)
         ops.set_state(st)
-        assert ops.h2_weight_images_begin(flat) is True
-        assert sorted(bank) == sorted((w.data_ptr(), tuple(w.shape), t) for w in (w_new, w_new2) for t in (False, True))
-        assert all(e["w"] is w for w in (w_new, w_new2) for t in (False, True) for e in [bank[(w.data_ptr(), tuple(w.shape), t)]])
-        assert not any(e["fresh"] for e in bank.values())
-        assert ops._h2w_entry(w_new, True) is bank[(w_new.data_ptr(), tuple(w_new.shape), True)]
-        for e in bank.values():
-            e["fresh"] = True
+        entry = bank.table[("h2", w_new.data_ptr(), tuple(w_new.shape), True)]
+        planes, scale = wi.weight_image(w_new, "h2", True)
+        assert planes is entry[0] and scale is entry[1] and planes is first[(id(w_new), True)][0] and len(launched) == 9
+        assert bank.table[("h2", w_new.data_ptr(), tuple(w_new.shape), True)] is entry and bank.n["h2"] == 4
+        assert wi.weight_image(w_old, "h2", True)[0] is not first[(id(w_old), True)][0] and len(launched) == 10, "not cached"
+        assert bank.due(True, with_heads=True) == ["h2"] and bank.due(True, with_heads=False) == [] and bank.due(False, with_heads=True) == []
+        bank.refresh(["h2"])                # ... or by the refresh: then a lookup launches nothing
+        assert len(launched) == 14 and st.refreshed == {"h2": 4}
+        assert wi.weight_image(w_new, "h2", True)[0] is entry[0] and len(launched) == 14
         st.release()
-        assert len(bank) == 4 and not any(e["fresh"] for e in bank.values())
-        assert ops.h2_weight_images_begin(old) is False and not bank
+        assert not st.refreshed and bank.n["h2"] == 4 and len(bank.table) == 4
+        assert wi.weight_image(w_new, "h2", True)[0] is entry[0] and len(launched) == 15, "a released pass's flag is cleared: in line again"
+        assert not bank.stale(flat) and bank.stale(old) and bank.stale(flat.clone())
+
+        class Net(EngineNet):               # a network whose flat buffer was replaced gets a new, empty bank
+            pass
+        net = Net()
+        net._flatp = type("FP", (), {"flat": flat, "offsets": {}, "ensure": lambda self: self})()
+        net._wimages = bank
+        assert net.weight_images() is bank
+        net._flatp.flat = old
+        fresh = net.weight_images()
+        assert fresh is not bank and fresh is net._wimages and fresh.flat is old and not fresh.table and not fresh.heads and fresh.n["h2"] == 0
     finally:
+        wi.head_image_launch = real
         ops.set_state(None)
 
 

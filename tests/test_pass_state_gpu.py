@@ -8,7 +8,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-COUNTED = ("split2h", "split3", "split3_blocked", "_h2w_launch")
+COUNTED = ("split2h", "split3", "split3_blocked")
 
 
 def _nets():
@@ -31,11 +31,11 @@ def test_interleaved_passes_of_two_networks_match_the_sequential_order():
     The count assertion FAILS on the code before ops.PassState, and that is the defect this test pins: B's forward released the planes and
     images A's forward had kept in module globals, so A's backward split every activation again and built a one-layer image bank per
     layer, and it entered its head images into B's bank."""
-    from miccai2021_cataract_semantic_segmentation_amd import ops
+    from miccai2021_cataract_semantic_segmentation_amd import ops, weight_images as wi
     assert ops.TRUNK == "f16x2" and ops.HEADS == "f16x2" and ops.PLANES and ops.H2W_BANK, "shipped defaults expected"
     saved = (ops.PRECISION, ops.B3_MIN_TAPS, ops.B3_MIN_K, ops.B3_MIN_N, ops.B3_MIN_TILES, ops.B3_MIN_WGRAD_ROWS, ops.DCONV3_MIN_ROWS)
     real = {n: getattr(ops, n) for n in COUNTED}
-    real_d3, real_p1 = ops.Dconv3Bank.refresh, ops.P1Bank.refresh
+    real_refresh, real_head = wi.WeightImages.refresh, wi.head_image_launch
     counts = {}
 
     def counted(name, fn):
@@ -73,12 +73,12 @@ def test_interleaved_passes_of_two_networks_match_the_sequential_order():
         ops.DCONV3_MIN_ROWS = 1
         for n in COUNTED:
             setattr(ops, n, counted(n, real[n]))
-        ops.Dconv3Bank.refresh = counted("Dconv3Bank.refresh", real_d3)
-        ops.P1Bank.refresh = counted("P1Bank.refresh", real_p1)
+        wi.WeightImages.refresh = counted("WeightImages.refresh", real_refresh)
+        wi.head_image_launch = counted("head_image_launch", real_head)      # (here, in the launch loop: every head image is made in line)
         cpu_nets = _nets()
         seq, n_seq, kinds = run(cpu_nets, "f0 b0 f1 b1")
         assert {"fwd_d3p", "dgrad_d3p", "wgrad_d3p", "fwd_h2", "dgrad_h2", "wgrad_h2"} <= kinds, kinds
-        assert n_seq.get("split2h", 0) > 0 and n_seq.get("_h2w_launch", 0) > 0 and n_seq.get("Dconv3Bank.refresh", 0) > 0, n_seq
+        assert n_seq.get("split2h", 0) > 0 and n_seq.get("head_image_launch", 0) > 0 and n_seq.get("WeightImages.refresh", 0) > 0, n_seq
         mix, n_mix, kinds_mix = run(cpu_nets, "f0 f1 b0 b1")
         assert kinds_mix == kinds
         for (o_s, g_s, _), (o_m, g_m, _) in zip(seq, mix):
@@ -93,14 +93,14 @@ def test_interleaved_passes_of_two_networks_match_the_sequential_order():
         for res in (seq, mix):
             for i in (0, 1):
                 net, other = res[i][2], res[1 - i][2]
-                bank, own, foreign = net._h2w_images, net.flat().flat.untyped_storage().data_ptr(), other.flat().flat.untyped_storage().data_ptr()
-                assert bank and len(bank) == len(other._h2w_images)
-                assert all(e["w"].untyped_storage().data_ptr() == own for e in bank.values()), "a head bank holds weights of another buffer"
-                assert not any(e["w"].untyped_storage().data_ptr() == foreign for e in bank.values())
+                bank, own, foreign = net._wimages.heads, net.flat().flat.untyped_storage().data_ptr(), other.flat().flat.untyped_storage().data_ptr()
+                assert bank and len(bank) == len(other._wimages.heads) and net._wimages.flat is net.flat().flat
+                assert all(e[0].untyped_storage().data_ptr() == own for e in bank), "a head bank holds weights of another buffer"
+                assert not any(e[0].untyped_storage().data_ptr() == foreign for e in bank)
     finally:
         for n in COUNTED:
             setattr(ops, n, real[n])
-        ops.Dconv3Bank.refresh, ops.P1Bank.refresh = real_d3, real_p1
+        wi.WeightImages.refresh, wi.head_image_launch = real_refresh, real_head
         (ops.PRECISION, ops.B3_MIN_TAPS, ops.B3_MIN_K, ops.B3_MIN_N, ops.B3_MIN_TILES, ops.B3_MIN_WGRAD_ROWS, ops.DCONV3_MIN_ROWS) = saved
         ops.PROFILE = None
         ops.release_b3_cache()

@@ -202,3 +202,63 @@ def test_gather_launches_vs_float64_conv2d(B, H, W, Cin, Cout, k, stride, pad, d
     refw = wr.grad
     sw = float(refw.abs().max())
     assert float((dw.cpu().double() - refw).abs().max()) <= TOL * sw, (float((dw.cpu().double() - refw).abs().max()), sw)
+
+
+def test_batched_weight_images_equal_single_prep():
+    """weight_images.WeightImages (one amax + one image launch over the flat parameter buffer: catseg_pconv1_prep_batch) writes, for pointwise
+    and gather layers alike, the images and scale records that a layer's own one-layer launch writes (the in-line path of a lookup that
+    misses), in both directions; for the stride-2 layer each of the four parity-class images of backward-data"""
+    _need_gpu()
+    import ctypes
+    import numpy as np
+    from miccai2021_cataract_semantic_segmentation_amd import ops, weight_images as wi
+    from miccai2021_cataract_semantic_segmentation_amd._lib import lib
+    from miccai2021_cataract_semantic_segmentation_amd.weight_images import WeightImages, gather_desc
+    g = torch.Generator().manual_seed(5)
+    shapes = [(256, 1, 1, 64), (64, 1, 1, 256), (96, 3, 3, 48)]          # physical OHWI
+    geo = [(1, 0, 1), (1, 0, 1), (2, 1, 1)]                              # stride, pad, dil
+    sizes = [o * kh * kw * i for o, kh, kw, i in shapes]
+    offs, end = [], 5 * 64
+    for n in sizes:
+        offs.append(end)
+        end += (n + 63) // 64 * 64 + 64
+    flat = (torch.randn(end, generator=g) * 0.05).cuda()
+    ws = [flat[a:a + n].view(*s).permute(0, 3, 1, 2) for a, n, s in zip(offs, sizes, shapes)]
+    assert ops.g1_dgrad_layer(gather_desc(48, 96, 3, 3, 2, 1, 1), 48, 96, 3, 3, 2) and ops.p1_layer(64, 256, 1, 1, 1, 0, 1) and ops.p1_layer(256, 64, 1, 1, 1, 0, 1)
+
+    def look(i, bwd):
+        st, pd, dl = geo[i]
+        return ops.g1_weight_image(ws[i], bwd, st, pd, dl) if i == 2 else ops.p1_weight_image(ws[i], transposed=bwd)
+
+    ops.release_b3_cache()
+    try:
+        bank = WeightImages(flat, [("g1" if i == 2 else "p1", w, off) + geo[i] for i, (w, off) in enumerate(zip(ws, offs))])
+        assert bank.n["p1"] == 2 + 2 + 1 + 4, "1 x 1: two images; 3 x 3 / stride 2: the forward image and four parity classes"
+        st = ops.PassState(bank)
+        ops.set_state(st)
+        bank.refresh()
+        got = {(i, bwd): look(i, bwd) for i in range(3) for bwd in (False, True)}
+        assert not st.inline and len({img.data_ptr() for img, _ in got.values()}) == 6
+        assert all(img.untyped_storage().data_ptr() == bank.images["p1"].untyped_storage().data_ptr() for img, _ in got.values()), "the bank's"
+        ops.set_state(None)         # (the default state has no bank: every lookup makes the layer's images alone)
+        for (i, bwd), (img, rec) in got.items():
+            one_img, one_rec = look(i, bwd)
+            assert one_img.untyped_storage().data_ptr() != img.untyped_storage().data_ptr()
+            assert one_img.numel() == img.numel() and torch.equal(one_rec, rec), (i, bwd)
+            if not (i == 2 and bwd):
+                assert torch.equal(img, one_img), (i, bwd)
+                continue
+            # four parity classes, each in a slot sized for the largest one (catseg_gconv_class_bytes): the image of a class is the
+            # slot's first catseg_pconv1_wimg_bytes(N = Cin, K = taps of the class * Cout) bytes, the rest of the slot is never written
+            d = gather_desc(48, 96, 3, 3, 2, 1, 1)
+            entries = np.zeros(4, dtype=wi._P1_ENTRY)
+            assert lib.catseg_gconv_entries(ctypes.byref(d), 1, 0, 0, entries.ctypes.data) == 4
+            slot = lib.catseg_gconv_class_bytes(ctypes.byref(d))
+            assert img.numel() == 4 * slot and sorted(int(e["nky"]) * int(e["nkx"]) for e in entries) == [1, 2, 2, 4]
+            for c, e in enumerate(entries):
+                used = lib.catseg_pconv1_wimg_bytes(48, int(e["nky"]) * int(e["nkx"]) * 96)
+                assert int(e["img"]) == c * slot and 0 < used <= slot
+                assert torch.equal(img[c * slot:c * slot + used], one_img[c * slot:c * slot + used]), (i, bwd, c)
+    finally:
+        ops.set_state(None)
+        ops.release_b3_cache()
