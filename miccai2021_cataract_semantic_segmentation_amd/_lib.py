@@ -304,6 +304,19 @@ for _name, (_res, _args) in _SIGS_OPTIM.items():
     _fn.restype = _res
     _fn.argtypes = _args
 
+# the running average of the weights, EMA / SWA (include/ext/ema/catseg_ema.h); a table of its own like the two above: _SIGS_EXT is the
+# table of include/ext/*.h proper
+_SIGS_EMA = {
+    "catseg_ema_update": (I, [P, P, L, F, P, P]),
+    "catseg_ema_swap": (I, [P, P, L, P]),
+    "catseg_ema_table": (I, [P, I, P, I, F, P, P]),
+    "catseg_ema_grid_cap": (I, []),
+}
+for _name, (_res, _args) in _SIGS_EMA.items():
+    _fn = getattr(lib, _name)
+    _fn.restype = _res
+    _fn.argtypes = _args
+
 if os.environ.get("CATSEG_SYNC"):  # debugging aid: synchronise after every entry point so a device fault names its launch
     class _SyncLib:
         def __init__(self, inner):

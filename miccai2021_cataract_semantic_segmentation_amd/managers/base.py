@@ -14,6 +14,7 @@ parallelism (absent in the reference) shards frames by rank and averages gradien
 The dataset is any ``torch.utils.data.Dataset`` yielding ``(img float[3,H,W], lbl int[H,W], metadata)`` like
 datasets/Dataset_from_df.py:69; the CaDIS cv2/PIL pipeline itself is outside the accelerated path.
 """
+import contextlib
 import copy
 import datetime
 import json
@@ -26,7 +27,7 @@ from torch.utils.data import DataLoader
 from .. import dist as D
 from .. import losses as _losses
 from .. import models as _models
-from ..optim import FusedOptimizer, build_optimiser
+from ..optim import FusedOptimizer, WeightAverage, average_config, build_average, build_optimiser
 from ..utils import LRFcts
 from ..utils.metrics import t_get_confusion_matrix, t_get_mean_iou, t_get_pixel_accuracy
 
@@ -120,11 +121,15 @@ class BaseManager:
         self.video_set, self.frame_sink = video_set, frame_sink
         self.load_model()
         self.loss = self.optimiser = self.scheduler = None
+        # config['train']['ema'] (build-side key, optim.average_config): a running average of the weights updated behind every optimiser
+        # step, scored by validate(), saved beside the model and loaded by the inference modes.  Without the key nothing is attached.
+        self.ema_cfg, self.average = average_config(self.config["train"].get("ema")), None
         self.labeled_validation = False      # inside _eval_pass(with_loss=True): a SemiSupervisedLoss scores the whole batch as labelled
         if self.config["mode"] == "training":
             self.load_loss()
             torch.manual_seed(self.config["seed"])      # after model construction, as BaseManager.py:104-112
             self.load_optimiser()
+            self.average = build_average(self.model, self.optimiser, self.ema_cfg)
         elif self.config["mode"] not in ("inference", "demo_video_inference"):
             raise ValueError("mode: {} is not recognized".format(self.config["mode"]))
         self.history = []
@@ -388,13 +393,27 @@ class BaseManager:
     def validate(self):
         self.model.eval()
         D.sync_bn_stats(self.model)      # every rank scores (and rank 0 saves) the same running statistics
-        cm, valid_loss = self._eval_pass(self.valid_loader, with_loss=True)
+        # config['train']['ema']: the averaged weights are scored ("ema"; "both": the live ones as well, for the history) -- swapped into
+        # the live model in place.  Data parallel: the averaged running statistics are pooled over ranks like the live ones above (the
+        # parameter shadows are bit-identical across ranks as the parameters are), so that every rank scores what rank 0 saves.
+        which = self.ema_cfg["validate"] if self.average is not None and self.average.ready else "live"
+        live = None
+        if which == "live":
+            cm, valid_loss = self._eval_pass(self.valid_loader, with_loss=True)
+        else:
+            if which == "both":
+                live = self._eval_pass(self.valid_loader, with_loss=True)
+            with self.average.applied():
+                D.sync_bn_stats(self.model)
+                cm, valid_loss = self._eval_pass(self.valid_loader, with_loss=True)
         pa, pac = t_get_pixel_accuracy(cm)
         m_iou, m_ins, m_anat, m_rare = t_get_mean_iou(cm, self.experiment, True, rare=True)
         m_iou, m_ins, m_anat = round(float(m_iou), 4), round(float(m_ins), 4), round(float(m_anat), 4)
         step = [self.epoch + self.start_epoch, self.global_step - 1]
         if self.history:
             self.history[-1].update({"valid_loss": valid_loss, "valid_miou": m_iou})
+            if live is not None:
+                self.history[-1].update({"valid_loss_live": live[1], "valid_miou_live": round(float(t_get_mean_iou(live[0], self.experiment)), 4)})
         if m_iou > self.metrics["best_miou"]:
             self.metrics.update({"best_miou": m_iou, "best_miou_anatomies": m_anat, "best_miou_instruments": m_ins,
                                  "best_miou_rare": float(m_rare), "best_miou_epoch_step": step})
@@ -482,14 +501,20 @@ class BaseManager:
         flush(ring[(n + 1) % 2])
         return n
 
-    def pseudo_label(self, frame_set=None, label_sink=None, threshold=None):
+    def pseudo_label(self, frame_set=None, label_sink=None, threshold=None, weights="live"):
         """Pseudo labels for unlabelled frames, in the form DatasetFromDF(labels_remaped=True) reads (datasets/Dataset_from_df.py:49-53):
         the eval-mode forward as infer() runs it (the model, an Ensemble, or TTA per config['tta']) over every frame of frame_set (items
         (frame float [3, H, W], ...); default: video_set), then utils.GpuEgress with `threshold` and the pad rows of config['demo_crop']
         cropped.  label_sink(index, labels) receives, in order, a uint8 [H, W] map of the experiment's NETWORK ids in which the
         experiment's ignore id marks the pixels whose largest softmax score is below the threshold (utils.clipped_argmax).  The maps
         travel to the host through demo_infer's two-slot pinned ring, beside the next frame's forward pass.  Experiment 1 has no ignore
-        id: a threshold is refused there.  Returns the number of frames."""
+        id: a threshold is refused there.  weights="ema" (a training manager with config['train']['ema']): the frames are labelled with
+        the averaged weights, swapped in for the duration of the call -- the teacher of a mean-teacher loop.  Returns the number of frames."""
+        if weights not in ("live", "ema"):
+            raise ValueError("pseudo_label: weights is 'live' or 'ema', got {!r}".format(weights))
+        if weights == "ema" and self.average is None:
+            raise ValueError("pseudo_label(weights='ema') needs a training manager with config['train']['ema'] (an inference manager loads "
+                             "the averaged weights of its checkpoint by that key's 'infer')")
         frame_set = self.video_set if frame_set is None else frame_set
         if frame_set is None or not callable(label_sink):
             raise ValueError("pseudo_label needs frame_set= (or video_set) and a callable label_sink(index, labels)")
@@ -499,7 +524,8 @@ class BaseManager:
         flags = {f: getattr(self.model, f) for f in ("get_intermediate", "get_features") if hasattr(self.model, f)}
         was_training = self.model.training
         try:
-            return self._pseudo_label(frame_set, label_sink, threshold)
+            with self.average.applied() if weights == "ema" else contextlib.nullcontext():
+                return self._pseudo_label(frame_set, label_sink, threshold)
         finally:                                     # a training manager goes on training: (interm, final) outputs, train mode
             for f, v in flags.items():
                 setattr(self.model, f, v)
@@ -556,7 +582,7 @@ class BaseManager:
 
     def load_inference_weights(self):
         """BaseManager.py:649: inference scores this run's 'best' checkpoint (EnsembleManager: its members' own, loaded at construction)"""
-        self.load_checkpoint("best")
+        self.load_checkpoint("best", averaged=bool(self.ema_cfg and self.ema_cfg["infer"]))
 
     # ------------------------------------------------------------------ checkpoints (BaseManager.py:471-529)
     def save_checkpoint(self, is_best):
@@ -574,10 +600,15 @@ class BaseManager:
             state["scheduler_state_dict"] = self.scheduler.state_dict()
         if self.iou_tracker is not None:             # the adaptive sampler's per-class IoU averages (metrics['iou_values'] of the reference)
             state["iou_values"] = self.iou_tracker.iou_values.detach().cpu().numpy()
+        if self.average is not None and self.average.ready:      # the averaged network under the model's own keys, and the averaging record
+            avg = self.average.state_dict()
+            state["ema"] = avg.pop(WeightAverage.META)
+            state["ema_state_dict"] = {k: v.detach().cpu().contiguous() for k, v in avg.items()}
         name = "chkpt_best.pt" if is_best else "chkpt_epoch_{:03d}.pt".format(state["epoch"])
         torch.save(state, base / name)
 
-    def load_checkpoint(self, chkpt_type):
+    def load_checkpoint(self, chkpt_type, averaged=False):
+        """averaged (the inference modes): the model takes the checkpoint's 'ema_state_dict' where it has one"""
         names = sorted(f.name for f in (self.log_dir / "chkpts").iterdir())
         name = "chkpt_best.pt"
         if chkpt_type == "best":
@@ -588,7 +619,7 @@ class BaseManager:
                 raise ValueError("No checkpoint of type 'last' found.")
             name = names[-1]
         ck = torch.load(str(self.log_dir / "chkpts" / name), map_location=self.device, weights_only=False)
-        self.model.load_state_dict(ck["model_state_dict"], strict=False)
+        self.model.load_state_dict(ck["ema_state_dict"] if averaged and "ema_state_dict" in ck else ck["model_state_dict"], strict=False)
         if self.config["mode"] == "training":
             self.optimiser.load_state_dict(ck["optimiser_state_dict"])
             if "scheduler_state_dict" in ck:
@@ -598,6 +629,11 @@ class BaseManager:
                 self._checkpoint_iou = ck["iou_values"]
                 if self.iou_tracker is not None:
                     self.iou_tracker.load_values(ck["iou_values"])
+            if self.average is not None:             # (behind the optimiser's state: the count continues from the step count it restored)
+                if "ema_state_dict" in ck:
+                    self.average.load_state_dict(dict(ck["ema_state_dict"], **{WeightAverage.META: ck["ema"]}))
+                else:
+                    self.average.reset()
         self.best_loss = ck["best_loss"]
         self.metrics["best_miou"] = ck["best_miou"]
 

@@ -2259,6 +2259,43 @@ def grad_norm(g, out, work, max_norm, grad_scale=1.0, hyper_dev=None):
     return out
 
 
+# ---- the running average of the weights (include/ext/ema/catseg_ema.h).  w: a float (passed by value) or a DEVICE float32 tensor whose
+# first element the kernel reads (a captured launch replays with what was uploaded)
+EMA_LERP, EMA_SWAP = 0, 1
+EMA_ENTRY = [("live", "<i8"), ("shadow_off", "<i8"), ("n", "<i4"), ("pad", "<i4")]      # csrc/ema.hip: EmaEntry (24 bytes)
+
+
+def _ema_weight(w):
+    if torch.is_tensor(w):
+        if not w.is_cuda or w.dtype != torch.float32 or w.numel() < 1:
+            raise ValueError("the weight is a number or a DEVICE float32 tensor")
+        return 0.0, ptr(w)
+    return float(w), None
+
+
+def ema_update(p, avg, w):
+    """avg = lerp(avg, p, w) over two flat float32 buffers of one length (torch.lerp's two-sided form; w = 1 copies p)"""
+    if avg.numel() != p.numel():
+        raise ValueError("ema_update: p and avg differ in length")
+    wh, wd = _ema_weight(w)
+    with _Timed("hbm:ema", 12.0 * p.numel()):
+        check(lib.catseg_ema_update(ptr(p), ptr(avg), p.numel(), wh, wd, stream()))
+
+
+def ema_swap(a, b):
+    """exchanges two flat float32 buffers of one length in place"""
+    if a.numel() != b.numel():
+        raise ValueError("ema_swap: a and b differ in length")
+    with _Timed("hbm:ema_swap", 16.0 * a.numel()):
+        check(lib.catseg_ema_swap(ptr(a), ptr(b), a.numel(), stream()))
+
+
+def ema_table(entries, count, shadow, mode, w=0.0):
+    """one launch over a DEVICE table of EMA_ENTRY records: mode EMA_LERP shadow = lerp(shadow, live, w), mode EMA_SWAP exchanges the two"""
+    wh, wd = _ema_weight(w)
+    check(lib.catseg_ema_table(ptr(entries), count, ptr(shadow), mode, wh, wd, stream()))
+
+
 def add_n_act(terms, relu, out=None):
     """out = act(sum(terms)); terms: up to 4 NHWC tensors of one shape (row strides may differ)"""
     t0 = terms[0]

@@ -2,7 +2,11 @@
 
 FusedAdam with its constructor arguments of old is torch.optim.Adam(lr) as built at managers/BaseManager.py:441 of the reference and
 launches catseg_adam_step / catseg_adam_step_dev (include/catseg.h).  Weight decay (coupled or decoupled), amsgrad, parameter groups,
-momentum SGD and clipping by the global gradient norm run on the kernels of include/ext/optim/catseg_optim.h."""
+momentum SGD and clipping by the global gradient norm run on the kernels of include/ext/optim/catseg_optim.h.  WeightAverage keeps a
+running average of the weights (EMA / SWA, torch.optim.swa_utils.AveragedModel's arithmetic) in a shadow of the flat buffer: one launch
+of include/ext/ema/catseg_ema.h behind the update."""
+import contextlib
+
 import numpy as np
 import torch
 
@@ -10,6 +14,9 @@ from . import ops
 from .engine import FlatParams
 
 MAX_GROUPS = ops.OPTIM_MAX_GROUPS
+# the row device_hyper() uploads: the CATSEG_OPTIM_HYPER_FLOATS entries the optimiser kernels read, then the weight of the running average
+AVERAGE_SLOT = ops.OPTIM_HYPER_FLOATS
+HYPER_ROW_FLOATS = ops.OPTIM_HYPER_FLOATS + 4
 
 
 def chunk_group_map(offsets, sizes, groups, total, align=FlatParams.ALIGN):
@@ -124,6 +131,7 @@ class FusedOptimizer(torch.optim.Optimizer):
         self._map = self._map_key = None
         self._hyper_dev = self._hyper_host = None      # device_hyper(): the step-dependent scalars live in device memory
         self._row = torch.zeros(ops.OPTIM_HYPER_FLOATS, dtype=torch.float32)
+        self._avg = None                               # attach_average(): the running average updated behind every step
 
     def zero_grad(self, set_to_none=True):
         """The backward tape OVERWRITES each parameter's slice of the flat gradient buffer (it does not accumulate over
@@ -155,7 +163,24 @@ class FusedOptimizer(torch.optim.Optimizer):
 
     def state_buffers(self):
         """every flat state tensor of this optimiser (what a snapshot of the training state has to hold besides `_steps`)"""
-        return self._state(self.model.flat())
+        own = self._state(self.model.flat())
+        return own if self._avg is None else own + self._avg.buffers()
+
+    def attach_average(self, avg):
+        """avg: a WeightAverage over this optimiser's model (None detaches).  Every step() launches its update behind the parameter
+        update, on the same stream; its shadows join state_buffers(); its update count follows this optimiser's step count."""
+        if avg is not None:
+            if not isinstance(avg, WeightAverage) or avg.model is not self.model:
+                raise ValueError("attach_average takes a WeightAverage over the optimiser's own model")
+            avg._attach(self)
+        elif self._avg is not None:
+            self._avg.optimiser = None
+        self._avg = avg
+        return avg
+
+    def _average(self):
+        if self._avg is not None:
+            self._avg.update()
 
     def _group_map(self, fp):
         """DEVICE uint8 per 64-float chunk, or None with one group"""
@@ -178,7 +203,7 @@ class FusedOptimizer(torch.optim.Optimizer):
         """switch to the device-scalar kernel form (catseg_adam_step_dev, the hyper_dev form of catseg_optim.h); bit-identical updates"""
         if self._hyper_dev is None:
             fp = self.model.flat()
-            n = ops.OPTIM_HYPER_FLOATS
+            n = HYPER_ROW_FLOATS
             self._hyper_host = torch.zeros((16, n), dtype=torch.float32).pin_memory()     # a ring: the host may run steps ahead of the GPU
             self._hyper_events = [None] * 16
             self._hyper_dev = torch.zeros(n, dtype=torch.float32, device=fp.flat.device)
@@ -192,6 +217,8 @@ class FusedOptimizer(torch.optim.Optimizer):
             self._hyper_events[slot].synchronize()         # (the copy that last read this pinned slot, 16 steps ago)
         row = self._hyper_host[slot]
         self._fill_hyper(row)
+        if self._avg is not None:
+            row[AVERAGE_SLOT] = self._avg.weight()     # (behind the entries the optimiser kernels read)
         self._hyper_dev.copy_(row, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
@@ -313,10 +340,12 @@ class FusedAdam(FusedOptimizer):
                     self._steps += 1
                     self.upload_hyper()
                 ops.adam_step_dev(fp.flat, fp.grad, m, v, self._hyper_dev, g["betas"][0], g["betas"][1], g["eps"])
+                self._average()
                 return
             self._steps += 1
             ops.adam_step(fp.flat, fp.grad, m, v, float(g["lr"]), self._steps, g["betas"][0], g["betas"][1], g["eps"],
                           self.grad_scale)
+            self._average()
             return
         hyper = self._advance()
         clip = self._clip(fp, hyper)
@@ -326,6 +355,7 @@ class FusedAdam(FusedOptimizer):
         ops.adam_step_ex(fp.flat, fp.grad, m, v, hyper, G=len(self.param_groups), group_map=self._group_map(fp),
                          vmax=state[2] if len(state) > 2 else None, beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], wd_mode=wd_mode,
                          clip=clip)
+        self._average()
 
     def _state_entry(self, views):
         return dict({"step": torch.tensor(float(self._steps))}, **views)
@@ -399,6 +429,7 @@ class FusedSGD(FusedOptimizer):
         ops.sgd_step(fp.flat, fp.grad, state[0] if state else None, hyper, G=len(self.param_groups), group_map=self._group_map(fp),
                      momentum=float(g["momentum"]), nesterov=bool(g["nesterov"]), use_wd=any(q["weight_decay"] for q in self.param_groups),
                      clip=clip)
+        self._average()
 
     def _state_entry(self, views):
         return views if views else None
@@ -460,3 +491,265 @@ def build_optimiser(model, cfg, lr, grad_scale=1.0):
         groups = param_groups(model, wd, no_decay=tuple(cfg.get("no_decay") or ()), lr_mult=cfg.get("lr_mult"))
     cls = {"Adam": FusedAdam, "AdamW": FusedAdamW, "SGD": FusedSGD}[name]
     return cls(model, lr=lr, groups=groups, max_grad_norm=cfg.get("clip_grad_norm"), grad_scale=grad_scale, **kw)
+
+
+# ---------------------------------------------------------------------- the running average of the weights (EMA / SWA)
+AVERAGE_MODES = ("ema", "swa")
+
+
+def average_weight(n, mode="ema", decay=0.999, warmup=False):
+    """the weight w of update number n + 1 (n = updates already done, AveragedModel's n_averaged in front of the update) in
+    avg = lerp(avg, p, w), in double: 1 for the first update (a copy); 'ema': 1 - decay as torch.optim.swa_utils.get_ema_multi_avg_fn,
+    with warmup 1 - min(decay, (1 + n) / (10 + n)); 'swa': 1 / (n + 1), AveragedModel's default (the equal-weight average)."""
+    n = int(n)
+    if n < 0:
+        raise ValueError("average_weight: n counts the updates already done")
+    if mode not in AVERAGE_MODES:
+        raise ValueError("average_weight: mode is one of %s, got %r" % (list(AVERAGE_MODES), mode))
+    if n == 0:
+        return 1.0
+    if mode == "swa":
+        return 1.0 / (n + 1.0)
+    d = float(decay)
+    if warmup:
+        d = min(d, (1.0 + n) / (10.0 + n))
+    return 1.0 - d
+
+
+class WeightAverage:
+    """A running average of a network's weights, kept beside the live ones: torch.optim.swa_utils.AveragedModel's arithmetic
+    (get_ema_multi_avg_fn(decay) for mode 'ema', the default equal-weight average for 'swa', use_buffers = `buffers`) without a second
+    network.  It owns a zero-initialised shadow of model.flat().flat and, with buffers=True, one packed shadow of the running_mean /
+    running_var of every BatchNorm module with the device table catseg_ema_table walks; num_batches_tracked is not averaged and the
+    generator states of Dropout2d / PointSampler are never touched.
+
+    optimiser.attach_average(avg): every step() launches avg = lerp(avg, p, w) behind the parameter update.  The count of updates is
+    derived from the optimiser's step count (n_averaged = steps since the attachment - start_step, never below 0), so whatever saves
+    and restores the optimiser's `_steps` and state_buffers() -- graph.GraphedTrainStep's warm-up -- covers the average too.  Steps up
+    to start_step run with w = 1: the shadow tracks the weights.
+
+    applied(): swaps the averaged weights (and statistics) into the live model in place for the duration of a `with` block: the flat
+    buffer, the weight-image bank and captured graphs keep their pointers; an eval pass builds its weight images in line from what the
+    flat buffer holds, the next training pass refreshes its images as every step does."""
+    META = "_average"           # state_dict(): the key of the averaging record beside the model's own keys
+
+    def __init__(self, model, decay=0.999, mode="ema", warmup=False, start_step=0, buffers=True):
+        if mode not in AVERAGE_MODES:
+            raise ValueError("WeightAverage: mode is one of %s, got %r" % (list(AVERAGE_MODES), mode))
+        if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= decay < 1.0:
+            raise ValueError("WeightAverage: decay is a number in [0, 1), got %r" % (decay,))
+        if isinstance(start_step, bool) or not isinstance(start_step, int) or start_step < 0:
+            raise ValueError("WeightAverage: start_step is a non-negative integer, got %r" % (start_step,))
+        self.model, self.mode, self.decay, self.warmup = model, mode, float(decay), bool(warmup)
+        self.start_step, self.use_buffers = start_step, bool(buffers)
+        self.optimiser = None
+        self._origin = 0            # the optimiser's step count at this average's step 0
+        self._loaded_steps = 0      # steps a loaded state had behind it (applied at the attachment)
+        self.shadow = self.buf_shadow = self._table = None
+        self._count, self._key, self._slices, self._bns = 0, None, [], None
+        self._swapped = False
+
+    # ------------------------------------------------------------------ the count and the weight
+    def _attach(self, optimiser):
+        self.optimiser = optimiser
+        self._origin = optimiser._steps - self._loaded_steps
+
+    @property
+    def steps(self):
+        """optimiser steps this average has seen (those of the tracking phase included)"""
+        return 0 if self.optimiser is None else self.optimiser._steps - self._origin
+
+    @property
+    def n_averaged(self):
+        return max(0, self.steps - self.start_step)
+
+    @property
+    def ready(self):
+        """the shadows hold weights (at least one update ran, or a state was loaded)"""
+        return self.steps > 0
+
+    def weight(self):
+        """the weight of the update behind the optimiser step that `steps` counts (float: the kernels take it as float32)"""
+        return average_weight(max(0, self.steps - 1 - self.start_step), self.mode, self.decay, self.warmup)
+
+    def reset(self):
+        """forget the average: zero shadows, the count starts at the optimiser's current step"""
+        for b in self.buffers():
+            b.zero_()
+        self._loaded_steps = 0
+        if self.optimiser is not None:
+            self._origin = self.optimiser._steps
+
+    # ------------------------------------------------------------------ the shadows
+    def _bn_modules(self):
+        if self._bns is None:       # (the selection of dist.sync_bn_stats)
+            self._bns = [(name, m) for name, m in self.model.named_modules()
+                         if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.running_mean is not None] if self.use_buffers else []
+        return self._bns
+
+    def _ensure(self):
+        """the flat parameters; (re)builds the shadows and the table when the flat buffer or a statistics buffer is another tensor
+        (the values are carried along where the sizes still match)"""
+        fp = self.model.flat()
+        if self.shadow is None or self.shadow.numel() != fp.flat.numel() or self.shadow.device != fp.flat.device:
+            new = torch.zeros_like(fp.flat)
+            if self.shadow is not None and self.shadow.numel() == new.numel():
+                new.copy_(self.shadow)
+            self.shadow = new
+        bns = self._bn_modules()
+        if bns:
+            key = (fp.flat.device,) + tuple(t.data_ptr() for _, m in bns for t in (m.running_mean, m.running_var))
+            if key != self._key:
+                rec, slices, off = [], [], 0
+                for name, m in bns:
+                    for attr in ("running_mean", "running_var"):
+                        t = getattr(m, attr)
+                        if t.dtype != torch.float32 or not t.is_contiguous():
+                            raise ValueError("WeightAverage: %s.%s is not a contiguous float32 buffer" % (name, attr))
+                        rec.append((t.data_ptr(), off, t.numel(), 0))
+                        slices.append((name + "." + attr if name else attr, off, t.numel()))
+                        off += t.numel()
+                new = torch.zeros(off, dtype=torch.float32, device=fp.flat.device)
+                if self.buf_shadow is not None and self.buf_shadow.numel() == off:
+                    new.copy_(self.buf_shadow)
+                table = np.array(rec, dtype=ops.EMA_ENTRY)
+                self._table = torch.from_numpy(table.view(np.uint8).copy()).to(fp.flat.device)
+                self.buf_shadow, self._count, self._slices, self._key = new, len(rec), slices, key
+        return fp
+
+    def buffers(self):
+        """the shadows (what a snapshot of the training state has to hold; part of the optimiser's state_buffers())"""
+        self._ensure()
+        return [self.shadow] + ([self.buf_shadow] if self._count else [])
+
+    def update(self):
+        """avg = lerp(avg, live, w) on the current stream: one launch over the flat buffer, one over the statistics table.  The weight
+        goes by value, or -- the optimiser in its device-scalar form -- is read from the row uploaded with the step scalars."""
+        opt = self.optimiser
+        if opt is None:
+            raise RuntimeError("WeightAverage.update(): attach the average to a fused optimiser first (optimiser.attach_average)")
+        if self._swapped:
+            raise RuntimeError("WeightAverage.update() inside applied(): the live model holds the averaged weights")
+        fp = self._ensure()
+        w = opt._hyper_dev[AVERAGE_SLOT:AVERAGE_SLOT + 1] if opt._hyper_dev is not None else self.weight()
+        ops.ema_update(fp.flat, self.shadow, w)
+        if self._count:
+            ops.ema_table(self._table, self._count, self.buf_shadow, ops.EMA_LERP, w)
+
+    # ------------------------------------------------------------------ scoring the average
+    def _swap(self):
+        fp = self._ensure()
+        ops.ema_swap(fp.flat, self.shadow)
+        if self._count:
+            ops.ema_table(self._table, self._count, self.buf_shadow, ops.EMA_SWAP)
+        self._swapped = not self._swapped
+
+    @contextlib.contextmanager
+    def applied(self):
+        """the averaged weights and statistics in the live model, in place, until the block ends (also by an exception)"""
+        if self._swapped:
+            raise RuntimeError("WeightAverage.applied() is not re-entrant")
+        if not self.ready:
+            raise RuntimeError("WeightAverage.applied(): the average holds no weights yet (no optimiser step since it was attached)")
+        fp = self.model.flat()
+        if fp.flat.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("WeightAverage.applied() inside a stream capture: the swap would become part of the captured graph")
+        state = self.model._open_state() if getattr(self.model, "_open_state", None) is not None else None
+        if getattr(self.model, "_last_pass", None) is not None or (state is not None and (state.kept or state.refreshed or state.inline)):
+            raise RuntimeError("WeightAverage.applied() while a recorded forward pass awaits its backward: that pass would read the "
+                               "averaged weights")
+        self._swap()
+        try:
+            yield self
+        finally:
+            self._swap()
+
+    # ------------------------------------------------------------------ (de)serialisation
+    def record(self):
+        return {"n_averaged": self.n_averaged, "steps": self.steps, "mode": self.mode, "decay": self.decay, "warmup": self.warmup,
+                "start_step": self.start_step}
+
+    def state_dict(self):
+        """the averaged network under the model's own state-dict keys (conv weights in their logical OIHW shape; what is not averaged --
+        num_batches_tracked, other buffers -- as the live model holds it), and the averaging record under META"""
+        fp = self._ensure()
+        out = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+        if not self._swapped:       # (inside applied() the live model IS the average)
+            for name, p in self.model.named_parameters():
+                if name in out:
+                    out[name] = FlatParams._view(self.shadow, fp.offsets[id(p)], p).detach().clone().contiguous()
+            for key, off, n in self._slices:
+                if key in out:
+                    out[key] = self.buf_shadow[off:off + n].clone().view(out[key].shape)
+        out[self.META] = self.record()
+        return out
+
+    def load_state_dict(self, sd):
+        """restores the shadows and continues the count: n_averaged (and the position inside the tracking phase) go on from the saved
+        record, whatever step count the optimiser's own state format restored"""
+        meta = sd.get(self.META)
+        if not isinstance(meta, dict) or "n_averaged" not in meta:
+            raise ValueError("WeightAverage.load_state_dict: the state lacks its averaging record (%r)" % self.META)
+        for k in ("mode", "start_step"):        # (what the count means; decay and warmup may change on a resume)
+            if k in meta and meta[k] != getattr(self, k):
+                raise ValueError("WeightAverage.load_state_dict: the state was averaged with %s = %r, this average has %r" % (k, meta[k], getattr(self, k)))
+        if self._swapped:
+            raise RuntimeError("WeightAverage.load_state_dict() inside applied()")
+        fp = self._ensure()
+        with torch.no_grad():
+            for name, p in self.model.named_parameters():
+                if name not in sd:
+                    raise ValueError("WeightAverage.load_state_dict: %r is missing" % name)
+                if tuple(sd[name].shape) != tuple(p.shape):
+                    raise ValueError("WeightAverage.load_state_dict: %r has shape %s, the parameter has %s" % (name, tuple(sd[name].shape), tuple(p.shape)))
+                FlatParams._view(self.shadow, fp.offsets[id(p)], p).copy_(sd[name])
+            for key, off, n in self._slices:
+                if key not in sd:
+                    raise ValueError("WeightAverage.load_state_dict: %r is missing" % key)
+                self.buf_shadow[off:off + n].copy_(sd[key].reshape(-1))
+        n_avg = int(meta["n_averaged"])
+        self._loaded_steps = int(meta["steps"]) if "steps" in meta else (n_avg + self.start_step if n_avg > 0 else 0)
+        if self.optimiser is not None:
+            self._origin = self.optimiser._steps - self._loaded_steps
+
+
+# ---------------------------------------------------------------------- config['train']['ema']
+_AVERAGE_KEYS = {"decay": 0.999, "mode": "ema", "warmup": False, "start_step": 0, "buffers": True, "validate": "ema", "infer": True}
+AVERAGE_VALIDATE = ("ema", "live", "both")
+
+
+def average_config(cfg):
+    """config['train']['ema'] (a build-side key; the reference has no weight averaging) with its defaults filled in:
+    {"decay": 0.999, "mode": "ema" | "swa", "warmup": false, "start_step": 0, "buffers": true, "validate": "ema" | "live" | "both",
+     "infer": true}.  None stays None; unknown keys and ill-typed entries are refused."""
+    if cfg is None:
+        return None
+    if not isinstance(cfg, dict):
+        raise ValueError("config['train']['ema'] is a dictionary")
+    unknown = sorted(set(cfg) - set(_AVERAGE_KEYS))
+    if unknown:
+        raise ValueError("unknown key(s) %s in config['train']['ema']: it takes %s" % (unknown, sorted(_AVERAGE_KEYS)))
+    out = dict(_AVERAGE_KEYS, **cfg)
+    for k in ("warmup", "buffers", "infer"):
+        if not isinstance(out[k], bool):
+            raise ValueError("config['train']['ema'][%r] is true or false, got %r" % (k, out[k]))
+    if isinstance(out["decay"], bool) or not isinstance(out["decay"], (int, float)) or not 0.0 <= out["decay"] < 1.0:
+        raise ValueError("config['train']['ema']['decay'] is a number in [0, 1), got %r" % (out["decay"],))
+    if isinstance(out["start_step"], bool) or not isinstance(out["start_step"], int) or out["start_step"] < 0:
+        raise ValueError("config['train']['ema']['start_step'] is a non-negative integer, got %r" % (out["start_step"],))
+    if out["mode"] not in AVERAGE_MODES:
+        raise ValueError("config['train']['ema']['mode'] is one of %s, got %r" % (list(AVERAGE_MODES), out["mode"]))
+    if out["validate"] not in AVERAGE_VALIDATE:
+        raise ValueError("config['train']['ema']['validate'] is one of %s, got %r" % (list(AVERAGE_VALIDATE), out["validate"]))
+    return out
+
+
+def build_average(model, optimiser, cfg):
+    """the WeightAverage of config['train']['ema'], attached to the optimiser; cfg None: nothing is built or attached"""
+    cfg = average_config(cfg)
+    if cfg is None:
+        return None
+    if not isinstance(optimiser, FusedOptimizer):
+        raise TypeError("config['train']['ema'] needs a fused optimiser of optim.py")
+    avg = WeightAverage(model, decay=cfg["decay"], mode=cfg["mode"], warmup=cfg["warmup"], start_step=cfg["start_step"], buffers=cfg["buffers"])
+    return optimiser.attach_average(avg)
