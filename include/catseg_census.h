@@ -1,5 +1,5 @@
 /*
- * libcatseg_hip.so -- extension header: the label census and the per-batch IoU average behind the class-aware train loaders
+ * libcatseg_hip.so -- feature header: the label census and the per-batch IoU average behind the class-aware train loaders
  * (adaptive batching, oversampling, weighted random; managers/BaseManager.py:198-229, 286-405 of the reference), csrc/census.hip.
  * The conventions of catseg.h hold (asynchronous on `stream`, never allocates, never synchronises, 0 = ok, catseg_last_error() gives
  * the message, which starts with the function's name).  Both launches can be captured into a hipGraph.
@@ -35,7 +35,7 @@
 #ifndef CATSEG_CENSUS_H
 #define CATSEG_CENSUS_H
 
-#include "../../catseg.h"
+#include "catseg.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -1,5 +1,5 @@
 /*
- * libcatseg_hip.so -- extension header: the frequency-weighted crop pick (CropNP with crop_mode 'freq', utils/transforms.py:282-293 of the
+ * libcatseg_hip.so -- feature header: the frequency-weighted crop pick (CropNP with crop_mode 'freq', utils/transforms.py:282-293 of the
  * reference), csrc/cropfreq.hip.  The conventions of catseg.h hold (asynchronous on `stream`, never allocates, never synchronises, 0 = ok,
  * catseg_last_error() gives the message, which starts with the function's name).
  *
@@ -29,7 +29,7 @@
 #ifndef CATSEG_CROPFREQ_H
 #define CATSEG_CROPFREQ_H
 
-#include "../catseg.h"
+#include "catseg.h"
 
 #ifdef __cplusplus
 extern "C" {

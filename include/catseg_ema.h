@@ -1,5 +1,5 @@
 /*
- * libcatseg_hip.so -- extension header: the running average of the weights (EMA / SWA; optim.WeightAverage), csrc/ema.hip.
+ * libcatseg_hip.so -- feature header: the running average of the weights (EMA / SWA; optim.WeightAverage), csrc/ema.hip.
  * The conventions of catseg.h hold (asynchronous on `stream`, never allocates, never synchronises, 0 = ok, catseg_last_error() gives
  * the message, which starts with the function's name).  Every launch can be captured into a hipGraph.
  *
@@ -32,7 +32,7 @@
 #ifndef CATSEG_EMA_H
 #define CATSEG_EMA_H
 
-#include "../../catseg.h"
+#include "catseg.h"
 
 #define CATSEG_EMA_LERP 0
 #define CATSEG_EMA_SWAP 1

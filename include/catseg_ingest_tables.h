@@ -1,5 +1,5 @@
 /*
- * libcatseg_hip.so -- extension header: per-frame label tables for the ingest launches (csrc/ingest.hip, csrc/warp.hip, csrc/cropfreq.hip).
+ * libcatseg_hip.so -- feature header: per-frame label tables for the ingest launches (csrc/ingest.hip, csrc/warp.hip, csrc/cropfreq.hip).
  * The conventions of catseg.h hold (asynchronous on `stream`, never allocates, never synchronises, 0 = ok, catseg_last_error() gives the
  * message).
  *
@@ -9,14 +9,14 @@
  *   table_of_frame:  DEVICE int32 [B], the table row of every frame, or NULL = row 0 for every frame.  The kernels clamp the index into
  *                    [0, T): whatever it holds, no read is unguarded.
  * Every other argument is the one of the entry point without `_tables` (catseg.h: catseg_ingest_u8, catseg_ingest_warp_u8;
- * ext/catseg_cropfreq.h: catseg_crop_freq_pick), and so are the results: those entry points are these with T = 1 and a NULL index.
+ * catseg_cropfreq.h: catseg_crop_freq_pick), and so are the results: those entry points are these with T = 1 and a NULL index.
  * CATSEG_EINVAL before anything is launched, beside the refusals of the plain entry points: T < 1, an index without tables, a misaligned
  * index.
  */
 #ifndef CATSEG_INGEST_TABLES_H
 #define CATSEG_INGEST_TABLES_H
 
-#include "../../catseg.h"
+#include "catseg.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -1,5 +1,5 @@
 /*
- * libcatseg_hip.so -- extension header: the fused optimiser updates on the flat parameter buffer (Adam / AdamW with weight decay and
+ * libcatseg_hip.so -- feature header: the fused optimiser updates on the flat parameter buffer (Adam / AdamW with weight decay and
  * amsgrad, momentum SGD, parameter groups, clipping by the global gradient norm; optim.py), csrc/optim.hip.
  * The conventions of catseg.h hold (asynchronous on `stream`, never allocates, never synchronises, 0 = ok, catseg_last_error() gives
  * the message, which starts with the function's name).  Every launch can be captured into a hipGraph.
@@ -55,7 +55,7 @@
 #ifndef CATSEG_OPTIM_H
 #define CATSEG_OPTIM_H
 
-#include "../../catseg.h"
+#include "catseg.h"
 
 #define CATSEG_OPTIM_HYPER_FLOATS 20
 #define CATSEG_OPTIM_MAX_GROUPS 8

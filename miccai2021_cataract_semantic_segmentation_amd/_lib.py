@@ -1,4 +1,4 @@
-"""ctypes binding of libcatseg_hip.so (C ABI declared in include/catseg.h).
+"""ctypes binding of libcatseg_hip.so (C ABI declared in include/*.h).
 
 There is no CPU fallback: importing this module without the built library raises.
 PyTorch is used only to own device memory and streams; every kernel is launched
@@ -70,6 +70,7 @@ class PointrendGatherBwdDesc(C.Structure):
 
 
 _SIGS = {
+    # include/catseg.h, include/catseg_debug.h
     "catseg_last_error": (C.c_char_p, []),
     "catseg_version": (I, []),
     "catseg_conv2d_fwd": (I, [P, P]),
@@ -250,6 +251,28 @@ _SIGS = {
     "catseg_pointrend_gather_bwd": (I, [P, P]),
     "catseg_pointrend_scatter_last": (I, [P, I, P, I, I, L, P, I, I, P]),
     "catseg_pointrend_scatter_bwd": (I, [P, I, P, I, I, L, P, I, I, I, P]),
+    # include/catseg_cropfreq.h
+    "catseg_crop_freq_workspace": (SZ, [I, I, I, I]),
+    "catseg_crop_freq_pick": (I, [P, I, I, I, P, P, P, I, I, I, P, P, P, P, P, P, SZ, P]),
+    # include/catseg_ingest_tables.h: the plain entry's arguments with (T, table_of_frame) after the tables
+    "catseg_ingest_u8_tables": (I, [P, P, I, I, I, P, I, P, P, I, I, P, P, P, P, P, P]),
+    "catseg_ingest_warp_u8_tables": (I, [P, P, I, I, I, P, I, P, P, P, I, I, P, I, I, I, I, P, P, P, P, P, P, P]),
+    "catseg_crop_freq_pick_tables": (I, [P, I, I, I, P, I, P, P, P, I, I, I, P, P, P, P, P, P, SZ, P]),
+    # include/catseg_census.h
+    "catseg_label_census_u8": (I, [P, I, I, I, P, I, P, I, P]),
+    "catseg_iou_ema": (I, [P, P, I, F, F, P, P, P]),
+    # include/catseg_optim.h
+    "catseg_optim_hyper": (None, [I, F, F, F, F, I, P, P, P]),
+    "catseg_adam_step_ex": (I, [P, P, P, P, P, L, P, I, P, P, F, F, F, I, P, P]),
+    "catseg_sgd_step": (I, [P, P, P, L, P, I, P, P, F, I, I, P, P]),
+    "catseg_grad_norm_workspace": (SZ, [L]),
+    "catseg_grad_norm": (I, [P, L, F, P, F, P, SZ, P, P]),
+    "catseg_optim_grid_cap": (I, []),
+    # include/catseg_ema.h
+    "catseg_ema_update": (I, [P, P, L, F, P, P]),
+    "catseg_ema_swap": (I, [P, P, L, P]),
+    "catseg_ema_table": (I, [P, I, P, I, F, P, P]),
+    "catseg_ema_grid_cap": (I, []),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(lib, _name)  # AttributeError here = header / library mismatch
@@ -257,65 +280,6 @@ for _name, (_res, _args) in _SIGS.items():
     _fn.argtypes = _args
 
 EXPORTS = tuple(_SIGS)
-
-# the entry points of the extension headers (include/ext/*.h), bound the same way; not part of EXPORTS (= the prototypes of include/*.h)
-_SIGS_EXT = {
-    "catseg_crop_freq_workspace": (SZ, [I, I, I, I]),
-    "catseg_crop_freq_pick": (I, [P, I, I, I, P, P, P, I, I, I, P, P, P, P, P, P, SZ, P]),
-}
-for _name, (_res, _args) in _SIGS_EXT.items():
-    _fn = getattr(lib, _name)
-    _fn.restype = _res
-    _fn.argtypes = _args
-
-# the per-frame label-table forms of the ingest launches (include/ext/tables/catseg_ingest_tables.h): the plain entry's arguments with
-# (T, table_of_frame) after the tables
-_SIGS_TABLES = {
-    "catseg_ingest_u8_tables": (I, [P, P, I, I, I, P, I, P, P, I, I, P, P, P, P, P, P]),
-    "catseg_ingest_warp_u8_tables": (I, [P, P, I, I, I, P, I, P, P, P, I, I, P, I, I, I, I, P, P, P, P, P, P, P]),
-    "catseg_crop_freq_pick_tables": (I, [P, I, I, I, P, I, P, P, P, I, I, I, P, P, P, P, P, P, SZ, P]),
-}
-for _name, (_res, _args) in _SIGS_TABLES.items():
-    _fn = getattr(lib, _name)
-    _fn.restype = _res
-    _fn.argtypes = _args
-
-# the label census and the per-batch IoU average of the class-aware train loaders (include/ext/census/catseg_census.h)
-_SIGS_CENSUS = {
-    "catseg_label_census_u8": (I, [P, I, I, I, P, I, P, I, P]),
-    "catseg_iou_ema": (I, [P, P, I, F, F, P, P, P]),
-}
-for _name, (_res, _args) in _SIGS_CENSUS.items():
-    _fn = getattr(lib, _name)
-    _fn.restype = _res
-    _fn.argtypes = _args
-
-# the fused optimiser updates: Adam / AdamW / SGD with parameter groups, and the global gradient norm (include/ext/optim/catseg_optim.h)
-_SIGS_OPTIM = {
-    "catseg_optim_hyper": (None, [I, F, F, F, F, I, P, P, P]),
-    "catseg_adam_step_ex": (I, [P, P, P, P, P, L, P, I, P, P, F, F, F, I, P, P]),
-    "catseg_sgd_step": (I, [P, P, P, L, P, I, P, P, F, I, I, P, P]),
-    "catseg_grad_norm_workspace": (SZ, [L]),
-    "catseg_grad_norm": (I, [P, L, F, P, F, P, SZ, P, P]),
-    "catseg_optim_grid_cap": (I, []),
-}
-for _name, (_res, _args) in _SIGS_OPTIM.items():
-    _fn = getattr(lib, _name)
-    _fn.restype = _res
-    _fn.argtypes = _args
-
-# the running average of the weights, EMA / SWA (include/ext/ema/catseg_ema.h); a table of its own like the two above: _SIGS_EXT is the
-# table of include/ext/*.h proper
-_SIGS_EMA = {
-    "catseg_ema_update": (I, [P, P, L, F, P, P]),
-    "catseg_ema_swap": (I, [P, P, L, P]),
-    "catseg_ema_table": (I, [P, I, P, I, F, P, P]),
-    "catseg_ema_grid_cap": (I, []),
-}
-for _name, (_res, _args) in _SIGS_EMA.items():
-    _fn = getattr(lib, _name)
-    _fn.restype = _res
-    _fn.argtypes = _args
 
 if os.environ.get("CATSEG_SYNC"):  # debugging aid: synchronise after every entry point so a device fault names its launch
     class _SyncLib:

@@ -1,4 +1,4 @@
-// Label census and per-batch IoU average (include/ext/census/catseg_census.h): what the class-aware train loaders start from and feed on.
+// Label census and per-batch IoU average (include/catseg_census.h): what the class-aware train loaders start from and feed on.
 //
 // label_census_kernel   grid (chunks of a frame, frames), 256 threads.  A frame is H * W bytes at any address: the bytes in front of its
 //   first 16-byte boundary and behind its last one (at most 15 each) are counted bytewise by the frame's block 0, the 16-byte vectors
@@ -13,7 +13,7 @@
 // iou_ema_kernel        one block: thread c owns class c (integer row / column sums of cm_running - cm_prev, one fp32 conversion each,
 //   fp32 arithmetic in the reference's order, contraction off), then the block copies cm_running over cm_prev.
 #include "common.h"
-#include "ext/census/catseg_census.h"
+#include "catseg_census.h"
 
 #pragma clang fp contract(off)
 

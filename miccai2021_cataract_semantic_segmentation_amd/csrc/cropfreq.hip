@@ -10,8 +10,8 @@
 // No atomics, no ordering between blocks, integer sums: two launches give the same bits.  Reads: the label bytes under the region once (+ one
 // row per frame), through the guards of warp_taps; the tables by an 8-bit index.  8 B written per region row, 8 (+16) B per frame.
 #include "common.h"
-#include "ext/catseg_cropfreq.h"
-#include "ext/tables/catseg_ingest_tables.h"
+#include "catseg_cropfreq.h"
+#include "catseg_ingest_tables.h"
 #include "warp_label.h"
 
 namespace {

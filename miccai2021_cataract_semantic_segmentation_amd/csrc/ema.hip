@@ -1,4 +1,4 @@
-// The running average of the weights (include/ext/ema/catseg_ema.h): EMA / SWA update of a shadow of the flat parameter buffer, the
+// The running average of the weights (include/catseg_ema.h): EMA / SWA update of a shadow of the flat parameter buffer, the
 // in-place exchange of the two, and the same two operations over a table of small buffers (BatchNorm running statistics).
 //
 // ema_update_kernel / ema_swap_kernel   streaming, the shape of adam_ex_kernel (csrc/optim.hip): a capped grid of 256-thread blocks
@@ -6,7 +6,7 @@
 //   memory (one 4-byte load per thread, uniform).  The last n % 4 elements go one by one.
 // ema_table_kernel   one block per table entry, 4-byte accesses (the live buffers promise no more than that alignment).
 #include "common.h"
-#include "ext/ema/catseg_ema.h"
+#include "catseg_ema.h"
 
 #pragma clang fp contract(off)
 

@@ -6,7 +6,7 @@
 //   image:  ToTensor (u8 HWC -> f32 CHW, / 255), optional Normalize(mean, std)  utils/utils.py:440-447
 // One thread per output pixel; HBM-bound: 4 B read, 12 (+16) + 8 B written per pixel.
 #include "common.h"
-#include "ext/tables/catseg_ingest_tables.h"
+#include "catseg_ingest_tables.h"
 #include "warp_label.h"
 
 namespace {

@@ -1,4 +1,4 @@
-// Fused optimiser updates on the flat parameter buffer (include/ext/optim/catseg_optim.h): Adam / AdamW with weight decay and amsgrad,
+// Fused optimiser updates on the flat parameter buffer (include/catseg_optim.h): Adam / AdamW with weight decay and amsgrad,
 // momentum SGD, parameter groups through a per-chunk group map, and the global gradient norm behind clipping.
 //
 // adam_ex_kernel / sgd_kernel   streaming: a capped grid of 256-thread blocks strides over the 16-byte vectors; an iteration issues every
@@ -11,7 +11,7 @@
 //   vectors in order into one accumulator, the 64 lanes of a wave combine in a fixed butterfly, thread 0 adds the four wave sums in order.
 //   The second launch stages the partials in LDS and thread 0 adds them in index order.
 #include "common.h"
-#include "ext/optim/catseg_optim.h"
+#include "catseg_optim.h"
 
 #pragma clang fp contract(off)
 

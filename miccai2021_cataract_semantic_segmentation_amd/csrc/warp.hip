@@ -10,7 +10,7 @@
 // Every source read is guarded by a bounds test in the flipped frame's coordinates: whatever the matrix / origin hold, the worst case is zeros.
 // HBM-bound: <= 4 x 4 B read (neighbours share cache lines), 12 (+16) (+3) + 8 B written per pixel; ~10 fp64 operations beside it.
 #include "common.h"
-#include "ext/tables/catseg_ingest_tables.h"
+#include "catseg_ingest_tables.h"
 #include "warp_label.h"
 
 namespace {

@@ -2209,7 +2209,7 @@ def adam_step_dev(p, g, m, v, hyper, beta1=0.9, beta2=0.999, eps=1e-8):
         check(lib.catseg_adam_step_dev(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(hyper), beta1, beta2, eps, stream()))
 
 
-# ---- the fused optimiser updates of include/ext/optim/catseg_optim.h.  hyper: the 20 step scalars (catseg_optim_hyper) as a HOST float32
+# ---- the fused optimiser updates of include/catseg_optim.h.  hyper: the 20 step scalars (catseg_optim_hyper) as a HOST float32
 # tensor (passed by value) or a DEVICE one (read by the kernel: a captured launch replays with what was uploaded); group_map: uint8 per
 # 64-float chunk or None; clip: the float32[2] that grad_norm wrote, or None
 OPTIM_HYPER_FLOATS, OPTIM_MAX_GROUPS = 20, 8
@@ -2259,7 +2259,7 @@ def grad_norm(g, out, work, max_norm, grad_scale=1.0, hyper_dev=None):
     return out
 
 
-# ---- the running average of the weights (include/ext/ema/catseg_ema.h).  w: a float (passed by value) or a DEVICE float32 tensor whose
+# ---- the running average of the weights (include/catseg_ema.h).  w: a float (passed by value) or a DEVICE float32 tensor whose
 # first element the kernel reads (a captured launch replays with what was uploaded)
 EMA_LERP, EMA_SWAP = 0, 1
 EMA_ENTRY = [("live", "<i8"), ("shadow_off", "<i8"), ("n", "<i4"), ("pad", "<i4")]      # csrc/ema.hip: EmaEntry (24 bytes)

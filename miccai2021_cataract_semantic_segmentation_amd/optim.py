@@ -2,9 +2,9 @@
 
 FusedAdam with its constructor arguments of old is torch.optim.Adam(lr) as built at managers/BaseManager.py:441 of the reference and
 launches catseg_adam_step / catseg_adam_step_dev (include/catseg.h).  Weight decay (coupled or decoupled), amsgrad, parameter groups,
-momentum SGD and clipping by the global gradient norm run on the kernels of include/ext/optim/catseg_optim.h.  WeightAverage keeps a
+momentum SGD and clipping by the global gradient norm run on the kernels of include/catseg_optim.h.  WeightAverage keeps a
 running average of the weights (EMA / SWA, torch.optim.swa_utils.AveragedModel's arithmetic) in a shadow of the flat buffer: one launch
-of include/ext/ema/catseg_ema.h behind the update."""
+of include/catseg_ema.h behind the update."""
 import contextlib
 
 import numpy as np

@@ -2,14 +2,14 @@
 (tests/golden/class_loaders.npz, written by tests/golden/make_golden_class_loaders.py): get_class_info, get_prob / get_dist, the v1 / v2
 weights, adaptive batch sequences and oversampling lists on tie-free tables, every item EXACTLY (probabilities and weights bit for bit).
 The schedule loop cannot be called in the reference (it sits inside load_data): it is pinned to hand-written known answers.  Also: the
-IoUTracker's lag logic with a fake event source, and the C ABI of include/ext/census/catseg_census.h."""
-import ctypes
+IoUTracker's lag logic with a fake event source, and the C ABI of include/catseg_census.h."""
 import functools
 import os
-import re
 
 import numpy as np
 import pytest
+
+import _abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIST_NAMES = (("1/", "inv"), ("1-", "one_minus"), ("1-**2", "one_minus_sq"))
@@ -274,36 +274,18 @@ def test_tracker_never_overwrites_the_slot_the_host_reads():
         assert np.array_equal(view, kept)
 
 
-# ---- the C ABI of include/ext/census/catseg_census.h (in the style of tests/test_abi_cpu.py)
-_VALUE_TYPES = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
+# ---- the C ABI of include/catseg_census.h
 EINVAL = 1
 A = [0x10000 * (i + 1) for i in range(8)]     # fake device pointers: a refusal returns before anything is launched
 
 
-def _ctype(text):
-    t = " ".join(text.replace("*", " * ").split())
-    if "*" in t or t == "catseg_stream_t":
-        return ctypes.c_void_p
-    return _VALUE_TYPES[t.replace("const ", "")]
-
-
 def test_census_signature_table_matches_the_header():
     from miccai2021_cataract_semantic_segmentation_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "ext", "census", "catseg_census.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    hdr = re.sub(r"//[^\n]*", " ", hdr)
-    hdr = re.sub(r"^\s*#[^\n]*$", " ", hdr, flags=re.M).replace('extern "C" {', " ").replace("}", " ")
-    protos = {}
-    for stmt in hdr.split(";"):
-        m = re.match(r"^\s*(.+?)\b(catseg_[a-z0-9_]+)\s*\((.*)\)\s*$", stmt, flags=re.S)
-        assert m or not stmt.strip(), "cannot parse %r" % stmt
-        if m:
-            args = [re.match(r"^(.*?)\w+$", a.strip(), flags=re.S).group(1) for a in m.group(3).split(",")]
-            protos[m.group(2)] = (_ctype(m.group(1)), [_ctype(a) for a in args])
-    assert sorted(protos) == sorted(_lib._SIGS_CENSUS) == ["catseg_iou_ema", "catseg_label_census_u8"]
-    for name, sig in protos.items():
-        assert _lib._SIGS_CENSUS[name] == sig
-        assert name not in _lib.EXPORTS and name not in _lib._SIGS_EXT and hasattr(_lib.lib, name)
+    protos = _abi.prototypes("catseg_census.h")
+    assert sorted(protos) == ["catseg_iou_ema", "catseg_label_census_u8"]
+    for name, (res, args, _) in protos.items():
+        assert _lib._SIGS[name] == (res, args), "%s: header %r, _lib._SIGS %r" % (name, (res, args), _lib._SIGS[name])
+        assert hasattr(_lib.lib, name)
 
 
 def _census_args(**kw):

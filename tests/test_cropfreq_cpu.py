@@ -1,16 +1,15 @@
 """Host side of the frequency-weighted crop (CropNP, crop_mode 'freq'): the exact integer pick against the offsets the REAL reference
 reported (tests/golden/cropfreq.npz, written by tests/golden/make_golden_cropfreq.py), the region arithmetic, the integer weight table, the
-opt-in, and the C ABI of include/ext/catseg_cropfreq.h (prototypes against _lib._SIGS_EXT, every refusal before a launch)."""
-import ctypes
+opt-in, and the C ABI of include/catseg_cropfreq.h (prototypes against _lib._SIGS, every refusal before a launch)."""
 import functools
 import os
 import random
-import re
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+import _abi
 import _cropfreq_ref as CR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -107,41 +106,15 @@ def test_freq_is_opt_in():
         check_crop({"mode": "centre", "on_device": True})
 
 
-# ---- the C ABI of the extension header, checked the way tests/test_abi_cpu.py checks include/*.h
-_VALUE_TYPES = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
-
-
-def _ctype(text, result=False):
-    t = " ".join(text.replace("*", " * ").split())
-    if result and t == "void":
-        return None
-    if result and t == "const char *":
-        return ctypes.c_char_p
-    if "*" in t or t == "catseg_stream_t":
-        return ctypes.c_void_p
-    return _VALUE_TYPES[t.replace("const ", "")]
-
-
+# ---- the C ABI of include/catseg_cropfreq.h
 def test_ext_signature_table_matches_the_header():
-    """return type, argument count and every argument type of every catseg_* prototype of include/ext/*.h, against _lib._SIGS_EXT"""
+    """the header declares the crop pick's two entry points; each has the header's signature in _lib._SIGS and is exported"""
     from miccai2021_cataract_semantic_segmentation_amd import _lib
-    ext = os.path.join(ROOT, "include", "ext")
-    hdr = "".join(open(os.path.join(ext, f)).read() for f in sorted(os.listdir(ext)) if f.endswith(".h"))
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    hdr = re.sub(r"//[^\n]*", " ", hdr)
-    hdr = re.sub(r"^\s*#[^\n]*$", " ", hdr, flags=re.M).replace('extern "C" {', " ").replace("}", " ")
-    protos = {}
-    for stmt in hdr.split(";"):
-        m = re.match(r"^\s*(.+?)\b(catseg_[a-z0-9_]+)\s*\((.*)\)\s*$", stmt, flags=re.S)
-        assert m or not stmt.strip(), "cannot parse %r" % stmt
-        if m:
-            args = [a.strip() for a in m.group(3).split(",")]
-            args = [] if args == ["void"] else [re.match(r"^(.*?)\w+$", a, flags=re.S).group(1) for a in args]
-            protos[m.group(2)] = (_ctype(m.group(1), result=True), [_ctype(a) for a in args])
-    assert sorted(protos) == sorted(_lib._SIGS_EXT) == ["catseg_crop_freq_pick", "catseg_crop_freq_workspace"]
-    for name, sig in protos.items():
-        assert _lib._SIGS_EXT[name] == sig, "%s: header %r, _lib._SIGS_EXT %r" % (name, sig, _lib._SIGS_EXT[name])
-        assert name not in _lib.EXPORTS and hasattr(_lib.lib, name)
+    protos = _abi.prototypes("catseg_cropfreq.h")
+    assert sorted(protos) == ["catseg_crop_freq_pick", "catseg_crop_freq_workspace"]
+    for name, (res, args, _) in protos.items():
+        assert _lib._SIGS[name] == (res, args), "%s: header %r, _lib._SIGS %r" % (name, (res, args), _lib._SIGS[name])
+        assert hasattr(_lib.lib, name)
 
 
 EINVAL, EWORKSPACE = 1, 3

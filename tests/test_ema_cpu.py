@@ -1,16 +1,15 @@
-"""Host side of the running weight average (optim.WeightAverage, include/ext/ema/catseg_ema.h): the schedule of weights pinned to stock
+"""Host side of the running weight average (optim.WeightAverage, include/catseg_ema.h): the schedule of weights pinned to stock
 torch.optim.swa_utils.AveragedModel in fp64, every refusal of the three entry points before a launch, the prototypes against
-_lib._SIGS_EMA, and config['train']['ema']."""
-import ctypes
+_lib._SIGS, and config['train']['ema']."""
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 from torch.optim.swa_utils import AveragedModel, get_ema_multi_avg_fn
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _abi
+
 STEPS, START = 12, 3
 
 
@@ -121,29 +120,15 @@ def test_refusals_before_any_launch():
 
 
 def test_signature_table_matches_the_extension_header():
-    """return type, argument count and every argument type of include/ext/ema/catseg_ema.h against _lib._SIGS_EMA; none of the entries
-    is part of the top-level ABI; the entry record's numpy mirror has the header's size"""
+    """include/catseg_ema.h declares the four averaging entry points; each has the header's signature in _lib._SIGS and is exported; the
+    entry record's numpy mirror has the header's size"""
     from miccai2021_cataract_semantic_segmentation_amd import _lib, ops
-    hdr = open(os.path.join(ROOT, "include", "ext", "ema", "catseg_ema.h")).read()
-    assert "#define CATSEG_EMA_ENTRY_BYTES %d" % np.dtype(ops.EMA_ENTRY).itemsize in hdr
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    hdr = re.sub(r"^\s*#[^\n]*$", " ", hdr, flags=re.M).replace('extern "C" {', " ").replace("}", " ")
-    values = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
-
-    def ctype(text, result=False):
-        t = " ".join(text.replace("*", " * ").split())
-        return ctypes.c_void_p if "*" in t or t == "catseg_stream_t" else values[t.replace("const ", "")]
-    protos = {}
-    for stmt in filter(None, (s.strip() for s in hdr.split(";"))):
-        m = re.match(r"^(.+?)\b(catseg_[a-z0-9_]+)\s*\((.*)\)$", stmt, flags=re.S)
-        assert m, "cannot parse %r" % stmt
-        args = [a.strip() for a in m.group(3).split(",")]
-        args = [] if args == ["void"] else [re.match(r"^(.*?)\w+$", a, flags=re.S).group(1) for a in args]
-        protos[m.group(2)] = (ctype(m.group(1), True), [ctype(a) for a in args])
-    assert sorted(protos) == sorted(_lib._SIGS_EMA) == ["catseg_ema_grid_cap", "catseg_ema_swap", "catseg_ema_table", "catseg_ema_update"]
-    for name, sig in protos.items():
-        assert _lib._SIGS_EMA[name] == sig, "%s: header %r, table %r" % (name, sig, _lib._SIGS_EMA[name])
-        assert name not in _lib.EXPORTS and name not in _lib._SIGS_EXT and hasattr(_lib.lib, name)
+    assert "#define CATSEG_EMA_ENTRY_BYTES %d" % np.dtype(ops.EMA_ENTRY).itemsize in open(os.path.join(_abi.INCLUDE, "catseg_ema.h")).read()
+    protos = _abi.prototypes("catseg_ema.h")
+    assert sorted(protos) == ["catseg_ema_grid_cap", "catseg_ema_swap", "catseg_ema_table", "catseg_ema_update"]
+    for name, (res, args, _) in protos.items():
+        assert _lib._SIGS[name] == (res, args), "%s: header %r, table %r" % (name, (res, args), _lib._SIGS[name])
+        assert hasattr(_lib.lib, name)
     assert (ops.EMA_LERP, ops.EMA_SWAP) == (0, 1)
 
 

@@ -1,4 +1,4 @@
-"""The kernels of include/ext/ema/catseg_ema.h on the GPU: catseg_ema_update against torch.lerp evaluated on the CPU in fp64, with its fp32
+"""The kernels of include/catseg_ema.h on the GPU: catseg_ema_update against torch.lerp evaluated on the CPU in fp64, with its fp32
 evaluation as the yardstick (tests/_yardstick.within, the bar of tests/test_optim_kernels_gpu.py); catseg_ema_swap exactly; catseg_ema_table
 over ~700 small buffers with 4-byte aligned live pointers and gaps in the shadow.
 

@@ -1,14 +1,12 @@
 """Host side of the fused optimisers (optim.py): the chunk map, the parameter-group builder, every refusal, the index order of the
-stock-format state dictionaries, and the C ABI of include/ext/optim/catseg_optim.h (prototypes, the step-scalar row)."""
-import ctypes
-import os
-import re
+stock-format state dictionaries, and the C ABI of include/catseg_optim.h (prototypes, the step-scalar row)."""
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _abi
+
 SIZES = [1, 63, 64, 65, 200, 4099]          # the parameter sizes of tests/test_optim_kernels_gpu.py
 
 
@@ -229,27 +227,11 @@ def test_hyper_row_and_validation_without_gpu():
 
 
 def test_signature_table_matches_the_extension_header():
-    """return type, argument count and every argument type of include/ext/optim/catseg_optim.h against _lib._SIGS_OPTIM; none of the
-    entries is part of the top-level ABI"""
+    """include/catseg_optim.h declares the six optimiser entry points; each has the header's signature in _lib._SIGS and is exported"""
     from miccai2021_cataract_semantic_segmentation_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "ext", "optim", "catseg_optim.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    hdr = re.sub(r"^\s*#[^\n]*$", " ", hdr, flags=re.M).replace('extern "C" {', " ").replace("}", " ")
-    values = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
-
-    def ctype(text, result=False):
-        t = " ".join(text.replace("*", " * ").split())
-        if result and t == "void":
-            return None
-        return ctypes.c_void_p if "*" in t or t == "catseg_stream_t" else values[t.replace("const ", "")]
-    protos = {}
-    for stmt in filter(None, (s.strip() for s in hdr.split(";"))):
-        m = re.match(r"^(.+?)\b(catseg_[a-z0-9_]+)\s*\((.*)\)$", stmt, flags=re.S)
-        assert m, "cannot parse %r" % stmt
-        args = [a.strip() for a in m.group(3).split(",")]
-        args = [] if args == ["void"] else [re.match(r"^(.*?)\w+$", a, flags=re.S).group(1) for a in args]
-        protos[m.group(2)] = (ctype(m.group(1), True), [ctype(a) for a in args])
-    assert sorted(protos) == sorted(_lib._SIGS_OPTIM) and len(protos) == 6
-    for name, sig in protos.items():
-        assert _lib._SIGS_OPTIM[name] == sig, "%s: header %r, table %r" % (name, sig, _lib._SIGS_OPTIM[name])
-        assert name not in _lib.EXPORTS and name not in _lib._SIGS_EXT and hasattr(_lib.lib, name)
+    protos = _abi.prototypes("catseg_optim.h")
+    assert sorted(protos) == ["catseg_adam_step_ex", "catseg_grad_norm", "catseg_grad_norm_workspace", "catseg_optim_grid_cap",
+                              "catseg_optim_hyper", "catseg_sgd_step"]
+    for name, (res, args, _) in protos.items():
+        assert _lib._SIGS[name] == (res, args), "%s: header %r, table %r" % (name, (res, args), _lib._SIGS[name])
+        assert hasattr(_lib.lib, name)

@@ -1,4 +1,4 @@
-"""The optimiser kernels of include/ext/optim/catseg_optim.h on the GPU, through the C ABI: the option-free launch against catseg_adam_step
+"""The optimiser kernels of include/catseg_optim.h on the GPU, through the C ABI: the option-free launch against catseg_adam_step
 bit for bit, every option against the stock torch optimisers evaluated on the CPU in fp64 and fp32 (tests/_yardstick.within), the
 deterministic gradient norm against its derived 2-ulp bound, clipped updates, and the refusals with real device buffers.
 

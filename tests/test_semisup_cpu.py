@@ -1,17 +1,15 @@
 """Host side of semi-supervised training: the constructor contract of losses.SemiSupervisedLoss (losses/SemiSupervisedLoss.py:8-43 of the
 reference), the batch split and its one-pass gradient join, utils.BalancedConcatDataset and the pseudo_colorjitter arguments against what
 the REAL reference produced (tests/golden/semisup.npz, written by tests/golden/make_golden_semisup.py), the RandomApply draw of
-sample_color_jitter, the host validation of a per-frame label-table index, and the C ABI of include/ext/tables/catseg_ingest_tables.h."""
+sample_color_jitter, the host validation of a per-frame label-table index, and the C ABI of include/catseg_ingest_tables.h."""
 import copy
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _abi
 
 
 def _cfg(name="LovaszSoftmax", **kw):
@@ -238,53 +236,25 @@ def test_manager_batch_unpacking_and_the_encdec_refusal():
         m.load_loss()
 
 
-# ---- the C ABI of include/ext/tables/catseg_ingest_tables.h (in the style of test_abi_cpu.py)
-_VALUE_TYPES = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
+# ---- the C ABI of include/catseg_ingest_tables.h
 EINVAL = 1
 A = [0x10000 * (i + 1) for i in range(16)]     # fake device pointers: a refusal returns before anything is launched
 
 
-def _ctype(text, result=False):
-    t = " ".join(text.replace("*", " * ").split())
-    if "*" in t or t == "catseg_stream_t":
-        return ctypes.c_void_p
-    return _VALUE_TYPES[t.replace("const ", "")]
-
-
-def _prototypes(path):
-    hdr = open(path).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    hdr = re.sub(r"//[^\n]*", " ", hdr)
-    hdr = re.sub(r"^\s*#[^\n]*$", " ", hdr, flags=re.M).replace('extern "C" {', " ").replace("}", " ")
-    protos = {}
-    for stmt in hdr.split(";"):
-        m = re.match(r"^\s*(.+?)\b(catseg_[a-z0-9_]+)\s*\((.*)\)\s*$", stmt, flags=re.S)
-        assert m or not stmt.strip(), "cannot parse %r" % stmt
-        if m:
-            args = [re.match(r"^(.*?)(\w+)$", a.strip(), flags=re.S).groups() for a in m.group(3).split(",")]
-            protos[m.group(2)] = (_ctype(m.group(1), result=True), [_ctype(t) for t, _ in args], [n for _, n in args])
-    return protos
-
-
 def test_tables_signature_table_matches_the_header_and_the_plain_prototypes():
     from miccai2021_cataract_semantic_segmentation_amd import _lib
-    tables = _prototypes(os.path.join(ROOT, "include", "ext", "tables", "catseg_ingest_tables.h"))
-    assert sorted(tables) == sorted(_lib._SIGS_TABLES) == ["catseg_crop_freq_pick_tables", "catseg_ingest_u8_tables", "catseg_ingest_warp_u8_tables"]
+    tables = _abi.prototypes("catseg_ingest_tables.h")
+    assert sorted(tables) == ["catseg_crop_freq_pick_tables", "catseg_ingest_u8_tables", "catseg_ingest_warp_u8_tables"]
     lib = ctypes.CDLL(_lib.LIB_PATH)
-    plain = _prototypes(os.path.join(ROOT, "include", "ext", "catseg_cropfreq.h"))
-    main = open(os.path.join(ROOT, "include", "catseg.h")).read()
+    plain = set(_abi.prototypes("catseg.h")) | set(_abi.prototypes("catseg_cropfreq.h"))
     for name, (res, args, names) in tables.items():
         assert hasattr(lib, name), "libcatseg_hip.so does not export %s" % name
-        assert _lib._SIGS_TABLES[name] == (res, args), "%s: header %r, _lib._SIGS_TABLES %r" % (name, (res, args), _lib._SIGS_TABLES[name])
-        assert name not in _lib.EXPORTS and name not in _lib._SIGS_EXT
+        assert _lib._SIGS[name] == (res, args), "%s: header %r, _lib._SIGS %r" % (name, (res, args), _lib._SIGS[name])
         # the plain entry point's arguments with (T, table_of_frame) after the tables, nothing else moved
         i = names.index("luts")
         assert names[i:i + 3] == ["luts", "T", "table_of_frame"] and args[i + 1:i + 3] == [ctypes.c_int, ctypes.c_void_p]
         base = name[:-len("_tables")]
-        want = _lib._SIGS_EXT[base] if base in plain else _lib._SIGS[base]
-        assert (res, args[:i + 1] + args[i + 3:]) == want
-        if base not in plain:
-            assert re.search(r"\b%s\s*\(" % base, main)
+        assert base in plain and (res, args[:i + 1] + args[i + 3:]) == _lib._SIGS[base]
     # the existing entry points kept their signatures
     assert _lib._SIGS["catseg_ingest_u8"][1] == [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 6
 

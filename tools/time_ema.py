@@ -1,4 +1,4 @@
-"""Times the launches of include/ext/ema/catseg_ema.h on flat buffers of the size and layout of the bench model's (OCRNet-HRNetV2-W48: the
+"""Times the launches of include/catseg_ema.h on flat buffers of the size and layout of the bench model's (OCRNet-HRNetV2-W48: the
 model is built on the host for its FlatParams layout and its BatchNorm set, the buffers are random), with HIP events around single
 launches, in one run:
     adam_step       catseg_adam_step, the yardstick (profiles/optim_time.json records it at 0.73 of 8 TB/s), measured again here

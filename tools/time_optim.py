@@ -1,4 +1,4 @@
-"""Times the optimiser launches of include/ext/optim/catseg_optim.h beside the existing catseg_adam_step, on flat buffers of the size and
+"""Times the optimiser launches of include/catseg_optim.h beside the existing catseg_adam_step, on flat buffers of the size and
 layout of the bench model's (OCRNet-HRNetV2-W48: the model is built on the host for its FlatParams layout, the buffers are random), with
 HIP events around single launches, in one run:
     adam_step             catseg_adam_step (what FusedAdam launches with its arguments of old)
