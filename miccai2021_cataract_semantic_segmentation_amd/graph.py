@@ -16,6 +16,12 @@ What a replay must not freeze is kept out of the graph's kernel arguments: the A
 from device memory (catseg_adam_step_dev; uploaded in front of each replay: LambdaLR and the step count keep working), inputs are copied
 into static buffers.  The arithmetic is the eager step's, launch for launch: results are bit-identical (tests/test_graph_gpu.py).
 
+Gradient accumulation (accumulate=n > 1, optim.FusedOptimizer.set_accumulation) -- TWO graphs from one pool: the micro-step (zero_grad,
+forward, loss, backward, the fold of the gradients into the optimiser's window, confusion matrix), replayed by every call, and the
+optimiser step (norm pair, update, running average, the memset of the window), replayed behind the call that fills the window and by
+flush() on a partial one.  The host counts the folded micro-steps as it counts the steps; the row uploaded in front of the second graph
+carries grad_scale / micro-steps, so a flushed window replays the same graph with another scalar.
+
 Data-parallel runs (model._grad_sync attached) -- SEGMENTED replay.  The bucketed all-reduce of dist.GradSync has to start while the
 backward pass is still running (the xGMI traffic hides under the remaining backward kernels), and a collective is kept out of the
 capture (RCCL launches it on its own communicator stream as an ordinary asynchronous call: the very path the eager loop uses and the
@@ -90,7 +96,7 @@ class _CutRecorder:
 
 class GraphedTrainStep:
     def __init__(self, model, loss_fn, optimiser, img, lbl, confusion=None, warmup=2, keep_state=True, forward_loss=None,
-                 segment_bytes=None, tracker=None):
+                 segment_bytes=None, tracker=None, accumulate=1):
         """model: an EngineNet in training mode; loss_fn(model_output, labels) -> scalar loss tensor (or forward_loss(img, labels) ->
         (loss, final logits), the managers' method, instead of model + loss_fn); optimiser: a fused optimiser of optim.py over the model;
         img / lbl: a batch of the shapes every later call will have; confusion: optional int32 [K, K] matrix the step accumulates its
@@ -101,12 +107,26 @@ class GraphedTrainStep:
         segment_bytes: data parallel only -- see default_segment_bytes(); 0 = never cut (the whole exchange behind the backward pass).
         tracker: optional utils.IoUTracker whose step(confusion) is launched behind the confusion matrix INSIDE the capture (None: the
         captured graph is what it was).  Its device state (cm_prev, the averages) is saved and restored around the warm-up like the
-        confusion matrix: the warm-up steps would otherwise leave their batch in the average the first replay starts from."""
+        confusion matrix: the warm-up steps would otherwise leave their batch in the average the first replay starts from.
+        accumulate: the optimiser's window (optimiser.set_accumulation(n) first).  n > 1: TWO graphs from one pool -- the micro-step
+        (zero_grad, forward, loss, backward, optimiser.fold(), confusion matrix, tracker), replayed by every call, and the optimiser step
+        (norm pair, update, running average, the memset of the window), replayed behind the call that fills the window and by flush()
+        on a partial one.  The count of folded micro-steps is the optimiser's own, so an eager loop may continue a window this object
+        began.  Not with a gradient reducer attached."""
         if not isinstance(optimiser, FusedOptimizer):
             raise TypeError("GraphedTrainStep needs a fused optimiser of optim.py -- FusedAdam, FusedAdamW, FusedSGD -- (their kernels read the "
                             "step-dependent scalars from device memory)")
         if not model.training:
             raise RuntimeError("GraphedTrainStep captures a TRAINING step: call model.train() first")
+        if isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1:
+            raise ValueError("GraphedTrainStep: accumulate is an int >= 1, got %r" % (accumulate,))
+        if accumulate > 1 and model._grad_sync is not None:
+            raise ValueError("GraphedTrainStep(accumulate=%d) with a gradient reducer attached: the exchange of an accumulated window "
+                             "(once per window, behind its last backward pass) is not built" % accumulate)
+        if accumulate != optimiser._accum:
+            raise ValueError("GraphedTrainStep(accumulate=%d) over an optimiser whose window is %d: call optimiser.set_accumulation(%d)"
+                             % (accumulate, optimiser._accum, accumulate))
+        self.accumulate = accumulate
         self.model, self.loss_fn, self.opt, self.confusion = model, loss_fn, optimiser, confusion
         self.forward_loss = forward_loss
         self.tracker = tracker
@@ -132,7 +152,7 @@ class GraphedTrainStep:
         if keep_state:
             saved = (fp.flat.clone(), [b.clone() for b in state], None, [b.clone() for b in model.buffers()], optimiser._steps,
                      [(mod, mod._pending_batches) for mod in model.modules() if isinstance(mod, engine.BatchNorm2d)],
-                     None if confusion is None else confusion.clone(), None if tracker is None else tracker.save())
+                     None if confusion is None else confusion.clone(), None if tracker is None else tracker.save(), optimiser._folded)
         self.stream = torch.cuda.Stream(device=dev)
         self.stream.wait_stream(torch.cuda.current_stream(dev))
         self.graph = self.tail_graph = None
@@ -142,6 +162,8 @@ class GraphedTrainStep:
             with torch.cuda.stream(self.stream):
                 for _ in range(max(int(warmup), 1)):
                     self._body()
+                    if self.accumulate > 1:
+                        self.opt.step()              # (a window of one micro-step: the tail graph's launches)
         except BaseException:
             self._restore_model()
             raise
@@ -158,7 +180,7 @@ class GraphedTrainStep:
                     confusion.copy_(saved[6])
                 if tracker is not None:
                     tracker.restore(saved[7])
-            optimiser._steps = saved[4]
+            optimiser._steps, optimiser._folded = saved[4], saved[8]
             for mod, n in saved[5]:
                 mod._pending_batches = n
         self._bns = [mod for mod in model.modules() if isinstance(mod, engine.BatchNorm2d)]
@@ -166,6 +188,14 @@ class GraphedTrainStep:
         try:
             if self.split:
                 self._capture_segments(dev)
+            elif self.accumulate > 1:
+                self._pool = torch.cuda.graph_pool_handle()
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph, pool=self._pool, stream=self.stream):
+                    self.loss, self.outputs = self._body()
+                self.tail_graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.tail_graph, pool=self._pool, stream=self.stream):
+                    self.opt.step()
             else:
                 self.graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(self.graph, stream=self.stream):
@@ -177,7 +207,8 @@ class GraphedTrainStep:
             raise
         for mod, n in zip(self._bns, pend):          # (the capture ran the Python side of one step: undo its host-side counters)
             mod._pending_batches = n
-        self.replays = 0
+        self.replays = 0                             # calls (accumulate > 1: micro-steps)
+        self.steps = 0                               # accumulate > 1: replays of the optimiser-step graph
         self.launch_log = []                         # split: (index of the graph just replayed, bucket) of the last step, in call order
 
     # ------------------------------------------------------------------------------------------------ capture
@@ -266,12 +297,18 @@ class GraphedTrainStep:
                 loss.backward()
         finally:
             self.model._keep_pass = self._keep0
-        if not self.split:
+        if self.accumulate > 1:
+            self.opt.fold()                          # the micro-step graph ends here: the optimiser step is a graph of its own
+            self._metrics(out)
+        elif not self.split:
             self._tail(out)
         return loss.detach(), out
 
     def _tail(self, out):
         self.opt.step()
+        self._metrics(out)
+
+    def _metrics(self, out):
         if self.confusion is not None:
             from .utils.metrics import t_get_confusion_matrix
             final = out[-1] if isinstance(out, (tuple, list)) else out
@@ -286,6 +323,16 @@ class GraphedTrainStep:
             self.img.copy_(img, non_blocking=True)
         if lbl is not self.lbl:
             self.lbl.copy_(lbl, non_blocking=True)
+        if self.accumulate > 1:
+            self.graph.replay()                      # the micro-step; its fold is counted here, as the step count is below
+            self.opt._folded += 1
+            for mod in self._bns:
+                mod._pending_batches += 1
+            self.model._grads_pending = True
+            self.replays += 1
+            if self.opt.window_full():
+                self._step()
+            return self.loss
         self.opt._steps += 1
         self.opt.upload_hyper()                      # (on the current stream, in front of the replays)
         if self.split:
@@ -307,6 +354,19 @@ class GraphedTrainStep:
         self.model._grads_pending = True
         self.replays += 1
         return self.loss
+
+    def _step(self):
+        """the optimiser step over the window's `_folded` micro-steps: the row uploaded here carries grad_scale / _folded"""
+        self.opt._steps += 1
+        self.opt.upload_hyper()
+        self.tail_graph.replay()
+        self.opt._folded = 0
+        self.steps += 1
+
+    def flush(self):
+        """the optimiser step over a partial window (a mean over the micro-steps it holds); nothing on an empty one"""
+        if self.accumulate > 1 and self.opt._folded > 0:
+            self._step()
 
     def overlap_report(self):
         """what the bench line's comm.overlap says about the replayed step"""

@@ -18,6 +18,7 @@ import contextlib
 import copy
 import datetime
 import json
+import os
 import pathlib
 
 import numpy as np
@@ -27,7 +28,7 @@ from torch.utils.data import DataLoader
 from .. import dist as D
 from .. import losses as _losses
 from .. import models as _models
-from ..optim import FusedOptimizer, WeightAverage, average_config, build_average, build_optimiser
+from ..optim import FusedOptimizer, WeightAverage, accumulate_config, average_config, build_average, build_optimiser
 from ..utils import LRFcts
 from ..utils.metrics import t_get_confusion_matrix, t_get_mean_iou, t_get_pixel_accuracy
 
@@ -86,6 +87,9 @@ class BaseManager:
 
     def __init__(self, configuration, train_set=None, valid_set=None, train_sampler=None, video_set=None, frame_sink=None):
         self.config = merge_defaults(configuration)
+        # config['train']['accumulate'] (build-side key, optim.accumulate_config): micro-steps per optimiser step.  Checked in front of
+        # the process group: a window over data-parallel ranks is refused.  Without the key (1) nothing below differs.
+        self.accumulate = accumulate_config(self.config["train"].get("accumulate"), int(os.environ.get("WORLD_SIZE", "1")))
         self.start_epoch = self.epoch = 0
         self.best_loss = 1e10
         self.metrics = {"best_miou": 0, "best_miou_anatomies": 0, "best_miou_instruments": 0, "best_miou_rare": 0,
@@ -129,6 +133,10 @@ class BaseManager:
             self.load_loss()
             torch.manual_seed(self.config["seed"])      # after model construction, as BaseManager.py:104-112
             self.load_optimiser()
+            if self.accumulate > 1:
+                if not isinstance(self.optimiser, FusedOptimizer):
+                    raise ValueError("config['train']['accumulate'] needs a fused optimiser of optim.py (the window lives in it)")
+                self.optimiser.set_accumulation(self.accumulate)
             self.average = build_average(self.model, self.optimiser, self.ema_cfg)
         elif self.config["mode"] not in ("inference", "demo_video_inference"):
             raise ValueError("mode: {} is not recognized".format(self.config["mode"]))
@@ -309,7 +317,12 @@ class BaseManager:
         # config['train']['hip_graph'] (build-side key, default off): the step -- zero_grad, forward, loss, backward, Adam, confusion matrix --
         # is recorded once per epoch into a hipGraph and replayed (graph.GraphedTrainStep: bit-identical to this loop, one host call per
         # step instead of ~3000 launches); batches of another shape (a ragged last batch) run the loop below
+        # config['train']['accumulate'] = n > 1: every batch is a micro-step (zero_grad, forward, loss, backward, fold); the optimiser steps
+        # when its window is full and, on a partial window, at the end of the epoch in front of the scheduler: no window spans an epoch, no
+        # batch's gradient is dropped.  The graph and the loop below share the optimiser's window, so a ragged batch continues it eagerly.
         graphed = None
+        accumulate = self.accumulate
+        steps0 = self.optimiser._steps if accumulate > 1 else 0
         use_graph = bool(self.config.get("train", {}).get("hip_graph", False)) and isinstance(self.optimiser, FusedOptimizer)
         for batch in loader:
             img, lbl = unpack_batch(batch)
@@ -318,7 +331,7 @@ class BaseManager:
                 from ..graph import GraphedTrainStep
                 img, lbl = img.float().contiguous(), lbl.long().contiguous()
                 graphed = GraphedTrainStep(self.model, None, self.optimiser, img, lbl, confusion=running_cm, forward_loss=self.forward_loss,
-                                           tracker=tracker)
+                                           tracker=tracker, accumulate=accumulate)
             if graphed is not None and img.shape == graphed.img.shape and lbl.shape == graphed.lbl.shape:
                 loss_sum += graphed(img, lbl)
             else:
@@ -328,7 +341,12 @@ class BaseManager:
                 self.optimiser.zero_grad()
                 loss, out = self.forward_loss(img, lbl)
                 loss.backward()
-                self.optimiser.step()
+                if accumulate > 1:
+                    self.optimiser.fold()
+                    if self.optimiser.window_full():
+                        self.optimiser.step()
+                else:
+                    self.optimiser.step()
                 t_get_confusion_matrix(out.detach(), lbl, running_cm)      # accumulates on the device
                 if tracker is not None:
                     tracker.step(running_cm)
@@ -337,6 +355,11 @@ class BaseManager:
                 tracker.publish()                # K floats on their way to the pinned buffer the next batch's draw reads
             n += 1
             self.global_step += 1
+        if accumulate > 1 and self.optimiser._folded > 0:      # the epoch's last, partial window
+            if graphed is not None:
+                graphed.flush()
+            else:
+                self.optimiser.step()
         if graphed is not None:
             graphed.release()
         if self.scheduler is not None:
@@ -354,6 +377,8 @@ class BaseManager:
         miou = t_get_mean_iou(running_cm, self.experiment)
         rec = {"epoch": self.epoch + self.start_epoch, "train_loss": float(loss_sum / max(n, 1)), "train_miou": float(miou),
                "train_pixel_accuracy": float(pa), "lr": self.optimiser.param_groups[0]["lr"]}
+        if accumulate > 1:
+            rec["optimiser_steps"] = self.optimiser._steps - steps0
         self.history.append(rec)
         if self.rank == 0:
             print("Epoch {epoch:03d} - loss {train_loss:.5f} - miou {train_miou:.4f} - pa {train_pixel_accuracy:.4f}".format(**rec))

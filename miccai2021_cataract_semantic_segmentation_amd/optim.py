@@ -4,7 +4,8 @@ FusedAdam with its constructor arguments of old is torch.optim.Adam(lr) as built
 launches catseg_adam_step / catseg_adam_step_dev (include/catseg.h).  Weight decay (coupled or decoupled), amsgrad, parameter groups,
 momentum SGD and clipping by the global gradient norm run on the kernels of include/catseg_optim.h.  WeightAverage keeps a
 running average of the weights (EMA / SWA, torch.optim.swa_utils.AveragedModel's arithmetic) in a shadow of the flat buffer: one launch
-of include/catseg_ema.h behind the update."""
+of include/catseg_ema.h behind the update.  set_accumulation(n) makes n micro-steps one optimiser step: a window buffer beside the
+gradient buffer, folded by catseg_axpy2d, read by the same kernels with the gradient scale divided by the micro-steps it holds."""
 import contextlib
 
 import numpy as np
@@ -132,13 +133,92 @@ class FusedOptimizer(torch.optim.Optimizer):
         self._hyper_dev = self._hyper_host = None      # device_hyper(): the step-dependent scalars live in device memory
         self._row = torch.zeros(ops.OPTIM_HYPER_FLOATS, dtype=torch.float32)
         self._avg = None                               # attach_average(): the running average updated behind every step
+        self._accum, self._acc, self._folded = 1, None, 0      # set_accumulation(): the window, its flat sum, micro-steps folded so far
 
     def zero_grad(self, set_to_none=True):
         """The backward tape OVERWRITES each parameter's slice of the flat gradient buffer (it does not accumulate over
         several backward passes: a second backward() before zero_grad() raises); clearing the buffer here matters for
-        parameters that receive no gradient in a step (one memset of the flat buffer, ~0.1 ms)."""
+        parameters that receive no gradient in a step (one memset of the flat buffer, ~0.1 ms).  An accumulation window
+        (set_accumulation) is not touched: fold() has the micro-step's gradients by then."""
         self.model.zero_grad()
         return None
+
+    # ------------------------------------------------------------------ gradient accumulation
+    def set_accumulation(self, n):
+        """A window of n micro-steps per optimiser step: every micro-step runs zero_grad / forward / backward / fold(), step() follows
+        once window_full() (or earlier, on a partial window of m < n micro-steps: the mean is then taken over m).
+
+            acc = g_1 + g_2 + ... + g_m (fp32, in micro-batch order: one catseg_axpy2d launch per fold over the flat buffer)
+            g'  = (acc * grad_scale / m) * clip,    clip = min(1, max_grad_norm / (||acc * grad_scale / m|| + 1e-6))
+
+        and g' is what the update kernels take for the gradient: they read `acc` where they read the gradient buffer and
+        grad_scale / m where they read the gradient scale (by value, or from the device row), so no kernel is added.  The stock form
+        (loss / n).backward() scales every term before adding; the two differ in rounding only and are identical when n is a power of two.
+        BatchNorm takes its statistics and updates its running statistics per micro-batch, as torch does.  Step count, bias corrections,
+        LambdaLR and an attached running average follow optimiser steps, not micro-steps.  The window is not part of state_dict():
+        checkpoints are written where it is empty.  n = 1 (the default): nothing is allocated, fold() launches nothing, step() is the
+        step without a window."""
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError("set_accumulation: the window is an int >= 1, got %r" % (n,))
+        if n != self._accum and self._folded:
+            raise RuntimeError("set_accumulation: %d micro-steps are folded into the open window; step() first" % self._folded)
+        self._accum = n
+        if n == 1:
+            self._acc = None
+        return self
+
+    def _carried(self, cur, fp):
+        """`cur` if it is a buffer laid out like fp.flat on its device, else a new zero one (with cur's values if the model only moved)"""
+        if cur is None or cur.numel() != fp.flat.numel() or cur.device != fp.flat.device:
+            new = torch.zeros_like(fp.flat)
+            if cur is not None and cur.numel() == fp.flat.numel():
+                new.copy_(cur)
+            return new
+        return cur
+
+    def _window(self, fp):
+        """the flat sum of the window's gradients (allocated zero on first use; carried along when the model moved)"""
+        self._acc = self._carried(self._acc, fp)
+        return self._acc
+
+    def _capturing(self, fp):
+        return fp.flat.is_cuda and torch.cuda.is_current_stream_capturing()
+
+    def fold(self):
+        """behind every backward pass: acc += grad (one launch over the whole flat buffer; the gradient buffer is left as it is).  Inside
+        a stream capture the launch is recorded and nothing is counted: the replay's caller counts (graph.GraphedTrainStep)."""
+        if self._accum == 1:
+            return
+        fp = self.model.flat()
+        acc = self._window(fp)
+        n = fp.grad.numel()
+        assert n % FlatParams.ALIGN == 0 and acc.numel() == n, "the flat buffers are a multiple of %d floats" % FlatParams.ALIGN
+        ops.axpy(fp.grad.view(n // FlatParams.ALIGN, FlatParams.ALIGN), acc.view(n // FlatParams.ALIGN, FlatParams.ALIGN), 1.0, accumulate=True)
+        if not self._capturing(fp):
+            self._folded += 1
+
+    def window_full(self):
+        return self._folded >= self._accum
+
+    def _scale(self):
+        """the gradient scale of the step about to be launched: grad_scale, over the micro-steps folded into the window"""
+        return self.grad_scale if self._accum == 1 else self.grad_scale / max(self._folded, 1)
+
+    def _grad(self, fp):
+        """what step() reads for the gradient: the gradient buffer, or the window's sum (which must hold a micro-step; a capture
+        records the launches of a step whose count the replay's caller keeps)"""
+        if self._accum == 1:
+            return fp.grad
+        if self._folded < 1 and not self._capturing(fp):
+            raise RuntimeError("step() on an empty accumulation window: fold() a backward pass first")
+        return self._window(fp)
+
+    def _close_window(self, fp):
+        """behind the update and the running average: the window starts over"""
+        if self._accum > 1:
+            self._acc.zero_()
+            if not self._capturing(fp):
+                self._folded = 0
 
     # ------------------------------------------------------------------ state
     def _live(self):
@@ -149,12 +229,7 @@ class FusedOptimizer(torch.optim.Optimizer):
         """the flat state buffers (allocated zero on first use; carried along when the model moved), in _live() order"""
         out = []
         for a in self._live():
-            cur = getattr(self, a)
-            if cur is None or cur.numel() != fp.flat.numel() or cur.device != fp.flat.device:
-                new = torch.zeros_like(fp.flat)
-                if cur is not None and cur.numel() == fp.flat.numel():
-                    new.copy_(cur)
-                setattr(self, a, new)
+            setattr(self, a, self._carried(getattr(self, a), fp))
             out.append(getattr(self, a))
         if self.max_grad_norm is not None and (self.last_grad_norm is None or self.last_grad_norm.device != fp.flat.device):
             self.last_grad_norm = torch.zeros(2, dtype=torch.float32, device=fp.flat.device)
@@ -163,7 +238,10 @@ class FusedOptimizer(torch.optim.Optimizer):
 
     def state_buffers(self):
         """every flat state tensor of this optimiser (what a snapshot of the training state has to hold besides `_steps`)"""
-        own = self._state(self.model.flat())
+        fp = self.model.flat()
+        own = self._state(fp)
+        if self._accum > 1:
+            own = own + [self._window(fp)]
         return own if self._avg is None else own + self._avg.buffers()
 
     def attach_average(self, avg):
@@ -236,11 +314,11 @@ class FusedOptimizer(torch.optim.Optimizer):
         self._fill_hyper(self._row)
         return self._row
 
-    def _clip(self, fp, hyper):
-        """the two norm launches, right in front of the update; returns the update kernel's clip pointer"""
+    def _clip(self, grad, hyper):
+        """the two norm launches over the gradient step() reads, right in front of the update; returns the update kernel's clip pointer"""
         if self.max_grad_norm is None:
             return None
-        ops.grad_norm(fp.grad, self.last_grad_norm, self._norm_ws, self.max_grad_norm, self.grad_scale, hyper if hyper.is_cuda else None)
+        ops.grad_norm(grad, self.last_grad_norm, self._norm_ws, self.max_grad_norm, self._scale(), hyper if hyper.is_cuda else None)
         return self.last_grad_norm
 
     # ------------------------------------------------------------------ stock-format (de)serialisation
@@ -321,9 +399,9 @@ class FusedAdam(FusedOptimizer):
     def _fill_hyper(self, row):
         g = self.param_groups[0]
         if self._plain():       # {lr, 1 - beta1^step, sqrt(1 - beta2^step), grad_scale}: the row of catseg_adam_step_dev
-            ops.lib.catseg_adam_hyper(float(g["lr"]), g["betas"][0], g["betas"][1], max(self._steps, 1), self.grad_scale, row.data_ptr())
+            ops.lib.catseg_adam_hyper(float(g["lr"]), g["betas"][0], g["betas"][1], max(self._steps, 1), self._scale(), row.data_ptr())
         else:
-            ops.optim_hyper(row, max(self._steps, 1), g["betas"][0], g["betas"][1], self.grad_scale, 0.0,
+            ops.optim_hyper(row, max(self._steps, 1), g["betas"][0], g["betas"][1], self._scale(), 0.0,
                             [float(q["lr"]) for q in self.param_groups], [float(q["weight_decay"]) for q in self.param_groups])
 
     @torch.no_grad()
@@ -332,6 +410,7 @@ class FusedAdam(FusedOptimizer):
         state = self._state(fp)
         m, v = state[0], state[1]
         g = self.param_groups[0]
+        grad = self._grad(fp)
         if self._plain():
             if self._hyper_dev is not None:
                 # device-scalar form (graph.GraphedTrainStep): a launch recorded into a hipGraph reads {lr, bias corrections, gradient scale}
@@ -339,23 +418,24 @@ class FusedAdam(FusedOptimizer):
                 if not torch.cuda.is_current_stream_capturing():
                     self._steps += 1
                     self.upload_hyper()
-                ops.adam_step_dev(fp.flat, fp.grad, m, v, self._hyper_dev, g["betas"][0], g["betas"][1], g["eps"])
-                self._average()
-                return
-            self._steps += 1
-            ops.adam_step(fp.flat, fp.grad, m, v, float(g["lr"]), self._steps, g["betas"][0], g["betas"][1], g["eps"],
-                          self.grad_scale)
+                ops.adam_step_dev(fp.flat, grad, m, v, self._hyper_dev, g["betas"][0], g["betas"][1], g["eps"])
+            else:
+                self._steps += 1
+                ops.adam_step(fp.flat, grad, m, v, float(g["lr"]), self._steps, g["betas"][0], g["betas"][1], g["eps"],
+                              self._scale())
             self._average()
+            self._close_window(fp)
             return
         hyper = self._advance()
-        clip = self._clip(fp, hyper)
+        clip = self._clip(grad, hyper)
         wd_mode = ops.WD_NONE
         if any(q["weight_decay"] for q in self.param_groups):
             wd_mode = ops.WD_DECOUPLED if g.get("decoupled_weight_decay", False) else ops.WD_COUPLED
-        ops.adam_step_ex(fp.flat, fp.grad, m, v, hyper, G=len(self.param_groups), group_map=self._group_map(fp),
+        ops.adam_step_ex(fp.flat, grad, m, v, hyper, G=len(self.param_groups), group_map=self._group_map(fp),
                          vmax=state[2] if len(state) > 2 else None, beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"], wd_mode=wd_mode,
                          clip=clip)
         self._average()
+        self._close_window(fp)
 
     def _state_entry(self, views):
         return dict({"step": torch.tensor(float(self._steps))}, **views)
@@ -416,7 +496,7 @@ class FusedSGD(FusedOptimizer):
 
     def _fill_hyper(self, row):
         g = self.param_groups[0]
-        ops.optim_hyper(row, max(self._steps, 1), 0.0, 0.0, self.grad_scale, float(g["dampening"]),
+        ops.optim_hyper(row, max(self._steps, 1), 0.0, 0.0, self._scale(), float(g["dampening"]),
                         [float(q["lr"]) for q in self.param_groups], [float(q["weight_decay"]) for q in self.param_groups])
 
     @torch.no_grad()
@@ -424,12 +504,14 @@ class FusedSGD(FusedOptimizer):
         fp = self.model.flat()
         state = self._state(fp)
         g = self.param_groups[0]
+        grad = self._grad(fp)
         hyper = self._advance()
-        clip = self._clip(fp, hyper)
-        ops.sgd_step(fp.flat, fp.grad, state[0] if state else None, hyper, G=len(self.param_groups), group_map=self._group_map(fp),
+        clip = self._clip(grad, hyper)
+        ops.sgd_step(fp.flat, grad, state[0] if state else None, hyper, G=len(self.param_groups), group_map=self._group_map(fp),
                      momentum=float(g["momentum"]), nesterov=bool(g["nesterov"]), use_wd=any(q["weight_decay"] for q in self.param_groups),
                      clip=clip)
         self._average()
+        self._close_window(fp)
 
     def _state_entry(self, views):
         return views if views else None
@@ -491,6 +573,20 @@ def build_optimiser(model, cfg, lr, grad_scale=1.0):
         groups = param_groups(model, wd, no_decay=tuple(cfg.get("no_decay") or ()), lr_mult=cfg.get("lr_mult"))
     cls = {"Adam": FusedAdam, "AdamW": FusedAdamW, "SGD": FusedSGD}[name]
     return cls(model, lr=lr, groups=groups, max_grad_norm=cfg.get("clip_grad_norm"), grad_scale=grad_scale, **kw)
+
+
+# ---------------------------------------------------------------------- config['train']['accumulate']
+def accumulate_config(n, world=1):
+    """config['train']['accumulate'] (a build-side key; the reference steps on every batch): the micro-steps per optimiser step, an
+    int >= 1.  None (no key) is 1.  A window over data-parallel ranks is refused."""
+    if n is None:
+        return 1
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError("config['train']['accumulate'] is an int >= 1, got %r" % (n,))
+    if n > 1 and world > 1:
+        raise ValueError("config['train']['accumulate'] = %d with WORLD_SIZE = %d: the exchange of an accumulated window (once per window, "
+                         "behind its last backward pass) is not built" % (n, world))
+    return n
 
 
 # ---------------------------------------------------------------------- the running average of the weights (EMA / SWA)
