@@ -471,10 +471,24 @@ typedef struct {
   float* dy; int lddy;
   void* dy_planes;
   void* dy_h2_planes; void* dy_h2_scale; float* dbias;
+  int frozen;                          /* != 0: the statistics are constants of the layer, not functions of y (below) */
+  const float* running_mean; const float* running_var; float eps;
+  const float* scale;                  /* [C], the row catseg_bn_eval_scale wrote for the forward pass */
 } catseg_bn_backward_desc;
 size_t catseg_bn_backward_h2_workspace(long long rows, int C);
 int catseg_bn_backward(const catseg_bn_backward_desc* d, catseg_stream_t stream);
-/* eval-mode / frozen-statistics backward is not on the training path and is not provided. */
+/* frozen != 0: backward of z = act((y - running_mean) * scale + beta (+ residual)) with scale = gamma / sqrt(running_var + eps) -- a BatchNorm
+ * that keeps its running statistics while its gamma / beta train (nn.BatchNorm2d.eval() inside a training model):
+ *   g = dz * (ReLU mask if relu);  dy = g * scale[c];  dres (+)= g;  dbeta[c] = sum_rows g;
+ *   dgamma[c] = invstd[c] * sum_rows g * (y - running_mean[c]),  invstd = 1 / sqrt(running_var + eps) in fp32
+ * dy does not depend on the column sums: ONE streaming pass reads dz and the mask source (y only when dgamma is wanted or the mask is
+ * recomputed from it), writes dy and dres and leaves [row blocks][2][C] partial sums in the workspace; a small launch adds them in block
+ * order (no float atomics: two calls on the same input give the same bits).  With dgamma and dbeta both NULL nothing is summed and the
+ * second launch does not happen.  The three ReLU mask sources are those above; the recomputed one evaluates the forward's expression on
+ * (y, running_mean, scale, beta) and equals the mask catseg_bn_apply produced bit for bit.
+ * Output: dy (fp32) only, dy_record as above.  stats, partials, dy_planes, dy_h2_planes, dy_h2_scale and dbias must be NULL, gamma is not read;
+ * running_mean, running_var and scale are required.  With frozen == 0 the four fields behind it must be NULL / 0.
+ * workspace >= catseg_bn_workspace(rows, C) suffices. */
 
 /* ---- layout / pointwise helpers ---------------------------------------------------------- */
 /* img.float() NCHW (B,3,H,W) -> NHWC with 4 channels (4th = 0) : managers/OCRNet_Manager.py:86 */

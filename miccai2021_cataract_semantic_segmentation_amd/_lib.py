@@ -56,7 +56,8 @@ class BnBackwardDesc(C.Structure):
     _fields_ = [("dz", P), ("lddz", I), ("y", P), ("ldy", I), ("stats", P), ("gamma", P), ("rows", L), ("C", I), ("relu", I), ("z", P), ("ldz", I),
                 ("beta", P), ("mask", P), ("partials", P), ("n_blocks", I), ("dres", P), ("lddres", I), ("dres_accumulate", I), ("g_record", P),
                 ("y_record", P), ("dy_record", P), ("dgamma", P), ("dbeta", P), ("workspace", P), ("workspace_bytes", SZ), ("dy", P), ("lddy", I),
-                ("dy_planes", P), ("dy_h2_planes", P), ("dy_h2_scale", P), ("dbias", P)]
+                ("dy_planes", P), ("dy_h2_planes", P), ("dy_h2_scale", P), ("dbias", P), ("frozen", I), ("running_mean", P), ("running_var", P),
+                ("eps", F), ("scale", P)]
 
 
 class PointrendGatherDesc(C.Structure):

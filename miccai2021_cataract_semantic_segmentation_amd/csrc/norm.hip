@@ -695,6 +695,151 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
   if (amax) cs_amax_commit(m, amax);
 }
 
+// ---- frozen statistics (the `frozen` field of catseg_bn_backward_desc): z = act((y - running_mean) * scale + beta (+ res)) with mean and scale
+// CONSTANTS of the layer.  dy = g * scale has no term in the column sums, so the first pass of the training form disappears: ONE pass in the
+// geometry of bn_bwd_partial_kernel (a block owns rpb rows of its channel block, four rows in flight) reads dz and the mask source, writes dy
+// and dres, and -- when dgamma / dbeta are wanted (part != nullptr) -- leaves [row blocks][2][C] sums of g and g * (y - mean).  y is read only
+// for those sums or to recompute the mask (need_y); bn_bwd_frozen_merge_kernel adds the partials in block order.
+__global__ __launch_bounds__(256) void bn_bwd_frozen_kernel(const float* __restrict__ dz, int lddz, const float* __restrict__ z, int ldz,
+                                                            const float* __restrict__ y, int ldy, const float* __restrict__ rmean,
+                                                            const float* __restrict__ scale, const float* __restrict__ beta, long long rows, int C,
+                                                            int relu, RowSplit s, float* __restrict__ dy, int lddy, float* __restrict__ dres,
+                                                            int lddres, int dres_acc, float* __restrict__ part, unsigned* __restrict__ amax,
+                                                            const unsigned char* __restrict__ mask) {
+  const int t = threadIdx.x;
+  const int cg = blockIdx.y * s.tpr + t % s.tpr;
+  const int rl = t / s.tpr;
+  const int c = cg * 4;
+  const long long r0 = (long long)blockIdx.x * s.rpb;
+  const long long r1 = min(r0 + s.rpb, rows);
+  const bool act = (c < C) && (rl < s.rpp);
+  const bool recompute = relu && !z && !mask;
+  const bool need_y = part != nullptr || recompute;        // (uniform over the launch)
+  f32x4 sg = {0, 0, 0, 0}, sgd = {0, 0, 0, 0};
+  unsigned m = 0;
+  if (act) {
+    const f32x4 mean = ld4(rmean + c), sc = ld4(scale + c);
+    const f32x4 be = recompute ? ld4(beta + c) : f32x4{0, 0, 0, 0};
+    const long long st = s.rpp;
+    long long r = r0 + rl;
+    for (; r + 3 * st < r1; r += 4 * st) {   // four independent rows in flight (4 - 16 loads)
+      f32x4 g[4], yy[4], zz[4], dr[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        g[u] = ld4(dz + (r + u * st) * lddz + c);
+        yy[u] = need_y ? ld4(y + (r + u * st) * ldy + c) : mean;
+        if (dres && dres_acc) dr[u] = ld4(dres + (r + u * st) * lddres + c);
+      }
+      if (relu && mask) {        // (this quad's nibble of the mask byte (r C + c) >> 3)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const unsigned nib = (unsigned)mask[((r + u * st) * C + c) >> 3] >> (c & 4);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) g[u][i] = ((nib >> i) & 1u) ? g[u][i] : 0.f;
+        }
+      } else if (relu) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) zz[u] = z ? ld4(z + (r + u * st) * ldz + c) : bn_affine(yy[u], mean, sc, be);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) g[u][i] = zz[u][i] > 0.f ? g[u][i] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const f32x4 o = g[u] * sc;
+        *(f32x4*)(dy + (r + u * st) * lddy + c) = o;
+        m = max(m, cs_abs_bits4(o));
+        if (dres) *(f32x4*)(dres + (r + u * st) * lddres + c) = dres_acc ? (dr[u] + g[u]) : g[u];
+        sg += g[u];
+        sgd += g[u] * (yy[u] - mean);
+      }
+    }
+    for (; r < r1; r += st) {
+      f32x4 g = ld4(dz + r * lddz + c);
+      const f32x4 yy = need_y ? ld4(y + r * ldy + c) : mean;
+      if (relu && mask) {
+        const unsigned nib = (unsigned)mask[(r * C + c) >> 3] >> (c & 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) g[i] = ((nib >> i) & 1u) ? g[i] : 0.f;
+      } else if (relu) {
+        const f32x4 zz = z ? ld4(z + r * ldz + c) : bn_affine(yy, mean, sc, be);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) g[i] = zz[i] > 0.f ? g[i] : 0.f;
+      }
+      const f32x4 o = g * sc;
+      *(f32x4*)(dy + r * lddy + c) = o;
+      m = max(m, cs_abs_bits4(o));
+      if (dres) {
+        f32x4* d = (f32x4*)(dres + r * lddres + c);
+        *d = dres_acc ? (*d + g) : g;
+      }
+      sg += g;
+      sgd += g * (yy - mean);
+    }
+  }
+  if (part) {       // (uniform: every thread of the block reaches the barrier)
+    __shared__ f32x4 sh1[256], sh2[256];
+    sh1[t] = sg;
+    sh2[t] = sgd;
+    __syncthreads();
+    if (act && rl == 0) {
+      if (s.rpp > kLaneChainF32) {     // (a long chain of lanes merges in fp64: bn_partial_kernel)
+        double a1[4] = {sg[0], sg[1], sg[2], sg[3]}, a2[4] = {sgd[0], sgd[1], sgd[2], sgd[3]};
+        for (int k = 1; k < s.rpp; ++k) {
+          const f32x4 v1 = sh1[t + k * s.tpr], v2 = sh2[t + k * s.tpr];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            a1[i] += (double)v1[i];
+            a2[i] += (double)v2[i];
+          }
+        }
+        sg = f32x4{(float)a1[0], (float)a1[1], (float)a1[2], (float)a1[3]};
+        sgd = f32x4{(float)a2[0], (float)a2[1], (float)a2[2], (float)a2[3]};
+      } else {
+        for (int k = 1; k < s.rpp; ++k) {
+          sg += sh1[t + k * s.tpr];
+          sgd += sh2[t + k * s.tpr];
+        }
+      }
+      float* o = part + ((long long)blockIdx.x * 2) * C;
+      *(f32x4*)(o + c) = sg;
+      *(f32x4*)(o + C + c) = sgd;
+    }
+  }
+  if (amax) cs_amax_commit(m, amax);       // (uniform per launch; its LDS words are its own)
+}
+
+// dbeta = sum over the row blocks of part[b][0], dgamma = invstd * the same of part[b][1], invstd = 1 / sqrt(running_var + eps) in fp32 (the
+// factor catseg_bn_eval_scale gave the forward pass).  4 channels x 256 row-block lanes per block as in bn_bwd_finalize_kernel: lane rl adds
+// blocks rl, rl + 256, ... in fp64, the lanes merge by shuffles and through LDS -- a fixed order, no atomics
+__global__ __launch_bounds__(1024) void bn_bwd_frozen_merge_kernel(const float* __restrict__ part, int nrb, int C, const float* __restrict__ running_var,
+                                                                   float eps, float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  const int cl = threadIdx.x & 3, rl = threadIdx.x >> 2;
+  const int c = blockIdx.x * 4 + cl;
+  const bool live = c < C;
+  double sg = 0, sgd = 0;
+  if (live)
+    for (int b = rl; b < nrb; b += 256) {
+      const float* o = part + ((long long)b * 2) * C;
+      sg += (double)o[c];
+      sgd += (double)o[C + c];
+    }
+#pragma unroll
+  for (int o = 4; o <= 32; o <<= 1) {
+    sg += __shfl_xor(sg, o, 64);
+    sgd += __shfl_xor(sgd, o, 64);
+  }
+  __shared__ double s1[16][5], s2[16][5];
+  if ((threadIdx.x & 63) < 4) { s1[threadIdx.x >> 6][cl] = sg; s2[threadIdx.x >> 6][cl] = sgd; }
+  __syncthreads();
+  if (rl != 0 || !live) return;
+  sg = 0; sgd = 0;
+  for (int k = 0; k < 16; ++k) { sg += s1[k][cl]; sgd += s2[k][cl]; }
+  if (dbeta) dbeta[c] = (float)sg;
+  if (dgamma) dgamma[c] = (float)(sgd * (double)(1.0f / sqrtf(running_var[c] + eps)));
+}
+
 int grid_for(long long total) {
   long long b = (total + 255) / 256;
   return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
@@ -832,7 +977,8 @@ extern "C" int catseg_bn_apply(const catseg_bn_apply_desc* d, catseg_stream_t st
   return CATSEG_OK;
 }
 
-// ---- BatchNorm backward (include/catseg.h: catseg_bn_backward_desc): (partial ->) finalize -> one of three apply kernels.  The partial pass
+// ---- BatchNorm backward (include/catseg.h: catseg_bn_backward_desc).  frozen: bn_bwd_frozen_kernel (-> bn_bwd_frozen_merge_kernel), above.
+// Otherwise (partial ->) finalize -> one of three apply kernels.  The partial pass
 // leaves [row blocks][2][C] sums of g and g * xhat (with `partials` a convolution's backward-data epilogue already has: catseg_dconv3_bnbwd),
 // the finalize merges them into dgamma, dbeta and the two means the apply pass needs (coef) and, for the two planes outputs, derives the bound of
 // dy their exponent comes from.  The h2 output also sums the columns of dy: colpart, merged by colsum_rows_kernel.
@@ -841,10 +987,19 @@ extern "C" size_t catseg_bn_backward_h2_workspace(long long rows, int C) {
 }
 
 extern "C" int catseg_bn_backward(const catseg_bn_backward_desc* d, catseg_stream_t stream) {
-  CS_REQUIRE(d && d->dz && d->y && d->stats && d->gamma, "catseg_bn_backward: dz, y, stats and gamma are required");
-  const bool h2 = d->dy_h2_planes != nullptr, planes = d->dy_planes != nullptr, pre = d->partials != nullptr;
+  CS_REQUIRE(d && d->dz && d->y && (d->frozen || (d->stats && d->gamma)), "catseg_bn_backward: dz, y, stats and gamma are required");
+  const bool h2 = d->dy_h2_planes != nullptr, planes = d->dy_planes != nullptr, pre = d->partials != nullptr, frozen = d->frozen != 0;
   const long long rows = d->rows;
   const int C = d->C, relu = d->relu;
+  // frozen statistics: one rule per message, ahead of the rules of the training form (which then hold for what is left: dy, the ReLU sources,
+  // dres, dy_record)
+  CS_REQUIRE(frozen || (!d->running_mean && !d->running_var && !d->scale && d->eps == 0.f),
+             "catseg_bn_backward: running_mean, running_var, eps and scale belong to frozen != 0");
+  CS_REQUIRE(!frozen || !pre, "catseg_bn_backward: frozen takes no partials (its dy needs no column sums)");
+  CS_REQUIRE(!frozen || !planes, "catseg_bn_backward: frozen writes dy as fp32 only, not dy_planes");
+  CS_REQUIRE(!frozen || (!h2 && !d->dy_h2_scale && !d->dbias), "catseg_bn_backward: frozen writes dy as fp32 only, not dy_h2_planes / dy_h2_scale / dbias");
+  CS_REQUIRE(!frozen || !d->stats, "catseg_bn_backward: frozen takes running_mean / running_var, stats must be NULL");
+  CS_REQUIRE(!frozen || (d->running_mean && d->running_var && d->scale), "catseg_bn_backward: frozen needs running_mean, running_var and scale");
   CS_REQUIRE((d->dy != nullptr) + planes + h2 == 1, "catseg_bn_backward: exactly one of dy, dy_planes and dy_h2_planes");
   CS_REQUIRE(rows > 0 && C > 0 && C % (h2 ? 64 : planes || d->mask ? 8 : 4) == 0 && d->lddz % 4 == 0 && d->ldy % 4 == 0 && (!d->dy || d->lddy % 4 == 0) &&
                  (!d->z || d->ldz % 4 == 0) && (!d->dres || d->lddres % 4 == 0),
@@ -861,13 +1016,26 @@ extern "C" int catseg_bn_backward(const catseg_bn_backward_desc* d, catseg_strea
              "catseg_bn_backward: relu needs z, a mask, or (no residual branch) beta to recompute the mask from y");
   CS_REQUIRE(cs_aligned16(d->dz) && cs_aligned16(d->y) && cs_aligned16(d->stats) && cs_aligned16(d->gamma) && cs_aligned16(d->beta) && cs_aligned16(d->z) &&
                  cs_aligned16(d->dres) && cs_aligned16(d->dy) && cs_aligned16(d->dy_planes) && cs_aligned16(d->dy_h2_planes) &&
-                 (((uintptr_t)d->dy_h2_scale) & 7) == 0, "catseg_bn_backward: alignment");
+                 (((uintptr_t)d->dy_h2_scale) & 7) == 0 && cs_aligned16(d->running_mean) && cs_aligned16(d->scale), "catseg_bn_backward: alignment");
   const size_t need = pre ? cs_align_up((size_t)2 * ((C + 3) & ~3) * 4, 256) : h2 ? catseg_bn_backward_h2_workspace(rows, C) : catseg_bn_workspace(rows, C);
   if (d->workspace_bytes < need || !d->workspace) {
     catseg_set_error("catseg_bn_backward: workspace too small");
     return CATSEG_EWORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
+  if (frozen) {
+    // workspace: the [row blocks][2][C] partials alone, and only when a parameter gradient is wanted
+    const RowSplit s = plan_rows(rows, C);
+    float* part = d->dgamma || d->dbeta ? (float*)d->workspace : nullptr;
+    hipLaunchKernelGGL(bn_bwd_frozen_kernel, dim3(s.nrb, s.gy), dim3(256), 0, st, d->dz, d->lddz, d->z, d->ldz, d->y, d->ldy, d->running_mean, d->scale,
+                       d->beta, rows, C, relu, s, d->dy, d->lddy, d->dres, d->lddres, d->dres_accumulate, part, (unsigned*)d->dy_record,
+                       (const unsigned char*)d->mask);
+    if (part)
+      hipLaunchKernelGGL(bn_bwd_frozen_merge_kernel, dim3((C + 3) / 4), dim3(1024), 0, st, (const float*)part, s.nrb, C, d->running_var, d->eps, d->dgamma,
+                         d->dbeta);
+    CS_LAUNCH_CHECK();
+    return CATSEG_OK;
+  }
   // workspace: [partials of the first pass][coef: 2 C floats][h2: the column sums per row block]; with `partials`, coef alone
   float* part = (float*)d->workspace;
   float* coef = pre ? part : part + (size_t)kMaxRowBlocks * 3 * ((C + 3) & ~3);

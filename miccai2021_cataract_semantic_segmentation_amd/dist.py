@@ -293,7 +293,9 @@ def sync_bn_stats(model, how="mean"):
     modules take part; one all-reduce of a flat buffer."""
     if not dist.is_initialized() or dist.get_world_size() == 1:
         return
-    bns = [m for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.running_mean is not None]
+    # (a frozen BatchNorm -- engine.freeze_bn -- never updates its statistics: they are the same on every rank already and stay bit-unchanged)
+    bns = [m for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.running_mean is not None
+           and not getattr(m, "frozen", False)]
     if not bns:
         return
     means = torch.cat([m.running_mean.reshape(-1) for m in bns])

@@ -28,6 +28,10 @@ class Conv2d(nn.Conv2d):
 
 
 class BatchNorm2d(nn.BatchNorm2d):
+    # frozen: the layer normalises with its running statistics in every pass and never updates them, while its gamma / beta train
+    # (bn.eval() inside a training model in stock torch; freeze_bn below).  Not a mode: model.train() / .eval() leave it alone.
+    frozen = False
+
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self._pending_batches = 0  # num_batches_tracked is flushed lazily (no per-step kernel)
@@ -121,6 +125,39 @@ def rng_modules(module):
 
 def dropout_layers(module):
     return [m for m in module.modules() if isinstance(m, Dropout2d)]
+
+
+def bn_frozen(bn):
+    return bool(getattr(bn, "frozen", False))
+
+
+def freeze_bn(model, select):
+    """sets BatchNorm2d.frozen on the BatchNorm modules `select` names and returns the names of the modules it froze.
+    select: True / "all" -- every BatchNorm; "backbone" -- those under backbone. (under the model's `backbone_modules`); a list or tuple of named_modules() prefixes -- those under
+    one of them (a prefix names a module: "backbone.layer1" takes backbone.layer1.0.bn1, not backbone.layer10); False / None -- none.
+    Anything else, and a selection that matches no BatchNorm module, is a ValueError that quotes the value."""
+    if select is None or select is False:
+        return []
+    if select is True or (isinstance(select, str) and select == "all"):
+        prefixes = [""]
+    elif isinstance(select, str) and select == "backbone":
+        prefixes = list(getattr(model, "backbone_modules", ("backbone",)))      # (EncDec names its trunk enc_model)
+    elif isinstance(select, (list, tuple)) and all(isinstance(p, str) for p in select):
+        prefixes = list(select)
+    else:
+        raise ValueError("freeze_bn: expected True, 'all', 'backbone', a list of module name prefixes, False or None, got %r" % (select,))
+    frozen = []
+    for name, m in model.named_modules():
+        if isinstance(m, BatchNorm2d) and any(p == "" or name == p or name.startswith(p + ".") for p in prefixes):
+            m.frozen = True
+            frozen.append(name)
+    if not frozen:
+        raise ValueError("freeze_bn: %r matches no BatchNorm module of %s" % (select, type(model).__name__))
+    return frozen
+
+
+def frozen_bn_names(model):
+    return [name for name, m in model.named_modules() if isinstance(m, BatchNorm2d) and bn_frozen(m)]
 
 
 def flush_bn_counters(module):
@@ -483,22 +520,25 @@ FUSE_EVAL_BN = True   # eval-mode forward: fold BatchNorm into the conv and fuse
 # ---- the path of one conv_bn_act layer: decided ONCE, in its forward, and written down as a Path ------------------------------------------
 # input form -- how the convolution reads x:
 #   stem7 / stem3   the image as it is through a direct stem kernel (csrc/stem7.hip: ResNet 7x7/2; csrc/stem3.hip: HRNet 3x3/2), training forward
+#                   (also behind a frozen BatchNorm, which then asks the kernel for no statistics)
 #   stem4           the implicit GEMM's packed 4-channel stem (image as NHWC-4, weights as ops.stem_pack_weight)
 #   pad3            a 3-channel image into a generic convolution: image and weights padded to 4 channels
 #   plain           an NHWC activation
 STEM7, STEM3, STEM4, PAD3, PLAIN = "stem7", "stem3", "stem4", "pad3", "plain"
 # forward form: eval-mode BatchNorm folded into the convolution / training (batch statistics) / eval-mode BatchNorm as a kernel of its own
+# (a frozen BatchNorm in a training or recorded pass: running statistics, and a backward of its own -- ops.bn_backward_frozen)
 FOLDED, TRAIN, EVAL = "folded", "train", "eval"
 # backward form (recorded training passes only, else None) -- in which form the gradient of the convolution's output exists:
 #   planes   fp16 x 2 planes that the trunk's plane kernels stream (_bwd_planes)
 #   h2       blocked f16x2 planes that both GEMMs of a head layer read (_bwd_h2)
 #   head     as h2, behind the fused BatchNorm + ReLU + classifier (_fused_head / _bwd_fused_head)
-#   generic  an fp32 tensor (_bwd_generic)
+#   generic  an fp32 tensor (_bwd_generic); the only form of a frozen BatchNorm
 BWD_PLANES, BWD_H2, BWD_HEAD, BWD_GENERIC = "planes", "h2", "head", "generic"
 Path = collections.namedtuple("Path", "input forward backward")
 
 # what a recorded layer keeps for its backward (z: the tensor whose cotangent starts it -- the fused head's logits on that form)
-_Saved = collections.namedtuple("_Saved", "cx path c bn x x_in wk y stats yrec z relu residual need_dx private_in")
+# (stats: the batch statistics of a TRAIN layer; a frozen layer has None there and keeps `scale`, the row its forward normalised with)
+_Saved = collections.namedtuple("_Saved", "cx path c bn x x_in wk y stats yrec z relu residual need_dx private_in scale")
 
 # the first pass of a BatchNorm's backward as its private_in consumer's backward-data epilogue left it: sums = what ops.bn_backward_pre /
 # bn_backward_pre_planes take, planes = it came from the plane kernel (ops.conv_bwd_data_pl) and carries max|g|
@@ -677,12 +717,17 @@ def _bwd_generic(L, pre):
     dz, dres, acc = _cotangent(L)
     if dz is None:
         return
-    if pre is not None:
+    # without a residual branch the ReLU mask is recomputed from y (z is not read: 1 of 3 tensor reads saved)
+    z_mask = L.z if (L.residual is not None or not L.relu) else None
+    if L.path.forward == EVAL:
+        # frozen statistics: one pass, dy = g * scale (the layer registered no bn_src: no consumer has run a first pass for it)
+        assert pre is None
+        dy = ops.bn_backward_frozen(dz, z_mask, L.y, bn.running_mean, bn.running_var, bn.eps, L.scale, L.relu, cx.pgrad(bn.weight),
+                                    cx.pgrad(bn.bias), dres, acc, beta=bn.bias.data)
+    elif pre is not None:
         # dz is already masked and its per-tile sums exist (the consumer's backward-data epilogue): merge + apply only
         dy = ops.bn_backward_pre(dz, L.y, L.stats, bn.weight.data, pre.sums, cx.pgrad(bn.weight), cx.pgrad(bn.bias))
     else:
-        # without a residual branch the ReLU mask is recomputed from y (z is not read: 1 of 3 tensor reads saved)
-        z_mask = L.z if (L.residual is not None or not L.relu) else None
         dy = ops.bn_backward(dz, z_mask, L.y, L.stats, bn.weight.data, L.relu, cx.pgrad(bn.weight), cx.pgrad(bn.bias), dres, acc,
                              beta=bn.bias.data)
     del dz
@@ -729,7 +774,8 @@ def conv_bn_act(cx, x, conv, bn, relu=True, residual=None, out=None, need_dx=Tru
     x_in, wk = _conv_input(inp, x, c)
     bias = c.bias.data if c.bias is not None else None
     cx.claim(c.weight, c.bias, bn.weight, bn.bias)
-    fwd = FOLDED if (not cx.train and not cx.record and FUSE_EVAL_BN) else TRAIN if cx.train else EVAL
+    frozen = bn_frozen(bn)
+    fwd = FOLDED if (not cx.train and not cx.record and FUSE_EVAL_BN) else TRAIN if (cx.train and not frozen) else EVAL
     if fwd == FOLDED:
         # inference fast path: eval-mode BatchNorm folded into the weights, bias + residual + ReLU applied in
         # the convolution epilogue — one kernel per layer, no separate normalisation pass over HBM
@@ -740,7 +786,7 @@ def conv_bn_act(cx, x, conv, bn, relu=True, residual=None, out=None, need_dx=Tru
             tap(z_tap, zf)
         return zf if head is None else conv_bias(cx, zf, head)
     partials = yrec = zrec = None
-    dropping = drop is not None and fwd == TRAIN and drop.active(cx)
+    dropping = drop is not None and drop.active(cx)        # (Dropout2d follows the pass's mode, not the BatchNorm's: active() asks cx.train)
     if dropping and (not relu or residual is not None or out is not None):
         raise NotImplementedError("conv_bn_act(drop=): Dropout2d follows BatchNorm + ReLU of a layer without residual branch or out= view")
     if fwd == TRAIN:
@@ -765,23 +811,36 @@ def conv_bn_act(cx, x, conv, bn, relu=True, residual=None, out=None, need_dx=Tru
         bn._pending_batches += 1
         mean = stats[:Cout]
     else:
-        y = ops.conv_fwd(x_in, wk, bias, Cout, c.kh, c.kw, c.stride, c.pad, c.dil, stem4=inp == STEM4, groups=c.groups, train=cx.record)
+        if inp == STEM3:        # (the direct stem forms are chosen for a training pass: here behind a frozen BatchNorm, without statistics)
+            y = ops.stem3_fwd(x_in, wk, None)
+        elif inp == STEM7:
+            y = ops.stem7_fwd(x_in, wk, None)
+        else:
+            # (exact: the rule of the trunk's first layers holds for a training pass whatever the BatchNorm behind them does)
+            y = ops.conv_fwd(x_in, wk, bias, Cout, c.kh, c.kw, c.stride, c.pad, c.dil, stem4=inp == STEM4, groups=c.groups, train=cx.record,
+                             exact=cx.train and conv.exact_operands)
         stats = None
         mean = bn.running_mean
         scale = ops.bn_eval_scale(bn.weight.data, bn.running_var, bn.eps)
-    path = Path(inp, fwd, _backward_form(inp, c, x_in, y, yrec, partials, relu, residual, out, need_dx, head) if cx.record and fwd == TRAIN else None)
+    if cx.record and fwd != TRAIN and not frozen:
+        raise NotImplementedError("backward through eval-mode BatchNorm is not on the training path")
+    path = Path(inp, fwd, None if not cx.record else BWD_GENERIC if frozen else
+                _backward_form(inp, c, x_in, y, yrec, partials, relu, residual, out, need_dx, head))
     dm = drop.draw(y.shape[0], Cout, y.device) if dropping else None
     if path.backward == BWD_HEAD:
-        return _fused_head(_Saved(cx, path, c, bn, x, x_in, wk, y, stats, yrec, None, relu, residual, need_dx, private_in), scale, head, 32, dm)
+        return _fused_head(_Saved(cx, path, c, bn, x, x_in, wk, y, stats, yrec, None, relu, residual, need_dx, private_in, None), scale, head, 32, dm)
     z = ops.bn_apply(y, mean, scale, bn.bias.data, residual, relu, out=out, planes_rec=zrec,
                      planes_only=zrec is not None and sole_conv_out and relu and residual is None,
-                     want_mask=cx.record and cx.train)       # (a residual block's output: its ReLU mask as bits for the backward pass)
+                     want_mask=cx.record and cx.train,       # (a residual block's output: its ReLU mask as bits for the backward pass)
+                     want_record=not frozen)
+    # (no amax record behind a frozen BatchNorm: the kernels that split their input in registers scale it by max|z| and keep their 2^-22
+    #  only for elements within 2^-17 of it (csrc/planes.h) -- a range batch statistics guarantee and running statistics that need not fit
+    #  the batch do not.  Its consumers take the three-plane kernels, which have fp32's exponent range)
     if cx.record:
-        if fwd != TRAIN:
-            raise NotImplementedError("backward through eval-mode BatchNorm is not on the training path")
-        if relu and residual is None and out is None and dm is None:
-            cx.bn_src[id(z)] = (y, stats, bn.weight.data, bn.bias.data)     # for a private_in consumer of z
-        L = _Saved(cx, path, c, bn, x, x_in, wk, y, stats, yrec, z, relu, residual, need_dx, private_in)
+        if fwd == TRAIN and relu and residual is None and out is None and dm is None:
+            # for a private_in consumer of z (not behind a frozen BatchNorm: that pass belongs to a batch-statistics backward)
+            cx.bn_src[id(z)] = (y, stats, bn.weight.data, bn.bias.data)
+        L = _Saved(cx, path, c, bn, x, x_in, wk, y, stats, yrec, z, relu, residual, need_dx, private_in, scale if frozen else None)
         cx.push(lambda: _conv_bn_act_backward(L))
     if dm is not None:
         z = _dropout_pass(cx, z, dm)
@@ -1265,6 +1324,10 @@ class EngineNet(nn.Module):
         self._keep_pass = False  # graph.GraphedTrainStep (segmented capture): keep the recorded pass for backward_from()
         self._last_pass = self._last_outputs = None
         self._open_state = None  # weak reference to the state of the last recorded pass (dead once its Ctx is gone)
+
+    def apply_freeze_bn(self, config):
+        """config['freeze_bn'] (build-side key of the graph section; the values of freeze_bn's `select`), applied at the end of construction"""
+        self.frozen_bn = freeze_bn(self, config.get("freeze_bn"))
 
     def flat(self):
         if self._flatp is None:

@@ -183,7 +183,8 @@ class GraphedTrainStep:
             optimiser._steps, optimiser._folded = saved[4], saved[8]
             for mod, n in saved[5]:
                 mod._pending_batches = n
-        self._bns = [mod for mod in model.modules() if isinstance(mod, engine.BatchNorm2d)]
+        # (the modules whose batch counter a replay advances: a frozen BatchNorm tracks no batches)
+        self._bns = [mod for mod in model.modules() if isinstance(mod, engine.BatchNorm2d) and not engine.bn_frozen(mod)]
         pend = [mod._pending_batches for mod in self._bns]
         try:
             if self.split:

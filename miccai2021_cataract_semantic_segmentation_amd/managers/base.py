@@ -667,4 +667,5 @@ class BaseManager:
             return
         cfg = json.loads(json.dumps(self.config, default=str))
         with open(self.log_dir / "info.json", "w") as f:
-            json.dump({"config": cfg, "metrics": self.metrics, "history": self.history}, f, indent=1, default=str)
+            json.dump({"config": cfg, "metrics": self.metrics, "history": self.history,
+                       "frozen_bn_modules": len(getattr(self.model, "frozen_bn", ()))}, f, indent=1, default=str)

@@ -92,6 +92,7 @@ class DeepLabv3Plus(EngineNet):
         if "projector" in config:
             raise NotImplementedError("the contrastive projector is outside the accelerated path")
         self.projector_model = None
+        self.apply_freeze_bn(config)
 
     def _body(self, cx, x):
         H, W = image_hw(x)
@@ -126,6 +127,7 @@ class DeepLabv3(EngineNet):
         if "projector" in config:
             raise NotImplementedError("the contrastive projector is outside the accelerated path")
         self.projector_model = None
+        self.apply_freeze_bn(config)
 
     def _body(self, cx, x):
         H, W = image_hw(x)

@@ -245,6 +245,8 @@ _DECODERS = {"UPerNet": UPerNet, "PointRend": PointRend}
 
 
 class EncDec(EngineNet):
+    backbone_modules = ("enc_model",)       # what freeze_bn: "backbone" means here
+
     def __init__(self, config, experiment):
         super().__init__()
         self.config = config
@@ -261,6 +263,7 @@ class EncDec(EngineNet):
         self.get_features = True
         self.num_classes = self.dec_model.num_classes
         self.out_stride = 32
+        self.apply_freeze_bn(config)
 
     def forward(self, x):
         if not (self.training and isinstance(self.dec_model, PointRend)):

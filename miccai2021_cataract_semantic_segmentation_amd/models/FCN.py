@@ -39,6 +39,7 @@ class FCN(EngineNet):
         self.p3_conv = _padded_conv2d(n_ch[2], K, 1)
         self.deconv16 = _padded_convtranspose2d(K, K, 4, 2)
         self.deconv8 = _padded_convtranspose2d(K, K, 16, 8)
+        self.apply_freeze_bn(config)        # (no BatchNorm here: a freeze_bn key is refused as matching nothing)
 
     def _body(self, cx, x):
         H, W = image_hw(x)

@@ -36,7 +36,9 @@ class BasicBlock(nn.Module):
         self.stride = stride
 
     def run(self, cx, x):
-        o = conv_bn_act(cx, x, self.conv1, self.bn1, sole_conv_out=True)      # (o feeds conv2 and nothing else: private_in below)
+        # o feeds conv2 and nothing else (private_in below).  Behind a frozen bn2 conv2's backward-weight reads o as fp32 (the generic form):
+        # o then may not exist as planes only
+        o = conv_bn_act(cx, x, self.conv1, self.bn1, sole_conv_out=not engine.bn_frozen(self.bn2))
         idt = x if self.downsample is None else conv_bn_act(cx, x, self.downsample[0], self.downsample[1], relu=False)
         return conv_bn_act(cx, o, self.conv2, self.bn2, relu=True, residual=idt, private_in=True)
 
@@ -361,6 +363,7 @@ class HRNetv2(EngineNet):
                                                1 if self.final_conv_kernel == 3 else 0))
         self.out_stride = 4
         self.projector_model = None
+        self.apply_freeze_bn(config if isinstance(config, dict) else {})
 
     def _body(self, cx, x):
         H, W = image_hw(x)

@@ -118,6 +118,7 @@ class OCRNet(EngineNet):
         if "projector" in config:
             raise NotImplementedError("the contrastive projector is outside the accelerated path")
         self.projector_model = None
+        self.apply_freeze_bn(config)
 
     def _body(self, cx, x):
         H, W = image_hw(x)

@@ -32,6 +32,7 @@ class UNet(EngineNet):
         self.dconv_up2 = double_conv(128 + 256, 128)
         self.dconv_up1 = double_conv(128 + 64, 64)
         self.conv_last = Conv2d(64, self.num_classes, 1)
+        self.apply_freeze_bn(config or {})  # (no BatchNorm here: a freeze_bn key is refused as matching nothing)
 
     @staticmethod
     def _double(cx, x, block, last):

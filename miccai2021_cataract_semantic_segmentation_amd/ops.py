@@ -1182,8 +1182,9 @@ def _ld(t):
     return 0 if t is None else ld_of(t)
 
 
-def bn_apply(y, mean, scale, beta, residual, relu, out=None, planes_rec=None, planes_only=False, want_mask=False):
-    """the output carries an amax record (out._amax: max|out| accumulated by the kernel) when the trunk runs the f16x2 kernels.
+def bn_apply(y, mean, scale, beta, residual, relu, out=None, planes_rec=None, planes_only=False, want_mask=False, want_record=True):
+    """the output carries an amax record (out._amax: max|out| accumulated by the kernel) when the trunk runs the f16x2 kernels -- unless
+    want_record is False (a frozen BatchNorm: engine.conv_bn_act).
     planes_rec (the record bn_finalize(bound=...) left the bound in): the kernel also writes the fp16 x 2 planes of the output (out._planes);
     planes_only: and NOT the fp32 output -- `out` is then an unwritten placeholder that only plane-streaming kernels may consume"""
     rows, C = rows_of(y), y.shape[-1]
@@ -1194,7 +1195,7 @@ def bn_apply(y, mean, scale, beta, residual, relu, out=None, planes_rec=None, pl
     mask = None
     if want_mask and not (planes and planes_only) and relu_bits_ok(y, residual, relu, out):
         mask = torch.empty(lib.catseg_bn_mask_bytes(rows, C), dtype=torch.uint8, device=y.device)
-    rec = planes_rec if planes else new_amax(y.device) if _trunk_h2() else None
+    rec = planes_rec if planes else new_amax(y.device) if (_trunk_h2() and want_record) else None
     d = BnApplyDesc(y=ptr(y), ldy=ld_of(y), mean=ptr(mean), scale=ptr(scale), beta=ptr(beta), residual=ptr(residual), ldr=_ld(residual),
                     residual_record=ptr(amax_of(residual)) if planes and residual is not None else None,
                     z=None if planes and planes_only else ptr(out), ldz=ld_of(out), z_planes=ptr(buf), rows=rows, C=C, relu=1 if relu else 0,
@@ -1296,6 +1297,22 @@ def bn_backward(dz, z, y, stats, gamma, relu, dgamma, dbeta, dres=None, dres_acc
     # algorithmic bytes: two passes over (dz, y [or z, or its mask]) + dy written (+ the residual gradient)
     _bn_backward_call(dz, y, stats, gamma, dgamma, dbeta, 5 + (1 if dres is not None else 0), dy=ptr(dy_out), lddy=ld_of(dy_out), dy_record=ptr(rec),
                       dres=ptr(dres), lddres=_ld(dres), dres_accumulate=1 if dres_accumulate else 0, **_relu_source(z, relu, beta))
+    if rec is not None:
+        dy_out._amax = rec
+    return dy_out
+
+
+def bn_backward_frozen(dz, z, y, running_mean, running_var, eps, scale, relu, dgamma, dbeta, dres=None, dres_accumulate=False, dy_out=None, beta=None):
+    """bn_backward of a BatchNorm whose statistics are constants of the layer (engine.BatchNorm2d.frozen): the forward was bn_apply with
+    running_mean and `scale` = bn_eval_scale(gamma, running_var, eps); one streaming pass, dy = g * scale.  z / beta select the ReLU mask
+    source as in bn_backward; dgamma and dbeta may both be None (no sums, y read only for a recomputed mask)"""
+    if dy_out is None:
+        dy_out = torch.empty(y.shape, dtype=torch.float32, device=y.device)
+    rec = new_amax(y.device) if _trunk_h2() else None
+    # algorithmic bytes: dz and y (or z, or its mask) read once, dy written (+ the residual gradient)
+    _bn_backward_call(dz, y, None, None, dgamma, dbeta, 3 + (1 if dres is not None else 0), dy=ptr(dy_out), lddy=ld_of(dy_out), dy_record=ptr(rec),
+                      dres=ptr(dres), lddres=_ld(dres), dres_accumulate=1 if dres_accumulate else 0, frozen=1, running_mean=ptr(running_mean),
+                      running_var=ptr(running_var), eps=eps, scale=ptr(scale), **_relu_source(z, relu, beta))
     if rec is not None:
         dy_out._amax = rec
     return dy_out
