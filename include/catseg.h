@@ -654,7 +654,18 @@ int catseg_ingest_warp_u8(const uint8_t* img, const uint8_t* lbl, int B, int H, 
  *   catseg_aug_box_blur: ONE extended box-blur pass along axis (0 = H, 1 = W) with per-image (radius, ww, fw) of BoxBlur.c
  *     (radius[b] < 0: copy); ImageFilter.GaussianBlur(r) = 3 passes along W, then 3 along H, box radius from r (host side);
  *   catseg_aug_color_op: ONE operation of torchvision ColorJitter per image, in place: op[b] = 0 brightness, 1 contrast,
- *     2 saturation (factor[b] = the enhance factor), 3 hue (factor[b] = the integer H shift 0..255), < 0 none; workspace >= 8 B bytes. */
+ *     2 saturation (factor[b] = the enhance factor), 3 hue (factor[b] = the integer H shift 0..255), < 0 none; workspace >= 8 B bytes.
+ *     The workspace size selects the pipeline (op[] is device memory; the host cannot see which codes a call carries):
+ *       workspace_bytes <  CATSEG_AUG_WS_LUT(B) = roundup(8 B, 256) + 3072 B: the two ColorJitter launches; codes >= 4 are not served;
+ *       workspace_bytes >= CATSEG_AUG_WS_LUT(B): the extended pipeline (a 16-byte aligned workspace, H W < 2^31).  Codes 0 ... 3 give
+ *         the same bits, and 4 = ImageOps.autocontrast (cutoff 0), 5 = ImageOps.equalize, both per band (factor unused),
+ *         6 = ImageOps.posterize (factor[b] = bits, 1 ... 8), 7 = ImageOps.solarize (factor[b] = the threshold); codes < 0 or > 8
+ *         leave the image unchanged.  Layout: [B] 64-bit luma sums, at roundup(8 B, 256) [B][3][256] 32-bit histogram counters;
+ *       workspace_bytes >= CATSEG_AUG_WS_FULL(B, H, W) = CATSEG_AUG_WS_LUT(B) + 3 B H W: also 8 = ImageEnhance.Sharpness (factor[b] =
+ *         the enhance factor), which reads the neighbours from a copy of the frame at CATSEG_AUG_WS_LUT(B); below that size an
+ *         image with code 8 stays unchanged.  No byte at or behind workspace_bytes is written. */
+#define CATSEG_AUG_WS_LUT(B) ((((size_t)(B) * 8 + 255) / 256 * 256) + (size_t)(B) * 3072)
+#define CATSEG_AUG_WS_FULL(B, H, W) (CATSEG_AUG_WS_LUT(B) + (size_t)(B) * (size_t)(H) * (size_t)(W) * 3)
 int catseg_aug_pad_flip_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, int C, const int32_t* flips, int pad_top,
                            int pad_bottom, catseg_stream_t stream);
 int catseg_aug_box_blur(const uint8_t* in, uint8_t* out, int B, int H, int W, int axis, const int32_t* radius, const uint32_t* ww,

@@ -2527,12 +2527,27 @@ def aug_gaussian_blur(img, radius, ww, fw):
     return a
 
 
-def aug_color_op(img, op, factor):
-    """one torchvision ColorJitter operation per image, IN PLACE (op 0 brightness, 1 contrast, 2 saturation, 3 hue with factor = H shift)"""
+def aug_color_workspace_bytes(B, H, W, extended=None):
+    """the workspace sizes of catseg_aug_color_op (include/catseg.h): None = the ColorJitter pipeline (op codes < 4), "lut" = the extended
+    pipeline with the band histograms (codes 0 ... 7; CATSEG_AUG_WS_LUT), "full" = with the source copy as well (code 8; CATSEG_AUG_WS_FULL)"""
+    if extended is None:
+        return 8 * B + 256
+    if extended not in ("lut", "full"):
+        raise ValueError("aug_color_op: extended must be None, 'lut' or 'full', got %r" % (extended,))
+    lut = (8 * B + 255) // 256 * 256 + 3072 * B
+    return lut if extended == "lut" else lut + 3 * B * H * W
+
+
+def aug_color_op(img, op, factor, extended=None):
+    """one photometric operation per image, IN PLACE.  op 0 brightness, 1 contrast, 2 saturation (factor = the enhance factor), 3 hue (factor
+    = the H shift): torchvision ColorJitter's, two launches.  extended="lut" adds 4 autocontrast, 5 equalize, 6 posterize (factor = bits),
+    7 solarize (factor = threshold); extended="full" adds 8 sharpness (factor = the enhance factor), which needs a copy of the frames in
+    the workspace.  The library picks the pipeline from the workspace size it is handed, so exactly the size asked for is passed on."""
     assert img.dtype == torch.uint8 and img.is_contiguous() and img.is_cuda and img.shape[-1] == 3
     B, H, W, _ = img.shape
-    ws = workspace(8 * B + 256, img.device)
-    check(lib.catseg_aug_color_op(ptr(img), B, H, W, ptr(op), ptr(factor), ptr(ws), ws.numel(), stream()))
+    nbytes = aug_color_workspace_bytes(B, H, W, extended)
+    ws = workspace(nbytes, img.device)
+    check(lib.catseg_aug_color_op(ptr(img), B, H, W, ptr(op), ptr(factor), ptr(ws), nbytes, stream()))
     return img
 
 

@@ -1,5 +1,6 @@
 from .classes import CADIS_PALETTE, CATEGORIES, CLASS_REMAP, IGNORE_LABEL, NUM_CLASSES, ce_ignore_index, num_classes  # noqa: F401
-from .augment import GpuAugment, gaussian_box_params, pseudo_jitter_ranges, pseudo_jitter_strength, sample_blur, sample_color_jitter  # noqa: F401
+from .augment import (GpuAugment, check_randaugment, gaussian_box_params, pseudo_jitter_ranges, pseudo_jitter_strength,  # noqa: F401
+                      randaugment_from_transforms, randaugment_space, sample_blur, sample_color_jitter, sample_randaugment)
 from .ingest import GpuIngest, check_label_tables, label_tables_of, remap_lut, sample_flips  # noqa: F401
 from .semi import BalancedConcatDataset  # noqa: F401
 from .geometry import (affine_inverse, class_frequencies, crop_freq_region, crop_px, freq_weight_table, geometry_from_transforms,  # noqa: F401

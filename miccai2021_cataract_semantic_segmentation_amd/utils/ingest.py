@@ -59,7 +59,8 @@ def check_label_tables(label_tables, batch, tables=2):
 
 
 def _jitters(jitter):
-    """jitter: None, one (orders, factors) pair, or a list of pairs applied in turn (colorjitter, then pseudo_colorjitter)"""
+    """jitter: None, one (orders, factors) pair, or a list of pairs applied in turn (colorjitter, then pseudo_colorjitter); photometric=
+    takes the same forms with (ops, values) pairs"""
     if jitter is None:
         return []
     return list(jitter) if isinstance(jitter, list) else [jitter]
@@ -76,7 +77,8 @@ class GpuIngest:
         self.mean = torch.tensor(TORCHVISION_MEAN, device=self.device) if normalise else None
         self.std = torch.tensor(TORCHVISION_STD, device=self.device) if normalise else None
 
-    def __call__(self, img, lbl, flips=None, nhwc4=False, blur_radii=None, jitter=None, affine=None, crop=None, label_tables=None):
+    def __call__(self, img, lbl, flips=None, nhwc4=False, blur_radii=None, jitter=None, affine=None, crop=None, label_tables=None,
+                 photometric=None):
         """label_tables: HOST int [B] (None = 0 everywhere), per frame 0 = the label map holds raw CaDIS ids and is remapped, 1 = it holds
         network ids already (a pseudo-labelled frame) and passes through: a mixed batch is still one launch.
         affine: float64 [B,3,3] frame -> canvas matrices (utils.geometry.sample_affine): the frame is warped onto the reference's
@@ -87,7 +89,9 @@ class GpuIngest:
         (CropNP 'freq'; needs lbl) by two small launches ahead of the ingest's, on the same stream.
         blur_radii: per-frame GaussianBlur radius (0 = none; utils.augment.sample_blur); jitter: (orders, factors) of
         utils.augment.sample_color_jitter, or a list of such pairs applied in turn.  With either, the image takes the reference's order of operations on uint8
-        (flip + reflect pad -> blur -> colour jitter -> ToTensor / Normalize: utils/utils.py:394-447) in a few more kernels."""
+        (flip + reflect pad -> blur -> colour jitter -> ToTensor / Normalize: utils/utils.py:394-447) in a few more kernels.
+        photometric: (ops, values) of utils.augment.sample_randaugment (any op codes -1 ... 8 of GpuAugment.color_ops), or a list of such
+        pairs; applied after jitter, on the same uint8 frames."""
         img = img.to(self.device, non_blocking=True) if img is not None else None
         lbl = lbl.to(self.device, non_blocking=True) if lbl is not None else None
         if flips is not None:
@@ -99,8 +103,8 @@ class GpuIngest:
         lut = self.luts if tables is not None else self.lut
         from .. import ops   # needs libcatseg_hip.so; the table / flag helpers above do not
         if affine is not None or crop is not None:
-            return self._warped(ops, img, lbl, flips, nhwc4, blur_radii, jitter, affine, crop, lut, tables)
-        if img is not None and (blur_radii is not None or jitter is not None):
+            return self._warped(ops, img, lbl, flips, nhwc4, blur_radii, jitter, affine, crop, lut, tables, photometric)
+        if img is not None and (blur_radii is not None or jitter is not None or photometric is not None):
             from .augment import GpuAugment
             aug = GpuAugment(self.device)
             u8 = ops.aug_pad_flip_u8(img.contiguous(), flips, self.pad[0], self.pad[1])
@@ -108,14 +112,16 @@ class GpuIngest:
                 u8 = aug.blur(u8, blur_radii)
             for orders, factors in _jitters(jitter):
                 u8 = aug.color_jitter(u8, orders, factors)
+            for codes, values in _jitters(photometric):
+                u8 = aug.color_ops(u8, codes, values)
             x = ops.ingest_u8(u8, None, self.lut, None, 0, 0, self.mean, self.std, nhwc4=nhwc4)[0]
             labels = ops.ingest_u8(None, lbl, lut, flips, self.pad[0], self.pad[1], self.mean, self.std, tables=tables)[1] if lbl is not None \
                 else None
             return x, labels
         return ops.ingest_u8(img, lbl, lut, flips, self.pad[0], self.pad[1], self.mean, self.std, nhwc4=nhwc4, tables=tables)
 
-    def _warped(self, ops, img, lbl, flips, nhwc4, blur_radii, jitter, affine, crop, lut, tables):
-        """one warp launch for image and labels; with blur / jitter the image leaves it as uint8 and goes on as in __call__"""
+    def _warped(self, ops, img, lbl, flips, nhwc4, blur_radii, jitter, affine, crop, lut, tables, photometric=None):
+        """one warp launch for image and labels; with blur / jitter / photometric the image leaves it as uint8 and goes on as in __call__"""
         from .geometry import affine_inverse
         ref = img if img is not None else lbl
         H, W = int(ref.shape[1]), int(ref.shape[2])
@@ -131,7 +137,7 @@ class GpuIngest:
         else:
             origin, window = (crop[0], (int(crop[1]), int(crop[1]))) if crop is not None else (None, canvas)
         pad = self.pad if crop is None else (0, 0)          # utils/utils.py:396: padding only if no cropping has happened
-        staged = img is not None and (blur_radii is not None or jitter is not None)
+        staged = img is not None and (blur_radii is not None or jitter is not None or photometric is not None)
         form = "u8" if staged else ("nhwc4" if nhwc4 else "nchw")
         out = ops.ingest_warp_u8(img.contiguous() if img is not None else None, lbl.contiguous() if lbl is not None else None, lut, flips,
                                  minv, canvas, origin, window, pad[0], pad[1], self.mean, self.std, outputs=(form,), tables=tables)
@@ -143,5 +149,7 @@ class GpuIngest:
                 x = aug.blur(x, blur_radii)
             for orders, factors in _jitters(jitter):
                 x = aug.color_jitter(x, orders, factors)
+            for codes, values in _jitters(photometric):
+                x = aug.color_ops(x, codes, values)
             x = ops.ingest_u8(x, None, self.lut, None, 0, 0, self.mean, self.std, nhwc4=nhwc4)[0]
         return x, out["labels"]

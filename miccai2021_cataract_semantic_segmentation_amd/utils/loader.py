@@ -19,7 +19,8 @@ picked on the device from the warped labels (csrc/cropfreq.hip) ahead of the ing
 A ``utils.BalancedConcatDataset(labelled, pseudo)`` with ``labels_remapped=(False, True)`` gives semi-supervised batches: batch_size // 2
 items, laid out [labelled frames | pseudo-labelled frames] as losses.SemiSupervisedLoss splits them; the pseudo frames' label maps hold network
 ids already and pass the remap table by (GpuIngest's label_tables), still in the one ingest launch.  pseudo_colorjitter=s adds the
-'pseudo_colorjitter' keyword's RandomApply(ColorJitter(strength s), p=0.7) after colorjitter.
+'pseudo_colorjitter' keyword's RandomApply(ColorJitter(strength s), p=0.7) after colorjitter.  randaugment= adds RandAugment's photometric
+operations (utils.augment.sample_randaugment) after both, on all frames or on the pseudo-labelled half only.
 """
 import multiprocessing
 import multiprocessing.connection
@@ -31,7 +32,8 @@ import threading
 import numpy as np
 import torch
 
-from .augment import PSEUDO_JITTER_PROBABILITY, pseudo_jitter_ranges, sample_blur, sample_color_jitter
+from .augment import (PSEUDO_JITTER_PROBABILITY, check_randaugment, pseudo_jitter_ranges, sample_blur, sample_color_jitter,
+                      sample_randaugment)
 from .geometry import (check_affine, check_crop, check_freq_weights, class_frequencies, crop_freq_region, crop_px, freq_weight_table,
                        sample_affine, sample_crops, sample_freq_u)
 from .ingest import GpuIngest, sample_flips
@@ -147,7 +149,8 @@ class _WorkerPool:
 class PinnedFrameLoader:
     def __init__(self, dataset, batch_size, experiment, sampler=None, shuffle=True, drop_last=True, flip_probability=(0.0, 0.5),
                  pad=(2, 2), normalise=False, nhwc4=False, device="cuda", prefetch=3, workers=0, seed=0, rank=0, world=1,
-                 blur=False, colorjitter=False, worker_processes=0, affine=None, crop=None, labels_remapped=None, pseudo_colorjitter=None):
+                 blur=False, colorjitter=False, worker_processes=0, affine=None, crop=None, labels_remapped=None, pseudo_colorjitter=None,
+                 randaugment=None):
         """blur / colorjitter: the 'blur' / 'colorjitter' entries of the reference's `transforms` config list (utils/utils.py:412-417):
         BlurPIL(probability=.05, kernel_limits=(3, 7)) and ColorJitter((2/3, 1.5) x 3, hue (-.05, .05)) on the padded uint8 frames,
         as GPU kernels (utils/augment.py).
@@ -155,7 +158,10 @@ class PinnedFrameLoader:
         Their draws are seeded per epoch like the flips; with a crop the rows are not padded (the reference's pad rule).
         labels_remapped: per member of a two-member BalancedConcatDataset, whether its label maps hold network ids already
         (DatasetFromDF(labels_remaped=True), datasets/Dataset_from_df.py:49-53); (False, True) is the one form taken: labelled, then pseudo.
-        pseudo_colorjitter: the strength s in {1, 2, 3} of the 'pseudo_colorjitter' keyword (utils/utils.py:419-436; True = the default 2)"""
+        pseudo_colorjitter: the strength s in {1, 2, 3} of the 'pseudo_colorjitter' keyword (utils/utils.py:419-436; True = the default 2)
+        randaugment: the dict utils.augment.randaugment_from_transforms returns ({num_ops, magnitude, bins, p, frames}; True = the defaults):
+        RandAugment's photometric entries on the uint8 frames after every jitter.  Its draws continue the epoch's torch generator AFTER
+        all jitter draws of the epoch; frames "pseudo" gives only the pseudo-labelled rows of a paired batch operations"""
         from .class_sampling import AdaptiveBatchSampler
         if isinstance(sampler, AdaptiveBatchSampler):
             raise ValueError("PinnedFrameLoader: adaptive batches are refused -- this loader fills its batches `prefetch` steps ahead, so a "
@@ -175,6 +181,11 @@ class PinnedFrameLoader:
         self.pseudo_jitter = None
         if pseudo_colorjitter is not None and pseudo_colorjitter is not False:
             self.pseudo_jitter = pseudo_jitter_ranges(2 if pseudo_colorjitter is True else pseudo_colorjitter)
+        self.randaugment = None
+        if randaugment is not None and randaugment is not False:
+            self.randaugment = check_randaugment(randaugment)
+            if self.randaugment["frames"] == "pseudo" and not self.paired:
+                raise ValueError("PinnedFrameLoader: randaugment frames 'pseudo' needs semi-supervised batches (a BalancedConcatDataset)")
         self.device = torch.device(device)
         self.ingest = GpuIngest(experiment, pad=pad, normalise=normalise, device=device)
         self.flip_p, self.nhwc4 = flip_probability, nhwc4
@@ -205,8 +216,15 @@ class PinnedFrameLoader:
         # thread only enqueues the host -> device copy and the ingest kernels (immune to the interpreter lock and to a slow __getitem__)
         self.nproc = max(int(worker_processes), 0)
         self._pool = None
-        self.copy_stream = torch.cuda.Stream(device=self.device)
+        self._copy_stream = None
         self._slots = None
+
+    @property
+    def copy_stream(self):
+        """the side stream of the host -> device copies, made when the first epoch needs it (the constructor touches no device)"""
+        if self._copy_stream is None:
+            self._copy_stream = torch.cuda.Stream(device=self.device)
+        return self._copy_stream
 
     def close(self):
         if self._pool is not None:
@@ -348,14 +366,10 @@ class PinnedFrameLoader:
             for ev, _ in in_copy:
                 ev.synchronize()
 
-    def __iter__(self):
-        idx = self._indices()
-        self.epoch += 1
-        batches = [idx[i:i + self.per_batch] for i in range(0, len(idx), self.per_batch)]
-        if self.drop_last and batches and len(batches[-1]) < self.per_batch:
-            batches.pop()
-        if self.paired:        # staging rows [labelled frames | pseudo-labelled frames]: one (member, index) key per row
-            batches = [[(0, i) for i in b] + [(1, i) for i in b] for b in batches]
+    def _draws(self, batches):
+        """the host draws of the epoch self.epoch that do not depend on the frames: (the numpy stream, which the geometry continues; flips,
+        blur radii, jitters, photometric (ops, values) pairs -- each one entry per batch, or None).  One numpy RandomState: flips, then
+        blurs; one torch generator: colorjitter, then pseudo_colorjitter, then -- after ALL jitter draws of the epoch -- randaugment"""
         rng = np.random.RandomState(self.seed * 1000003 + self.epoch)
         flips = [sample_flips(len(b), self.flip_p, rng) for b in batches]
         gen = torch.Generator().manual_seed(self.seed * 1000003 + self.epoch)
@@ -364,6 +378,26 @@ class PinnedFrameLoader:
         if self.pseudo_jitter is not None:      # after colorjitter, the reference's order (utils/utils.py:415-436)
             jitters = [([j] if j is not None else []) + [sample_color_jitter(len(b), generator=gen, apply_probability=PSEUDO_JITTER_PROBABILITY,
                                                                             **self.pseudo_jitter)] for j, b in zip(jitters, batches)]
+        photometric = None
+        if self.randaugment is not None:
+            ra, photometric = self.randaugment, []
+            for b in batches:
+                codes, values = sample_randaugment(len(b), ra["num_ops"], ra["magnitude"], ra["bins"], generator=gen, apply_probability=ra["p"])
+                if ra["frames"] == "pseudo":    # rows [labelled | pseudo-labelled]: the labelled ones carry no operation
+                    labelled = np.array([m == 0 for m, _ in b])
+                    codes[labelled], values[labelled] = -1, 0.0
+                photometric.append((codes, values))
+        return rng, flips, blurs, jitters, photometric
+
+    def __iter__(self):
+        idx = self._indices()
+        self.epoch += 1
+        batches = [idx[i:i + self.per_batch] for i in range(0, len(idx), self.per_batch)]
+        if self.drop_last and batches and len(batches[-1]) < self.per_batch:
+            batches.pop()
+        if self.paired:        # staging rows [labelled frames | pseudo-labelled frames]: one (member, index) key per row
+            batches = [[(0, i) for i in b] + [(1, i) for i in b] for b in batches]
+        rng, flips, blurs, jitters, photometric = self._draws(batches)
         ready = queue.Queue(maxsize=self.prefetch)
         free = queue.Queue()
         first = self.frames[batches[0][0]] if batches else None
@@ -371,6 +405,9 @@ class PinnedFrameLoader:
         if self.paired:
             for g, b in zip(geos, batches):
                 g["label_tables"] = np.array([m for m, _ in b], dtype=np.int32)     # member 1 = network ids already: the identity row
+        if photometric is not None:             # (it travels in the batch's ingest arguments, to threads and worker processes alike)
+            for g, ph in zip(geos, photometric):
+                g["photometric"] = ph
         if first is not None and (self._slots is None or tuple(self._slots[0][0].shape[1:3]) != tuple(np.asarray(first[0]).shape[:2])
                                   or (self.nproc and self._pool is None)):
             self._alloc(*np.asarray(first[0]).shape[:2])
