@@ -275,7 +275,17 @@ _SIGS = {
     "catseg_ema_table": (I, [P, I, P, I, F, P, P]),
     "catseg_ema_grid_cap": (I, []),
 }
-for _name, (_res, _args) in _SIGS.items():
+# include/ext/catseg_contrast.h: the entry points of the dense contrastive loss, a table of their own beside the core surface (EXPORTS is
+# what the headers directly under include/ declare)
+_SIGS_CONTRAST = {
+    "catseg_contrast_pick_workspace": (SZ, [I, I, I, I]),
+    "catseg_contrast_pick": (I, [P, I, I, I, I, I, I, I, P, P, I, P, P, P, P, SZ, P]),
+    "catseg_contrast_gather": (I, [P, I, L, I, P, I, F, P, P, P]),
+    "catseg_contrast_rows": (I, [P, I, I, P, P, I, F, P, P, P]),
+    "catseg_contrast_finalize": (I, [P, I, P, P, P]),
+    "catseg_contrast_scatter_bwd": (I, [P, P, I, P, P, I, I, P, F, P, L, P]),
+}
+for _name, (_res, _args) in list(_SIGS.items()) + list(_SIGS_CONTRAST.items()):
     _fn = getattr(lib, _name)  # AttributeError here = header / library mismatch
     _fn.restype = _res
     _fn.argtypes = _args

@@ -1,13 +1,13 @@
 // Philox4x32-10, the generator of every device-side draw (csrc/dropout.hip: the Dropout2d masks; csrc/pointrend_train.hip: PointRend's training
-// points).  A draw is philox4x32_10(counter, key = (seed lo, seed hi)) with counter = (group of four elements, draw number, STREAM,
-// layer | rank << 16): the STREAM word keeps the consumers apart (PHILOX_STREAM_DROPOUT, PHILOX_STREAM_POINTS), so that two of them seeded
+// points; csrc/contrast.hip: the anchors of the dense contrastive loss).  A draw is philox4x32_10(counter, key = (seed lo, seed hi)) with counter = (group of four elements, draw number, STREAM,
+// layer | rank << 16): the STREAM word keeps the consumers apart (PHILOX_STREAM_DROPOUT, PHILOX_STREAM_POINTS, PHILOX_STREAM_ANCHORS), so that two of them seeded
 // alike never share a block of random bits.
 #pragma once
 #include <hip/hip_runtime.h>
 
 typedef unsigned ph_u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr unsigned PHILOX_STREAM_DROPOUT = 0u, PHILOX_STREAM_POINTS = 1u;
+constexpr unsigned PHILOX_STREAM_DROPOUT = 0u, PHILOX_STREAM_POINTS = 1u, PHILOX_STREAM_ANCHORS = 2u;
 
 __device__ __forceinline__ ph_u32x4 philox4x32_10(ph_u32x4 c, unsigned k0, unsigned k1) {
 #pragma unroll

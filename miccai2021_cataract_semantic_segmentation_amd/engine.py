@@ -118,6 +118,24 @@ class PointSampler(nn.Module, _DeviceRng):
         return self.fixed_points is None
 
 
+class AnchorSampler(nn.Module, _DeviceRng):
+    """The draws of the dense contrastive loss's anchor pick (ops.contrast_pick, counter word 2 = 2).  No parameters.  Owned by
+    models.Projector, so that what holds for a model's buffers holds for it: graph.GraphedTrainStep seeds it before the capture and restores
+    it around the warm-up, dist.attach gives it the rank.  The managers bind it to the loss (loss.sampler = model.projector_model.sampler).
+    fixed_u: a test knob -- an int32 tensor of K * M values in [0, 2^24) used instead of the draws (the state does not move)."""
+
+    def __init__(self, layer=0):
+        super().__init__()
+        self._init_rng(layer)
+        self.fixed_u = None
+
+    def forward(self, x):  # pragma: no cover
+        raise RuntimeError("engine AnchorSampler is read by losses.DenseContrastiveLoss, not called directly")
+
+    def draws(self):
+        return self.fixed_u is None
+
+
 def rng_modules(module):
     """the modules of a network that own a device generator state"""
     return [m for m in module.modules() if isinstance(m, _DeviceRng)]

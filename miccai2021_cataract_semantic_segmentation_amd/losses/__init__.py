@@ -6,3 +6,4 @@ from .wrapper import LossWrapper  # noqa: F401
 from .overlap import GenDiceLoss, SoftIoU  # noqa: F401
 from .focal import FocalLoss  # noqa: F401
 from .semi import SemiSupervisedLoss  # noqa: F401
+from .contrast import DenseContrastiveLoss  # noqa: F401

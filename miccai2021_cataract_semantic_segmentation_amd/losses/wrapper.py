@@ -4,6 +4,7 @@ import torch
 from torch import nn
 
 from ..utils import ce_ignore_index
+from .contrast import DenseContrastiveLoss
 from .cross_entropy import CrossEntropyLoss
 from .lovasz import LovaszSoftmax
 from .ohem import OhemCrossEntropy
@@ -28,6 +29,8 @@ class LossWrapper(nn.Module):
                 fct = TwoScaleLoss(config)
             elif name == "OhemCrossEntropy":
                 fct = OhemCrossEntropy(config)
+            elif name == "DenseContrastiveLoss":
+                fct = DenseContrastiveLoss(config)
             else:
                 raise NotImplementedError("loss '{}' is outside the accelerated path".format(name))
             self.loss_classes[name] = fct
@@ -47,6 +50,9 @@ class LossWrapper(nn.Module):
             elif name == "LovaszSoftmax":
                 off = self.dc_off and epoch is not None and epoch < self.config["dc_off_at_epoch"]
                 loss = zero if off else self.loss_classes[name](prediction, labels)
+            elif name == "DenseContrastiveLoss":
+                off = self.dc_off and epoch is not None and epoch >= self.config["dc_off_at_epoch"]
+                loss = zero if off else self.loss_classes[name](labels, deep_features)
             elif name == "TwoScaleLoss":
                 loss = self.loss_classes[name](interm_prediction, prediction, labels.long())
             else:

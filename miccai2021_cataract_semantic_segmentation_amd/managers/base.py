@@ -30,7 +30,7 @@ from .. import losses as _losses
 from .. import models as _models
 from ..optim import FusedOptimizer, WeightAverage, accumulate_config, average_config, build_average, build_optimiser
 from ..utils import LRFcts
-from ..utils.metrics import t_get_confusion_matrix, t_get_mean_iou, t_get_pixel_accuracy
+from ..utils.metrics import t_get_confusion_matrix, t_get_mean_iou, t_get_pixel_accuracy, t_normalise_confusion_matrix
 
 DEFAULTS = {"mode": "training", "debugging": False, "log_every_n_epochs": 100, "max_valid_imgs": 10, "cuda": True,
             "gpu_device": 0, "seed": 0, "tta": False, "log_path": "logs"}
@@ -131,6 +131,7 @@ class BaseManager:
         self.labeled_validation = False      # inside _eval_pass(with_loss=True): a SemiSupervisedLoss scores the whole batch as labelled
         if self.config["mode"] == "training":
             self.load_loss()
+            self.bind_contrast()
             torch.manual_seed(self.config["seed"])      # after model construction, as BaseManager.py:104-112
             self.load_optimiser()
             if self.accumulate > 1:
@@ -270,6 +271,33 @@ class BaseManager:
             return DataLoader(self.train_set, batch_size=bs, sampler=shard(sampler), drop_last=True, num_workers=0)
         raise ValueError("Dataloader special type '{}' not recognised".format(name))
 
+    def contrast_loss(self):
+        """the DenseContrastiveLoss of a LossWrapper, or None"""
+        if isinstance(self.loss, _losses.LossWrapper):
+            return self.loss.loss_classes.get("DenseContrastiveLoss")
+        return None
+
+    def bind_contrast(self):
+        """the anchors of a DenseContrastiveLoss are drawn from the projector's device state (engine.AnchorSampler): a buffer of the model,
+        which graph.GraphedTrainStep seeds before its capture and restores around its warm-up, and which dist.attach gives the rank"""
+        dc = self.contrast_loss()
+        if dc is None:
+            return
+        proj = getattr(self.model, "projector_model", None)
+        if proj is None:
+            raise ValueError("the loss 'DenseContrastiveLoss' contrasts the output of a projector: the model's configuration has no "
+                             "'projector' key")
+        if dc.K != self.model.num_classes:
+            raise ValueError("DenseContrastiveLoss was built for %d classes, the model predicts %d" % (dc.K, self.model.num_classes))
+        dc.sampler = proj.sampler
+
+    def update_contrast(self, running_cm):
+        """the end of a training epoch, managers/OCRNet_Manager.py:124-131 of the reference (without the TensorBoard figure): the epoch's
+        column-normalised confusion matrix goes to the contrastive loss"""
+        dc = self.contrast_loss()
+        if dc is not None:
+            dc.update_confusion_matrix(t_normalise_confusion_matrix(running_cm, mode="col"))
+
     # ------------------------------------------------------------------ hooks for the subclasses
     def forward_loss(self, img, lbl):
         """returns (loss, final logits)"""
@@ -362,6 +390,7 @@ class BaseManager:
                 self.optimiser.step()
         if graphed is not None:
             graphed.release()
+        self.update_contrast(running_cm)         # (this rank's matrix: each rank contrasts its own anchors with its own table)
         if self.scheduler is not None:
             self.scheduler.step()
         if self.world > 1:                       # logged training metrics are GLOBAL: one exchange per epoch

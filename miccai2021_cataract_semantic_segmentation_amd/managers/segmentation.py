@@ -11,7 +11,10 @@ class OCRNetManager(BaseManager):
     """managers/OCRNet_Manager.py:12-245: the model returns (interm, final); TwoScaleLoss takes both."""
 
     def forward_loss(self, img, lbl):
-        interm, out = self.model(img.float())
+        if self.model.projector_model is not None and isinstance(self.loss, LossWrapper):       # (:82-84 of the reference's manager)
+            interm, out, proj = self.model(img.float())
+            return self.loss(proj, out, lbl.long(), interm_prediction=interm), out
+        interm, out = self.model(img.float())[:2]
         if isinstance(self.loss, LossWrapper):
             return self.loss(None, out, lbl.long(), interm_prediction=interm), out
         if isinstance(self.loss, SemiSupervisedLoss):
@@ -27,11 +30,19 @@ class DeepLabv3PlusManager(BaseManager):
 
     def forward_loss(self, img, lbl):
         out = self.model(img.float())
+        if getattr(self.model, "projector_model", None) is not None:       # (out, proj): managers/DeepLabv3Plus_Manager.py:80-82
+            out, proj = out
+            if isinstance(self.loss, LossWrapper):
+                return self.loss(proj, out, lbl.long()), out
         if isinstance(self.loss, LossWrapper):
             return self.loss(None, out, lbl.long()), out
         if isinstance(self.loss, SemiSupervisedLoss):
             return self.semi_loss(out, lbl.long()), out
         return self.loss(out, lbl.long()), out
+
+
+    def final_output(self, out):
+        return out[0] if isinstance(out, tuple) else out        # (with a projector the logits come first)
 
 
 class DeepLabv3Manager(DeepLabv3PlusManager):

@@ -6,6 +6,7 @@ from torch import nn
 from ..engine import (BatchNorm2d, Conv2d, EngineNet, bilinear, image_hw, concat_views, conv_bias, conv_bn_act, global_avgpool)
 from ..utils import num_classes
 from .backbone import ResNetBackbone, load_pretrained_trunk
+from .Projector import make_projector
 
 
 def _bn(c):
@@ -89,9 +90,7 @@ class DeepLabv3Plus(EngineNet):
         mult = 1 if self.out_stride >= 16 else 2
         self.aspp = ASPP(self.high_level_channels, self.c_aspp, mult)
         self.decoder = Decoder(self.low_level_channels, self.c_aspp, self.num_classes)
-        if "projector" in config:
-            raise NotImplementedError("the contrastive projector is outside the accelerated path")
-        self.projector_model = None
+        self.projector_model = make_projector(config, self.high_level_channels)      # models/DeepLabv3Plus.py:50-56 of the reference
         self.apply_freeze_bn(config)
 
     def _body(self, cx, x):
@@ -99,7 +98,10 @@ class DeepLabv3Plus(EngineNet):
         f = self.backbone.run(cx, x)
         a = self.aspp.run(cx, f["high"])
         logits = self.decoder.run(cx, f["low"], a)
-        return [bilinear(cx, logits, H, W, True)]
+        outs = [bilinear(cx, logits, H, W, True)]
+        if self.projector_model is not None:          # models/DeepLabv3Plus.py:70-72: (out, proj)
+            outs.append(self.projector_model.run(cx, f["high"]))
+        return outs
 
 
 class DeepLabv3(EngineNet):
@@ -124,12 +126,14 @@ class DeepLabv3(EngineNet):
         self.backbone_out_channels = self.backbone.out_channels("layer4")
         self.aspp = ASPP(self.backbone_out_channels, self.c_aspp, 1 if self.out_stride >= 16 else 2)
         self.conv_out = Conv2d(self.c_aspp, self.num_classes, 1, 1)
-        if "projector" in config:
-            raise NotImplementedError("the contrastive projector is outside the accelerated path")
-        self.projector_model = None
+        self.projector_model = make_projector(config, self.backbone_out_channels)     # models/DeepLabv3.py:51-56 of the reference
         self.apply_freeze_bn(config)
 
     def _body(self, cx, x):
         H, W = image_hw(x)
-        a = self.aspp.run(cx, self.backbone.run(cx, x)["out"])
-        return [bilinear(cx, conv_bias(cx, a, self.conv_out), H, W, True)]
+        out = self.backbone.run(cx, x)["out"]
+        a = self.aspp.run(cx, out)
+        outs = [bilinear(cx, conv_bias(cx, a, self.conv_out), H, W, True)]
+        if self.projector_model is not None:          # models/DeepLabv3.py:67-69: (out, proj)
+            outs.append(self.projector_model.run(cx, out))
+        return outs

@@ -12,6 +12,7 @@ from ..engine import (BatchNorm2d, Conv2d, EngineNet, PointSampler, adaptive_avg
                       conv_bn_act, copy_into, maxpool, pointrend_refine, pointrend_train)
 from ..utils import num_classes
 from .backbone import BasicBlock, Bottleneck, _c1, load_pretrained_trunk
+from .Projector import make_projector
 
 
 class _GroupedBottleneck(nn.Module):
@@ -257,9 +258,8 @@ class EncDec(EngineNet):
         config["decoder"]["input_channels"] = self.enc_model.out_channels()
         config["decoder"]["input_scales"] = [4, 8, 16, 32]
         self.dec_model = _DECODERS[config["decoder"]["model"]](config["decoder"], experiment)
-        if "projector" in config:
-            raise NotImplementedError("the contrastive projector is outside the accelerated path")
-        self.projector_model = None
+        # models/EncDec.py:32-37 of the reference: the projector reads the last encoder stage; deep_features is then its output
+        self.projector_model = make_projector(config, self.enc_model.out_channels()[-1])
         self.get_features = True
         self.num_classes = self.dec_model.num_classes
         self.out_stride = 32
@@ -281,4 +281,7 @@ class EncDec(EngineNet):
         feats = self.enc_model.run(cx, x)
         pred = self.dec_model.run(cx, feats)
         pred = list(pred) if isinstance(pred, tuple) else [pred]
-        return [feats[-1]] + pred if self.get_features else pred
+        if not self.get_features:
+            return pred
+        deep = feats[-1] if self.projector_model is None else self.projector_model.run(cx, feats[-1])
+        return [deep] + pred

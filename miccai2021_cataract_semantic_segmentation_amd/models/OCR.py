@@ -9,6 +9,7 @@ from ..engine import (BatchNorm2d, Conv2d, EngineNet, bilinear, image_hw, concat
                       object_attention_core, spatial_gather)
 from ..utils import num_classes
 from .backbone import ResNetBackbone, load_pretrained_trunk
+from .Projector import make_projector
 from .HRNetv2 import build_hrnet_trunk, concat_branches, run_hrnet_trunk
 
 
@@ -115,9 +116,12 @@ class OCRNet(EngineNet):
         self.spatial_gather = SpatialGatherModule(self.num_classes)
         self.spatial_ocr_head = SpatialOCR_Module(512, 256, 512, 1, self.dropout)
         self.conv_out = Conv2d(512, self.num_classes, 1, 1, bias=True)
-        if "projector" in config:
-            raise NotImplementedError("the contrastive projector is outside the accelerated path")
-        self.projector_model = None
+        if "projector" in config and not isinstance(self.backbone, ResNetBackbone):
+            raise NotImplementedError("OCRNet(backbone='%s') with a contrastive projector is outside the accelerated path: the HRNet trunk's "
+                                      "'high' output exists only as the operand planes of the two head convolutions (and the reference "
+                                      "raises for this pairing: its HRNet trunk has no 'high' of high_out_channels)" % self.backbone_name)
+        # models/OCR.py:99-105 of the reference: the projector reads the trunk's 'high' output
+        self.projector_model = make_projector(config, self.high_out_channels)
         self.apply_freeze_bn(config)
 
     def _body(self, cx, x):
@@ -141,5 +145,8 @@ class OCRNet(EngineNet):
         engine.tap("logits_lowres", logits)
         up = bilinear(cx, logits, H, W, True)
         if self.get_intermediate:
-            return [bilinear(cx, interm, H, W, True), up]
+            outs = [bilinear(cx, interm, H, W, True), up]
+            if self.projector_model is not None:      # models/OCR.py:132-134: (interm, out, proj)
+                outs.append(self.projector_model.run(cx, high))
+            return outs
         return [up]

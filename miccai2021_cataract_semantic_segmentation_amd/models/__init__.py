@@ -5,4 +5,5 @@ from .EncDec import EncDec, PointRend, StandardPointHead, UPerNet  # noqa: F401
 from .FCN import FCN  # noqa: F401
 from .UNet import UNet  # noqa: F401
 from .Ensemble import Ensemble  # noqa: F401
+from .Projector import Projector  # noqa: F401
 from . import backbone  # noqa: F401

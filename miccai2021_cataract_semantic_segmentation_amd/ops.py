@@ -2790,3 +2790,77 @@ def pointrend_refine(seg, feats, head, k0, steps, record=None):
             record.append({"idx": idx, "uncertainty": unc})
         seg = up
     return seg
+
+
+# ---- the dense contrastive loss over K * M anchor slots (include/ext/catseg_contrast.h; losses.DenseContrastiveLoss).  Thin wrappers: the
+# loss module owns the buffers that live from its forward to its backward (Z, S / G).  r4(n) = n rounded up to a multiple of 4.
+CONTRAST_MAX_ANCHORS = 8192
+
+
+def r4(n):
+    return (n + 3) // 4 * 4
+
+
+def contrast_pick(labels, h, w, K, M, state=None, fixed_u=None, eval_mode=False):
+    """the anchors of one batch -> (idx [A], label [A], n_pos [1]), int32 on the device, A = K * M.  labels: int64 [B, H, W]; (h, w): the
+    feature map.  A training draw reads the 16-byte device state and advances its draw counter; with fixed_u (int32 [A]) or eval_mode
+    (u24 = 2^23) the state does not move."""
+    B, H, W = labels.shape
+    A = K * M
+    if A > CONTRAST_MAX_ANCHORS:
+        raise ValueError("contrast_pick: K * M = %d anchor slots exceed %d" % (A, CONTRAST_MAX_ANCHORS))
+    assert labels.dtype == torch.int64 and labels.is_contiguous()
+    if fixed_u is not None:
+        assert fixed_u.dtype == torch.int32 and fixed_u.numel() == A and fixed_u.is_contiguous()
+    dev = labels.device
+    idx = torch.empty(A, dtype=torch.int32, device=dev)
+    lab = torch.empty(A, dtype=torch.int32, device=dev)
+    n_pos = torch.empty(1, dtype=torch.int32, device=dev)
+    need = lib.catseg_contrast_pick_workspace(B, h, w, K)
+    ws = workspace(need, dev)
+    draws = fixed_u is None and not eval_mode
+    with _Timed("hbm:contrast_pick", 8.0 * B * h * w * 2 + 8.0 * A):      # the sampled labels twice (count, select), the slots' outputs
+        check(lib.catseg_contrast_pick(ptr(labels), B, H, W, h, w, K, M, ptr(state) if draws else None, ptr(fixed_u) if fixed_u is not None else None,
+                                       1 if eval_mode else 0, ptr(idx), ptr(lab), ptr(n_pos), ptr(ws), ws.numel(), stream()))
+    return idx, lab, n_pos
+
+
+def contrast_gather(feat, idx, eps, Z=None, inv_norm=None):
+    """feat: NHWC [B, h, w, d] of any pixel stride -> (Z [A, r4(d)], inv_norm [A]): the normalised feature rows of the anchors"""
+    B, h, w, d = feat.shape
+    A = idx.numel()
+    if Z is None:
+        Z = torch.empty((A, r4(d)), dtype=torch.float32, device=feat.device)
+    if inv_norm is None:
+        inv_norm = torch.empty(A, dtype=torch.float32, device=feat.device)
+    with _Timed("hbm:contrast_gather", 4.0 * A * (d + r4(d) + 2)):
+        check(lib.catseg_contrast_gather(ptr(feat), ld_of(feat), B * h * w, d, ptr(idx), A, eps, ptr(Z), ptr(inv_norm), stream()))
+    return Z, inv_norm
+
+
+def contrast_rows(S, A, label, Wt, inv_tau, n_pos, ell=None):
+    """S [A, lds] holds z_i . z_j; -> ell [A]; S is overwritten with G (zeros on the diagonal, in empty rows / columns and the pad columns)"""
+    K = Wt.shape[0]
+    if ell is None:
+        ell = torch.empty(A, dtype=torch.float32, device=S.device)
+    with _Timed("hbm:contrast_rows", 8.0 * A * r4(A)):
+        check(lib.catseg_contrast_rows(ptr(S), S.stride(0), A, ptr(label), ptr(Wt), K, inv_tau, ptr(n_pos), ptr(ell), stream()))
+    return ell
+
+
+def contrast_finalize(ell, n_pos):
+    loss = torch.empty(1, dtype=torch.float32, device=ell.device)
+    with _Timed("hbm:contrast_finalize", 4.0 * ell.numel()):
+        check(lib.catseg_contrast_finalize(ptr(ell), ell.numel(), ptr(n_pos), ptr(loss), stream()))
+    return loss
+
+
+def contrast_scatter_bwd(dZ, Z, inv_norm, idx, d, g, inv_tau, shape):
+    """-> the dense NHWC gradient [B, h, w, d] of the feature map: zero but at the anchors' pixels"""
+    B, h, w, _ = shape
+    A = idx.numel()
+    dfeat = torch.empty((B, h, w, d), dtype=torch.float32, device=dZ.device)
+    with _Timed("hbm:contrast_scatter_bwd", 4.0 * B * h * w * d + 12.0 * A * d):
+        check(lib.catseg_contrast_scatter_bwd(ptr(dZ), ptr(Z), dZ.stride(0), ptr(inv_norm), ptr(idx), A, d, ptr(g), inv_tau, ptr(dfeat), B * h * w,
+                                              stream()))
+    return dfeat

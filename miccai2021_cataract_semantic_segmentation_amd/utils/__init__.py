@@ -15,7 +15,7 @@ from .class_sampling import (OVERSAMPLING_PRESETS, AdaptiveBatchSampler, Shuffle
 
 
 def __getattr__(name):  # metrics need the HIP library: import lazily so CPU-only tooling can use the rest
-    if name in ("t_get_confusion_matrix", "t_get_pixel_accuracy", "t_get_miou", "t_get_mean_iou"):
+    if name in ("t_get_confusion_matrix", "t_get_pixel_accuracy", "t_get_miou", "t_get_mean_iou", "t_normalise_confusion_matrix"):
         from . import metrics
         return getattr(metrics, name)
     if name == "PinnedFrameLoader":

@@ -25,6 +25,20 @@ def t_get_confusion_matrix(prediction, target, existing_matrix=None, no_ignore_c
         return ops.confusion_matrix(rows.reshape(-1, K), lbl.contiguous(), cm)
 
 
+def t_normalise_confusion_matrix(matrix, mode):
+    """utils/torch_utils.py:244-256 of the reference: rows ('row') or columns ('col') divided by their sums, an all-zero one left as it is"""
+    with torch.no_grad():
+        if mode == "row":
+            sums = torch.sum(matrix, dim=1, dtype=torch.float)
+            sums[sums == 0] = 1
+            return matrix.to(torch.float) / sums.unsqueeze(1)
+        if mode == "col":
+            sums = torch.sum(matrix, dim=0, dtype=torch.float)
+            sums[sums == 0] = 1
+            return matrix.to(torch.float) / sums.unsqueeze(0)
+        raise ValueError("Normalise confusion matrix: mode needs to be either 'row' or 'col'.")
+
+
 def t_get_pixel_accuracy(confusion_matrix):
     with torch.no_grad():
         correct = torch.diag(confusion_matrix).to(torch.float)
