@@ -114,6 +114,65 @@ typedef struct {
 } catseg_conv_bwd_weight_desc;
 size_t catseg_conv2d_bwd_weight_workspace(const catseg_conv_desc* geo, int operands);
 int catseg_conv2d_bwd_weight(const catseg_conv_bwd_weight_desc* d, catseg_stream_t stream);
+/* Operand contract of the F32 convolutions: catseg_conv2d_fwd / _bwd_data / _bwd_weight with
+ * CATSEG_OPERANDS_F32.  r4(n) = n rounded up to 4; a "pixel" is a row of ldx / ldy floats.
+ * tests/test_conv_exact_gpu.py holds the kernels, on every tile form, to the sentences about what
+ * is read, what is written and what keeps its bits; the preconditions of the first paragraph
+ * (checked on the host before a launch) and the state of the workspace are not part of that test.
+ *
+ * All directions.  x / dx, y / dy, w / dw 16-byte aligned; ldx, ldy multiples of 4, ldx >= Cin,
+ *   ldy >= Cout; Cin (grouped: Cin / groups) a multiple of 4; every tensor below 2^31 floats.
+ *   Anything else returns CATSEG_EINVAL before a launch.
+ *   The tensors may be channel slices of wider buffers (concatenation views): of the B H W pixels
+ *   of x / dx and the B Ho Wo pixels of y / dy only the columns named below are touched; no float
+ *   in front of the first pixel, behind the last, in front of or behind w, dw, bias or dbias is
+ *   read or written.  A tap that falls outside the image contributes zero: it reads a zero page,
+ *   not a neighbouring row, pixel or image.
+ * w   [Cout][kh][kw][Cin / groups], dense.  Forward and backward-data read exactly these floats:
+ *     nothing has to be zero, no row >= Cout is read.
+ * stem4.  x is the dense 4-channel image (ldx == 4) with a FINITE fourth channel
+ *     (catseg_nchw3_to_nhwc4 writes 0); w / dw are the packed [Cout][kh][8][4] image of
+ *     catseg_stem_pack_weight: entries [..][7][.] and [..][.][3] of w are zero, the same entries
+ *     of dw are written with values that catseg_stem_unpack_grad drops.
+ *
+ * forward
+ *   x         exactly the columns [0, Cin) of the pixels a tap reaches are read; columns
+ *             [Cin, ldx) are never read, whatever they hold.
+ *   bias      [0, Cout) when not NULL.
+ *   residual  columns [0, Cout) of the B Ho Wo pixels of ldr floats; the rest of a pixel is never
+ *             read.
+ *   y         columns [0, Cout) of every pixel are written (previous contents are not read, NaNs
+ *             are overwritten): act((sum + bias) + residual); columns [Cout, zero_to) are written
+ *             as +0; columns [max(Cout, zero_to), ldy) keep their bits.  zero_to <= Cout writes
+ *             no zeros.  Grouped: zero_to == 0 and residual == NULL (CATSEG_EINVAL otherwise).
+ *             There is no accumulating forward.
+ * backward-data
+ *   dy        columns [0, r4(Cout)) of the pixels a tap reaches are read, and the pad columns
+ *             [Cout, r4(Cout)) MUST BE ZERO -- they are multiplied by zeros that stand in for w's
+ *             rows >= Cout, so an Inf / NaN there would reach every column of the dx pixels the
+ *             tap feeds (catseg_conv2d_fwd(zero_to) and catseg_bilinear_bwd(zero_to) write these
+ *             zeros); columns [r4(Cout), ldy) are never read.  Grouped: Cout / groups is a
+ *             multiple of 4, there are no pad columns.
+ *   dx        columns [0, Cin) of EVERY pixel are written or added to; columns [Cin, ldx) keep
+ *             their bits.  accumulate == 0: previous contents are not read, and a pixel no tap
+ *             reaches (a parity class of a strided convolution without a tap) is written as +0.
+ *             accumulate != 0: dx = dx + sum, the sum formed first; a pixel no tap reaches keeps
+ *             its value.
+ * backward-weight
+ *   x         exactly the columns [0, Cin) of the pixels a tap reaches.
+ *   dy        the B Ho Wo pixels only (the last K-step of 16 rows is filled with zeros, not with
+ *             rows behind the tensor).  Columns [0, r4(Cout)) are read; the pad columns
+ *             [Cout, r4(Cout)) may hold anything (they meet only accumulators that are not
+ *             stored).  With dbias != NULL, ldy == 32 and Cout <= 32 all 32 columns are read, and
+ *             [Cout, 32) may hold anything as well.  Other columns are never read.
+ *   dw        all of [Cout][kh][kw][Cin / groups] is written (previous contents are not read),
+ *             with or without a K split, through the implicit GEMM or the direct 48 / 96-channel
+ *             kernel; dbias [0, Cout) when not NULL.  Nothing else is written: the partial sums of
+ *             a split live in the workspace, whose contents are undefined afterwards.
+ *
+ * The summation order depends on the tile form, the split count and the kernel (and is fixed for a
+ * given shape and plan): results are deterministic, and bit-identical across forms only where the
+ * sums are exact. */
 /* w'[o,:] = w[o,:] * gamma[o]/sqrt(rv[o]+eps), b'[o] = beta[o] + (b[o] - rm[o]) * gamma[o]/sqrt(rv[o]+eps);
  * per_out = floats per output channel of w (kh*kw*Cin, or 7*32 for the packed stem) */
 int catseg_fold_bn(const float* w, const float* bias, const float* gamma, const float* beta, const float* running_mean,
